@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the MVNeRF render hot path on MI355X (BASELINE.json metric: rendered rays/sec).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` (rays/s), `ms_per_step` and the `roofline`
+of the field kernel, read from HIP events recorded inside those K steps.  `--full` adds what needs runs of its own: the two
+training legs (`train_step`, `train_cfg4`, `--train-steps`) and, at N = 1, the torch-CPU baseline and the parity check against
+the NumPy oracle (`cpu_baseline`, `parity`, `--cpu-baseline`).  `--dump-outputs DIR` writes the last timed step's results
+(rgb, depth, fine_rgb, fine_depth) as float32 `DIR/<name>.npy` after the timed steps; rank k > 0 writes `DIR/rank<k>_<name>.npy`.
+The inputs are seeded (synthetic.make_scene), so the same arguments give the same inputs in every run.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 `torch.distributed.run`, spawned before this process touches the GPU or loads the HIP library) and relays rank 0's line.
@@ -30,7 +37,7 @@ same peak - 2.6x lower, the price of fp32-grade products on a 16-bit pipe.  `--f
 (exact three-piece bf16 cut, six v_mfma_f32_16x16x32_bf16 per block: round 3's first default).  `--f32-gemm mfma_f32` times `field_eval_kernel` on the
 fp32 MFMA (v_mfma_f32_32x32x2_f32, 4 096 FLOP each, peak 157.3 TFLOP/s).  Durations are HIP events inside the timed region;
 `traffic` / `traffic_ratio` / `mfma_busy_pmc` come from the committed rocprofv3 counter passes (`traffic_source`).
-`cpu_baseline` times the op-for-op torch-CPU restatement of the reference's TF graph (oracle/mvnerf_torch.py, fp32; the reference
+With `--full`: `cpu_baseline` times the op-for-op torch-CPU restatement of the reference's TF graph (oracle/mvnerf_torch.py, fp32; the reference
 itself cannot run here) on all 4096 rays on the host cores; `parity` checks the GPU result against the NumPy oracle on all 4096
 rays.  `train_cfg4` is the data-parallel training leg (BASELINE.json configs[3]): one 128x128 scene = 16 384 rays per GPU,
 forward with stash + backward + ONE flat all-reduce of the 494 600 gradients + clip + Adam.
@@ -48,6 +55,7 @@ sys.path.insert(0, ROOT)
 FLOP_PER_SAMPLE_V1 = 491264          # BASELINE.md 3 (2 x 245 632 MAC), one source view
 PEAK_FP32_MFMA_TFLOPS = 157.3        # MI355X_MICROARCH.md, chip-level parameters
 METRIC = 'rendered rays/sec (64 samples/ray) at 1/2/4/8 MI355X; RGB L1 vs ref'
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs, all files of all ranks together
 
 
 def reference_flop_per_sample(v):
@@ -119,18 +127,24 @@ def main():
     ap.add_argument('--height', type=int, default=0, help='source image height (default: --size)')
     ap.add_argument('--width', type=int, default=0, help='source image width (default: --size)')
     ap.add_argument('--rays', type=int, default=0, help='random target pixels instead of every pixel of a size x size view (e.g. cfg5: 16384 rays, 480x640 sources)')
-    ap.add_argument('--cpu-baseline', default='on', choices=['on', 'off'], help='N=1: time the torch-CPU restatement and check parity on all rays')
+    ap.add_argument('--cpu-baseline', default='on', choices=['on', 'off'], help='with --full, N=1: time the torch-CPU restatement and check parity on all rays')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='bf16: both field passes on the bf16 MFMA kernel (configs 3/5; not the headline)')
     ap.add_argument('--f32-gemm', default='split_f16', choices=['mfma_f32', 'split_bf16', 'split_f16'],
                     help='fp32 Dense layers on the fp32 MFMA, or fp32-grade on the 16-bit matrix pipe: three fp16 MFMAs per product block on two-piece operands (default) or six bf16 MFMAs on exactly cut three-piece operands')
     ap.add_argument('--texel-table', default='auto', choices=['auto', 'on', 'off'],
                     help="hoist layer 0's feature rows to a per-texel table rebuilt every step (auto: when R*S >= 2*H*W)")
     ap.add_argument('--train-steps', type=int, default=5,
-                    help='timed train_step calls of the two training legs (cfg2 scene at N=1; cfg4 128x128 scene per GPU with the gradient all-reduce at every N); 0 = skip')
+                    help='with --full: timed train_step calls of the two training legs (cfg2 scene at N=1; cfg4 128x128 scene per GPU with the gradient all-reduce at every N); 0 = skip')
     ap.add_argument('--fused-call', action='store_true', help='time mvnerf_render_fwd (one C call) instead of the op sequence')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'],
                     help='weak: one cfg2 scene per GPU (default, the driver\'s run); strong: the 16 384 rays of ONE 128x128 scene (cfg4) split over the ranks')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the training legs (--train-steps) and, at N=1, the torch-CPU baseline with the oracle parity check (--cpu-baseline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write the last timed step's rgb, depth, fine_rgb, fine_depth as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args))
@@ -234,6 +248,8 @@ def main():
     elapsed = time.perf_counter() - t0
     red_dev = dev if backend == 'nccl' else 'cpu'
     elapsed = max_over_ranks(elapsed, red_dev)   # the slowest rank's clock (no-op at world 1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(['rgb', 'depth', 'fine_rgb', 'fine_depth'], out)), rank, world)
 
     rays_per_step = total_rays if strong else b * r * world
     ms_per_step = 1e3 * elapsed / args.steps
@@ -241,7 +257,7 @@ def main():
 
     result = {
         'metric': METRIC, 'value': value, 'unit': 'rays/s', 'n_gpus': world, 'steps': args.steps,
-        'warmup': args.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': args.scaling,
+        'warmup': args.warmup, 'full': args.full, 'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': args.scaling,
         'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic', 'f32_gemm': None if bf16 else args.f32_gemm,
         'config': {'workload': (f'cfg4 strong leg: ONE scene of {total_rays} rays split over {world} rank(s) by shard_bounds ({r} rays on rank 0), ' if strong else 'cfg2: ') +
                                f'_call on B=1 scene/GPU, V={args.views} source view {img_h}x{img_w}x(3+256) fp32, '
@@ -340,7 +356,7 @@ def main():
             except Exception:
                 pass
 
-    if args.train_steps > 0 and not bf16:
+    if args.full and args.train_steps > 0 and not bf16:
         # the training legs are reported beside the headline, never instead of it: a failure in one of them (it would be the same on every
         # rank: they run the same code on the same shapes) is recorded and the line is still printed
         if world == 1 and not strong:
@@ -355,11 +371,26 @@ def main():
         if rank == 0:
             result['train_cfg4'] = leg
     if rank == 0:
-        if world == 1 and args.cpu_baseline == 'on' and (img_h, img_w) == (64, 64) and args.views == 1 and not args.rays and not strong:
+        if args.full and world == 1 and args.cpu_baseline == 'on' and (img_h, img_w) == (64, 64) and args.views == 1 and not args.rays and not strong:
             result['cpu_baseline'], result['parity'] = cpu_baseline(sc, out)
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: each (B, R, ...) array of the last timed step as float32 .npy (rank 0: <name>.npy, rank k: rank<k>_<name>.npy).
+    Above DUMP_LIMIT_BYTES over all ranks, a fixed seeded sample of the rays (the same rays of every array, in ray order) is written."""
+    import numpy as np
+    host = {k: v.detach().cpu().numpy().astype(np.float32, copy=False) for k, v in arrays.items()}
+    total, limit = sum(a.nbytes for a in host.values()), DUMP_LIMIT_BYTES // world
+    if total > limit:
+        n_rays = next(iter(host.values())).shape[1]
+        idx = np.sort(np.random.default_rng(0).choice(n_rays, max(1, n_rays * limit // total), replace=False))
+        host = {k: a[:, idx] for k, a in host.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, (f'rank{rank}_' if rank else '') + k + '.npy'), np.ascontiguousarray(a))
 
 
 def train_throughput(sc, t, n_views, dev, steps):

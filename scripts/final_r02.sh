@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/final_r02; mkdir -p $OUT
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo pytest rc=$? "$(tail -1 $OUT/pytest.log)"
-timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo bench rc=$?; cat $OUT/bench.json
+timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo bench rc=$?; cat $OUT/bench.json
 timeout -k 10 200 python scripts/train_bench.py --steps 20 > $OUT/train_bench.log 2>&1; tail -1 $OUT/train_bench.log
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_train -- python scripts/train_bench.py --steps 5 > $OUT/trace_train.log 2>&1; echo trace_train rc=$?
 python scripts/summarize_trace.py $OUT/trace_train > $OUT/trace_train_summary.txt 2>&1

@@ -9,4 +9,4 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_train -- pyth
 python scripts/summarize_trace.py $OUT/trace_train > $OUT/trace_train.md
 bash scripts/pmc_split.sh $OUT/pmc_split
 python scripts/summarize_pmc.py $OUT/pmc_split > $OUT/pmc_split.md
-python bench.py --steps 50 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; echo bench rc=$?
+python bench.py --steps 50 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo bench rc=$?

@@ -103,7 +103,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(MVNERF_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--train-steps', '1'],
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--train-steps', '1', '--full'],
                           env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith('{')]
@@ -123,7 +123,7 @@ def test_bench_strong_scaling_leg(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(MVNERF_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--scaling', 'strong', '--steps', '2', '--warmup', '1',
-                           '--train-steps', '1'], env=env, capture_output=True, text=True, timeout=900)
+                           '--train-steps', '1', '--full'], env=env, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     d = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith('{')][0])
     assert d['n_gpus'] == 2 and d['scaling'] == 'strong' and d['config']['rays_per_gpu'] == 8192
