@@ -413,6 +413,38 @@ int mvnerf_grasp_head_vjp(const float* g_y, const float* c, const float* y, cons
 int mvnerf_grasp_head_vjp_bwd(const float* t_acts, const float* g_y, const float* c, const float* y, const float* q, const float* packed, long N,
                               float* out_gy, float* r, float* m, float* p, mvnerf_stream_t stream);
 
+/* ---- the grasp-pose optimiser (DNGFOptimizer, lmvnerf/grasp_optimizer.py:28-184; its loop, utils/optimization.py:40-152): the pose side
+ * of one optimisation step.  P poses: t (P, 3), rot (P, 4) quaternion (x, y, z, w; rep 0) or (P, 6) 6d ([r1 | r2]; rep 1); offsets (n5, 4, 4)
+ * = LanguageNeRF.transforms_to_check (model_v4.py:67-101).  The query tensors hold B scenes of `ld` rows (ld >= P * n5, padding rows are
+ * left alone), row p * n5 + o = (pose p, offset o). */
+
+/* compute_matrices (grasp_optimizer.py:113-124: tfg from_quaternion with q as given, or the 6d form normalise-and-cross) followed by
+ * LanguageNeRF._query_points (model_v4.py:222-226): points[b, p n5 + o] = R_p t_o + t_p, dirs[b, p n5 + o] = R_p z_o, the same for
+ * every scene b (the reference tiles the matrices over B, grasp_optimizer.py:97-98).  points, dirs: (B, ld, 3). */
+int mvnerf_pose_query_points(const float* t, const float* rot, int rep, const float* offsets, int P, int n5, int B, long ld, float* points,
+                             float* dirs, mvnerf_stream_t stream);
+/* The vector-Jacobian product of mvnerf_pose_query_points: d_points, d_dirs (B, ld, 3) -> d_t (P, 3), d_rot (P, 4|6), both multiplied by
+ * `scale` (-1: the gradient of loss = -success, grasp_optimizer.py:177).  Fixed-order sums (bit-identical from run to run). */
+int mvnerf_pose_query_vjp(const float* rot, int rep, const float* offsets, const float* d_points, const float* d_dirs, int P, int n5, int B,
+                          long ld, float scale, float* d_t, float* d_rot, mvnerf_stream_t stream);
+
+/* optimize(opt, var, g, 1.0) for each trained variable (grasp_optimizer.py:179-182; nerf_utils.py:8-12: clip-by-value, then
+ * tf.keras.optimizers.Adam with ExponentialDecay(lr0, decay_steps=1, decay, staircase=False), optimization.py:47-61), then post_process
+ * (grasp_optimizer.py:126-139) of every pose.  Step k of variable v uses lr = lr0[v] decay[v]^(k-1), alpha = lr sqrt(1 - beta2^k) /
+ * (1 - beta1^k); m += (g - m)(1 - beta1); v += (g^2 - v)(1 - beta2); x -= alpha m / (sqrt(v) + eps).
+ * train_flags (2) int32: variable 0 = t, 1 = rot is stepped when non-zero.  counters (2, P) int32: the step count k of each variable, per
+ * pose, advanced on the device by the thread that owns the pose (the two Keras optimisers' `iterations`).  Nothing per step comes from the
+ * host: a captured step serves both phases, the caller switches them by writing train_flags on the stream. */
+typedef struct mvnerf_pose_adam_config {
+    float lr0[2], decay[2];            /* [0] translations, [1] rotations */
+    float beta1, beta2, eps, clip;     /* clip <= 0: no clip-by-value */
+    int clip_translation;              /* clip t to [lo, hi] per axis (workspace_bounds) */
+    float lo[3], hi[3];
+} mvnerf_pose_adam_config;
+/* cfg is [host]; g_t, m_t, v_t, t: (P, 3); g_rot, m_r, v_r, rot: (P, 4|6).  In place on t, rot, m_*, v_*, counters. */
+int mvnerf_pose_adam_step(const mvnerf_pose_adam_config* cfg, int rep, int P, const int* train_flags, int* counters, const float* g_t,
+                          const float* g_rot, float* m_t, float* v_t, float* m_r, float* v_r, float* t, float* rot, mvnerf_stream_t stream);
+
 /* ---- the whole training step behind one call (MVVNeRFRenderer.train_step, model_v0.py:186-197: GradientTape over call(),
  * loss = MSE(y, rgb) + MSE(y, fine_rgb) :193, gradients :194, optimize() :195 = nerf_utils.py:8-12) ----
  * The matching `_bwd` of mvnerf_render_fwd: a host in any language takes a training step with these entry points and

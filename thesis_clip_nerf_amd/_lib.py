@@ -35,6 +35,12 @@ class AdamState(ctypes.Structure):
                 ('clip', c_float), ('update_mask', c_void_p), ('repack', c_int)]
 
 
+class PoseAdamConfig(ctypes.Structure):
+    """mvnerf_pose_adam_config (include/mvnerf_hip.h)."""
+    _fields_ = [('lr0', c_float * 2), ('decay', c_float * 2), ('beta1', c_float), ('beta2', c_float), ('eps', c_float), ('clip', c_float),
+                ('clip_translation', c_int), ('lo', c_float * 3), ('hi', c_float * 3)]
+
+
 class GemmTnBatch(ctypes.Structure):
     """mvnerf_gemm_tn_batch (include/mvnerf_hip.h)."""
     _fields_ = ([(n, c_void_p) for n in ('g', 'a', 'g2', 'a2')] +
@@ -110,6 +116,9 @@ SIGNATURES = {
     'mvnerf_grasp_head_fwd': (c_int, [c_void_p] * 4 + [c_long] + [c_void_p] * 3),
     'mvnerf_grasp_head_vjp': (c_int, [c_void_p] * 4 + [c_long] + [c_void_p] * 5),
     'mvnerf_grasp_head_vjp_bwd': (c_int, [c_void_p] * 6 + [c_long] + [c_void_p] * 5),
+    'mvnerf_pose_query_points': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_pose_query_vjp': (c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_long, c_float, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_pose_adam_step': (c_int, [ctypes.POINTER(PoseAdamConfig), c_int, c_int] + [c_void_p] * 11),
     'mvnerf_train_workspace_bytes': (c_size_t, [c_int] * 8),
     'mvnerf_loss_and_grads': (c_int, [ctypes.POINTER(TrainCall), c_void_p]),
     'mvnerf_apply_gradients': (c_int, [ctypes.POINTER(TrainCall), ctypes.POINTER(AdamState), c_void_p]),

@@ -1038,3 +1038,96 @@ def query_vjp(points, dirs, images, features, intrinsics, extrinsics_inv, bwd_st
                                          _p(d_dirs), _stream(points))
     _lib.check(rc, 'query_vjp')
     return d_points, d_dirs
+
+
+# ---- the grasp-pose optimiser's pose side (csrc/pose_ops.hip; lmvnerf/grasp_optimizer.py:113-184, utils/optimization.py:40-69) ---------
+POSE_REPS = {4: 0, 6: 1}          # rotation width -> rep (0 quaternion x y z w, 1 6d)
+
+
+def _rot_shape(rot):
+    _chk(rot, 'rot')
+    if rot.dim() not in (2, 3) or rot.shape[-1] not in POSE_REPS or (rot.dim() == 3 and rot.shape[0] != 1):
+        raise ValueError(f'rot: shape {tuple(rot.shape)}, expected (P, 4|6) or (1, P, 4|6)')
+    return rot.shape[-2], POSE_REPS[rot.shape[-1]], rot.shape[-1]
+
+
+def _pose_shapes(t, rot):
+    _chk(t, 't')
+    _chk(rot, 'rot')
+    if t.dim() not in (2, 3) or t.shape[-1] != 3 or (t.dim() == 3 and t.shape[0] != 1):
+        raise ValueError(f't: shape {tuple(t.shape)}, expected (P, 3) or (1, P, 3)')
+    p = t.shape[-2]
+    if rot.dim() != t.dim() or rot.shape[-1] not in POSE_REPS or rot.numel() != p * rot.shape[-1]:
+        raise ValueError(f'rot: shape {tuple(rot.shape)}, expected (P, 4) or (P, 6) with P = {p}')
+    return p, POSE_REPS[rot.shape[-1]], rot.shape[-1]
+
+
+def pose_query_points(t, rot, offsets, n_scenes=1, ld=None, out=None):
+    """mvnerf_pose_query_points: poses -> (points, dirs), each (n_scenes, ld, 3), rows p * n5 + o (ld defaults to P * n5; rows past P * n5
+    are not written).  out: a (points, dirs) pair to write into."""
+    p, rep, _ = _pose_shapes(t, rot)
+    _chk(offsets, 'offsets', shape=(None, 4, 4))
+    n5 = offsets.shape[0]
+    ld = p * n5 if ld is None else int(ld)
+    if out is None:
+        out = tuple(torch.empty((n_scenes, ld, 3), dtype=torch.float32, device=t.device) for _ in range(2))
+    points, dirs = out
+    _chk(points, 'points', shape=(n_scenes, ld, 3))
+    _chk(dirs, 'dirs', shape=(n_scenes, ld, 3))
+    with torch.cuda.device(t.device):
+        rc = _lib.lib().mvnerf_pose_query_points(_p(t), _p(rot), rep, _p(offsets), p, n5, int(n_scenes), ld, _p(points), _p(dirs), _stream(t))
+    _lib.check(rc, 'pose_query_points')
+    return points, dirs
+
+
+def pose_query_vjp(rot, offsets, d_points, d_dirs, scale=1.0, out=None):
+    """mvnerf_pose_query_vjp: (d_points, d_dirs) (B, ld, 3) -> scale * (d_t (P, 3), d_rot (P, 4|6)), fixed-order sums."""
+    p, rep, rd = _rot_shape(rot)
+    _chk(offsets, 'offsets', shape=(None, 4, 4))
+    n5 = offsets.shape[0]
+    _chk(d_points, 'd_points', shape=(None, None, 3))
+    b, ld, _ = d_points.shape
+    _chk(d_dirs, 'd_dirs', shape=(b, ld, 3))
+    if out is None:
+        out = (torch.empty((p, 3), dtype=torch.float32, device=rot.device), torch.empty((p, rd), dtype=torch.float32, device=rot.device))
+    d_t, d_rot = out
+    _chk(d_t, 'd_t', shape=(p, 3))
+    _chk(d_rot, 'd_rot', shape=(p, rd))
+    with torch.cuda.device(rot.device):
+        rc = _lib.lib().mvnerf_pose_query_vjp(_p(rot), rep, _p(offsets), _p(d_points), _p(d_dirs), p, n5, b, ld, float(scale), _p(d_t),
+                                              _p(d_rot), _stream(rot))
+    _lib.check(rc, 'pose_query_vjp')
+    return d_t, d_rot
+
+
+def pose_adam_config(lr0=(0.09, 0.09), decay=(1.0, 1.0), beta1=0.9, beta2=0.999, eps=1e-7, clip=1.0, clip_translation=False, bounds=None):
+    """mvnerf_pose_adam_config: lr0 / decay per variable (translations, rotations); bounds (3, 2) = workspace_bounds."""
+    bounds = np.zeros((3, 2)) if bounds is None else np.asarray(bounds, dtype=np.float64).reshape(3, 2)
+    c = _lib.PoseAdamConfig()
+    c.lr0[0], c.lr0[1] = float(lr0[0]), float(lr0[1])
+    c.decay[0], c.decay[1] = float(decay[0]), float(decay[1])
+    c.beta1, c.beta2, c.eps, c.clip = float(beta1), float(beta2), float(eps), float(clip)
+    c.clip_translation = int(bool(clip_translation))
+    for i in range(3):
+        c.lo[i], c.hi[i] = float(bounds[i, 0]), float(bounds[i, 1])
+    return c
+
+
+def pose_adam_step(cfg, train_flags, counters, g_t, g_rot, m_t, v_t, m_r, v_r, t, rot):
+    """mvnerf_pose_adam_step: clip, Keras Adam with the decayed rate from the device-side counters (2, P) int32 of the variables that
+    train_flags (2,) int32 marks, post_process; in place on t, rot, m_*, v_*, counters."""
+    p, rep, rd = _pose_shapes(t, rot)
+    _chk(train_flags, 'train_flags', dtype=torch.int32, shape=(2,))
+    _chk(counters, 'counters', dtype=torch.int32, shape=(2, p))
+    for x, n in ((g_t, 'g_t'), (m_t, 'm_t'), (v_t, 'v_t')):
+        _chk(x, n)
+        if x.numel() != 3 * p:
+            raise ValueError(f'{n}: {x.numel()} floats, expected {3 * p}')
+    for x, n in ((g_rot, 'g_rot'), (m_r, 'm_r'), (v_r, 'v_r')):
+        _chk(x, n)
+        if x.numel() != rd * p:
+            raise ValueError(f'{n}: {x.numel()} floats, expected {rd * p}')
+    with torch.cuda.device(t.device):
+        rc = _lib.lib().mvnerf_pose_adam_step(ctypes.byref(cfg), rep, p, _p(train_flags), _p(counters), _p(g_t), _p(g_rot), _p(m_t),
+                                              _p(v_t), _p(m_r), _p(v_r), _p(t), _p(rot), _stream(t))
+    _lib.check(rc, 'pose_adam_step')
