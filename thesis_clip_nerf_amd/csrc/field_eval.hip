@@ -9,62 +9,21 @@
 // (half a coarse ray, a quarter of a fine ray), waves are independent (no workgroup barrier).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <mutex>
 
+#include "mvnerf_field_common.h"
 #include "mvnerf_kernels.h"
 #include "mvnerf_math.h"
 #include "mvnerf_pack.h"
 
 namespace mvnerf {
 
-
-// Launch shape: measured best ("Field kernel: what was measured") is the plain one: one
-// 32-sample tile per wave, 4 waves per workgroup, 2 workgroups per CU (2 waves per SIMD).  The
-// persistent / ticket-queue / raised-priority forms below are kept as build switches for A/B runs.
-
-// Tuning switches (A/B-tested on the GPU, see DESIGN.md "Field kernel: what was measured")
-#ifndef MV_PERSIST
-#define MV_PERSIST 0       // 1: one workgroup per CU pulling tiles from an atomic ticket; 0: one tile per wave
-#endif
-#ifndef MV_PRIO
-#define MV_PRIO 0          // raise the priority of waves 0..3 of an 8-wave workgroup
-#endif
-#ifndef MV_ABL_PE
-#define MV_ABL_PE 0        // timing-only ablations (wrong results): skip sin/cos
-#endif
-#ifndef MV_ABL_GATHER
-#define MV_ABL_GATHER 0    // skip feature gather + lerp + LDS staging
-#endif
-#ifndef MV_ABL_BIAS
-#define MV_ABL_BIAS 0      // skip bias loads
-#endif
-#ifndef MV_ABL_WLOAD
-#define MV_ABL_WLOAD 0     // do not stream weights (re-use the first 4 chunks)
-#endif
-#ifndef MV_PIN_LOADS
-#define MV_PIN_LOADS 1
-#endif
-#ifndef MV_ASM_RELU
-#define MV_ASM_RELU 0
-#endif
-#ifndef MV_PE_RECUR
-#define MV_PE_RECUR 1      // double-angle recurrence between accurate sin/cos at octaves 0 and 5
-#endif
-#ifndef MV_FMA_LERP
-#define MV_FMA_LERP 1      // feature lerps as FMAs (6 instead of 9 VALU per channel); taps/indices unaffected
-#endif
-#ifndef MV_MV_OCC
-#define MV_MV_OCC 2        // waves per SIMD the multi-view kernels are compiled for: 2 spills the view sum to
-                           // scratch (132 B/lane) and is still 5 % faster than 1 (A/B, V=3: 745k -> 786k rays/s)
-#endif
-#ifndef MV_WAVES
-#define MV_WAVES 4         // waves per workgroup of the single-view kernel (4 or 8)
-#endif
-
-}  // namespace mvnerf
-#include "mvnerf_field_common.h"
-namespace mvnerf {
+// Launch shape: measured best ("What was measured on the way") is the plain one: one 32-sample tile per wave,
+// 4 waves per workgroup, 2 workgroups per CU (2 waves per SIMD).  Persistent workgroups pulling tiles from an atomic ticket
+// (0.739 of peak against 0.769), with raised priority for half of their waves (0.736), were slower.
+constexpr int kWaves = 4;          // waves per workgroup of the single-view kernel
+constexpr int kMvOcc = 2;          // waves per SIMD the multi-view kernels are compiled for: 2 spills the view sum to
+                                   // scratch (132 B/lane) and is still 5 % faster than 1 (A/B, V=3: 745k -> 786k rays/s)
 
 // acc += W^T relu(in)   (Dense 128->128 on the pre-activated input, layers.py:285-288)
 __device__ __forceinline__ void dense128(WStream& ws, const f32x16 (&in)[4], f32x16 (&acc)[4]) {
@@ -99,7 +58,7 @@ __device__ __forceinline__ void resnet_block(WStream& ws, const float* __restric
 // layer 0 is linear in the gathered features and the bilinear gather is linear in the texels, so
 // W0f^T lerp(taps) = lerp(W0f^T taps); the lerp then runs on 128 projected channels and adds into the accumulators.
 template <bool kMultiView, bool kStash, bool kProj>
-__global__ __launch_bounds__(kMultiView ? 256 : 64 * MV_WAVES, kMultiView ? MV_MV_OCC : 2) void field_eval_kernel(FieldParams p) {
+__global__ __launch_bounds__(kMultiView ? 256 : 64 * kWaves, kMultiView ? kMvOcc : 2) void field_eval_kernel(FieldParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];       // 16 KiB per wave
 
     const int lane = threadIdx.x & 63;
@@ -107,17 +66,9 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * MV_WAVES, kMultiView ? MV_M
     const int j = lane & 31;
     const int h = lane >> 5;
     float* stage = lds + wave * (kTile * kStageRow);
-    if (MV_PRIO && !kMultiView && MV_WAVES == 8 && wave < 4) __builtin_amdgcn_s_setprio(1);
 
-  for (;;) {                                             // persistent: one 32-sample tile per trip
-#if MV_PERSIST
-    unsigned ticket = 0;
-    if (lane == 0) ticket = atomicAdd(p.tile_counter, 1u);
-    const long tile = (long)__builtin_amdgcn_readfirstlane(ticket);
-#else
-    const long tile = (long)blockIdx.x * (blockDim.x >> 6) + wave;
-#endif
-    if (tile >= p.n_tiles) break;                        // whole wave leaves; there are no barriers
+    const long tile = (long)blockIdx.x * (blockDim.x >> 6) + wave;   // one 32-sample tile per wave
+    if (tile >= p.n_tiles) return;                       // whole wave leaves; there are no barriers
 
     long g = tile * kTile + j;
     const bool valid = g < p.total;
@@ -174,12 +125,8 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * MV_WAVES, kMultiView ? MV_M
                 // fl32(x * fl32(pi*2^k)) == 2^k * fl32(x * fl32(pi)) exactly, so octave k is the k-fold double
                 // angle of octave 0.  Accurate sin/cos at k = 0 and k = 5, double-angle steps in between (error
                 // x16 at most: ~2e-6 absolute against the 1e-4 bar; the op-level position_encoding is exact).
-                if (!MV_PE_RECUR || k == 0 || k == 5) {
-#if MV_ABL_PE
-                    sk = a0; ck = a0 + 1.0f;
-#else
+                if (k == 0 || k == 5) {
                     sincos_f32(a0 * (float)(1 << k), &sk, &ck);
-#endif
                 } else {
                     const float s2 = sk + sk;
                     const float cn = fmaf(-s2, sk, 1.0f);              // cos 2t = 1 - 2 sin^2 t
@@ -204,7 +151,7 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * MV_WAVES, kMultiView ? MV_M
 #pragma unroll
         for (int gq = 0; gq < 8; ++gq) {
             const float bb[4] = {pe[4 * gq], pe[4 * gq + 1], pe[4 * gq + 2], pe[4 * gq + 3]};
-            if (kProj && gq == 7 - ws_jump_lead()) ws.pos = kPackHidden * 4;   // the stream skips the 32 feature groups
+            if (kProj && gq == 7) ws.pos = kPackHidden * 4;   // the stream skips the 32 feature groups
             mfma_step(ws, bb, x);
         }
         if (kProj) {
@@ -242,25 +189,21 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * MV_WAVES, kMultiView ? MV_M
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // earlier reads of `stage` are done
             const f32x4* fbase = reinterpret_cast<const f32x4*>(p.features) + hf * 32 + j;
 #pragma unroll 4
-            for (int it = 0; it < (MV_ABL_GATHER ? 0 : 16); ++it) {
+            for (int it = 0; it < 16; ++it) {
                 const int src = 2 * it + h;                           // sample whose row this half-wave loads
                 const int tls = __shfl(tl, src);
                 const float axs = __shfl(tp.ax, src), ays = __shfl(tp.ay, src);
                 const f32x4* f = fbase + (long)tls * 64;
                 const f32x4 vtl = f[0], vtr = f[64], vbl = f[(long)p.W * 64], vbr = f[(long)p.W * 64 + 64];
                 f32x4 o;
-#if MV_FMA_LERP
-                // same bilinear form as tfa (lerp x, then y), each lerp as one FMA after the difference
+                // same bilinear form as tfa (lerp x, then y), each lerp as one FMA after the difference (6 instead of 9 vector
+                // instructions per channel)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float top = fmaf(axs, vtr[c] - vtl[c], vtl[c]);
                     const float bot = fmaf(axs, vbr[c] - vbl[c], vbl[c]);
                     o[c] = fmaf(ays, bot - top, top);
                 }
-#else
-#pragma unroll
-                for (int c = 0; c < 4; ++c) o[c] = bilerp(vtl[c], vtr[c], vbl[c], vbr[c], axs, ays);
-#endif
                 *reinterpret_cast<f32x4*>(stage + stage_offset(src, j)) = o;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // writes landed (same-wave DS order)
@@ -338,10 +281,6 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * MV_WAVES, kMultiView ? MV_M
         out[3] = softplus_f32(o[3]);
         *reinterpret_cast<f32x4*>(p.rgbs + 4 * g) = out;
     }
-#if !MV_PERSIST
-    break;
-#endif
-  }
 }
 
 // ---- per-(view, ray) layer-0 seed: b0 + W0[60:120]^T PE(cam dir)  (the direction is constant along a ray) ----
@@ -497,21 +436,8 @@ hipError_t launch_pack_net(const float* net_keras, float* packed, hipStream_t st
     return hipGetLastError();
 }
 
-// Ticket counters for the persistent kernel: a small ring of device words so that launches in flight
-// on different streams never share one; the slot is zeroed on the launch stream right before use.
-constexpr int kCounterSlots = 64;
-__device__ unsigned int g_tile_counters[kCounterSlots];
-
 namespace {
-struct DeviceInfo {
-    int cus = 0;
-    unsigned int* counters = nullptr;
-    bool attr_set = false;
-};
-DeviceInfo g_dev[16];
-#if MV_PERSIST
-std::atomic<unsigned> g_launch_seq{0};
-#endif
+bool g_attr_set[16] = {};            // per device: the kernels' LDS limits are raised
 std::mutex g_dev_mutex;
 }  // namespace
 
@@ -521,20 +447,15 @@ hipError_t launch_dir_bias(const FieldParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_field_eval(const FieldParams& p_in, hipStream_t stream) {
+hipError_t launch_field_eval(const FieldParams& p, hipStream_t stream) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 16) return hipErrorInvalidDevice;
-    DeviceInfo& di = g_dev[dev];
     {
         std::lock_guard<std::mutex> lock(g_dev_mutex);
-        if (!di.attr_set) {
-            hipDeviceProp_t prop;
-            if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-            di.cus = prop.multiProcessorCount;
-            if ((e = hipGetSymbolAddress(reinterpret_cast<void**>(&di.counters), HIP_SYMBOL(g_tile_counters))) != hipSuccess) return e;
-            const int lds_sv = MV_WAVES * kTile * kStageRow * 4, lds_mv = 4 * kTile * kStageRow * 4;
+        if (!g_attr_set[dev]) {
+            const int lds_sv = kWaves * kTile * kStageRow * 4, lds_mv = 4 * kTile * kStageRow * 4;
             const struct { const void* fn; int bytes; } kernels[] = {
                 {reinterpret_cast<const void*>(&field_eval_kernel<false, false, false>), lds_sv},
                 {reinterpret_cast<const void*>(&field_eval_kernel<false, false, true>), lds_sv},
@@ -547,20 +468,12 @@ hipError_t launch_field_eval(const FieldParams& p_in, hipStream_t stream) {
             };
             for (const auto& k : kernels)
                 if ((e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes)) != hipSuccess) return e;
-            di.attr_set = true;
+            g_attr_set[dev] = true;
         }
     }
-    FieldParams p = p_in;
-    p.tile_counter = nullptr;
-#if MV_PERSIST
-    p.tile_counter = di.counters + (g_launch_seq.fetch_add(1) % kCounterSlots);
-    if ((e = launch_zero(p.tile_counter, sizeof(unsigned int), stream)) != hipSuccess) return e;
-#endif
     if ((e = launch_dir_bias(p, stream)) != hipSuccess) return e;
-    const int waves = p.V > 1 ? 4 : MV_WAVES;
-    const long want = (p.n_tiles + waves - 1) / waves;
-    const long resident = (long)di.cus * (p.V > 1 ? 1 : 8 / MV_WAVES);   // workgroups that fit at once
-    const unsigned wgs = (unsigned)((MV_PERSIST && want > resident) ? resident : want);
+    const int waves = p.V > 1 ? 4 : kWaves;
+    const unsigned wgs = (unsigned)((p.n_tiles + waves - 1) / waves);
     const size_t lds_bytes = (size_t)waves * kTile * kStageRow * 4;
     if (p.V > 1) {
         if (p.stash) {
@@ -573,12 +486,12 @@ hipError_t launch_field_eval(const FieldParams& p_in, hipStream_t stream) {
             hipLaunchKernelGGL((field_eval_kernel<true, false, false>), dim3(wgs), dim3(256), lds_bytes, stream, p);
         }
     } else if (p.stash) {
-        if (p.texel_table) hipLaunchKernelGGL((field_eval_kernel<false, true, true>), dim3(wgs), dim3(64 * MV_WAVES), lds_bytes, stream, p);
-        else hipLaunchKernelGGL((field_eval_kernel<false, true, false>), dim3(wgs), dim3(64 * MV_WAVES), lds_bytes, stream, p);
+        if (p.texel_table) hipLaunchKernelGGL((field_eval_kernel<false, true, true>), dim3(wgs), dim3(64 * kWaves), lds_bytes, stream, p);
+        else hipLaunchKernelGGL((field_eval_kernel<false, true, false>), dim3(wgs), dim3(64 * kWaves), lds_bytes, stream, p);
     } else if (p.texel_table) {
-        hipLaunchKernelGGL((field_eval_kernel<false, false, true>), dim3(wgs), dim3(64 * MV_WAVES), lds_bytes, stream, p);
+        hipLaunchKernelGGL((field_eval_kernel<false, false, true>), dim3(wgs), dim3(64 * kWaves), lds_bytes, stream, p);
     } else {
-        hipLaunchKernelGGL((field_eval_kernel<false, false, false>), dim3(wgs), dim3(64 * MV_WAVES), lds_bytes, stream, p);
+        hipLaunchKernelGGL((field_eval_kernel<false, false, false>), dim3(wgs), dim3(64 * kWaves), lds_bytes, stream, p);
     }
     return hipGetLastError();
 }

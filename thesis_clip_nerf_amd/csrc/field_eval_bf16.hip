@@ -2,14 +2,14 @@
 // inputs, fp32 accumulate).  Same math and interfaces as field_eval.hip; what changes is the machine mapping:
 //
 //  * v_mfma_f32_32x32x16_bf16 runs 16x faster than the fp32 MFMA, so a wave can no longer stream its own
-//    copy of the weights from L2 (that would need > 64 B/clk/CU of L1 bandwidth).  A workgroup of 4 waves
-//    (4 tiles of 32 samples; two workgroups per CU, persistent over tile groups) shares them: the bf16 weight
-//    stream is cut into 8 KiB segments (2 k-steps x 4 output blocks) that travel through a ring of 5 LDS buffers
+//    copy of the weights from L2 (that would need > 64 B/clk/CU of L1 bandwidth).  A workgroup of 8 waves
+//    (8 tiles of 32 samples; one workgroup per CU, persistent over tile groups) shares them: the bf16 weight
+//    stream is cut into 16 KiB segments (4 k-steps x 4 output blocks) that travel through a ring of 5 LDS buffers
 //    by LDS-DMA (global_load_lds_dwordx4, no VGPR staging): while the waves run the MFMAs of segment i, the loads
 //    of segments i+1..i+3 are in flight; one counted vmcnt + workgroup barrier per segment.  The waves of a
 //    workgroup are in lock-step (they share the ring), so their gather / sin-cos phases leave the matrix pipe
-//    idle; the second, independent workgroup on the CU fills those holes (MV16_WAVES=8 is the single 512-thread
-//    workgroup form: half the weight traffic, no such overlap).
+//    idle.  Two independent 4-wave workgroups per CU, whose vector-only phases could fill the other's matrix
+//    phases at twice the weight traffic, measured 10 % slower.
 //  * activations stay fp32 in the accumulators (residual path, biases, read-out in fp32) and are rounded to
 //    bf16 only when a register block is fed as the next MFMA's B operand (v_cvt_pk_bf16_f32); gathered
 //    features are lerped in fp32, rounded once, and transposed through a wave-private bf16 LDS image.
@@ -93,41 +93,12 @@ static bool bf16x_enabled() {
 // Per tile the waves consume, for every view, the layer-0 segments (PE + rgb; the feature rows unless they come from
 // the texel table) and the 3 per-view blocks, then the 3 fusion blocks and the read-out.  Position p in [0, P) ->
 // first chunk of the segment.  The weights are the same for every tile, so positions wrap modulo P.
-#ifndef MV16_WAVES
-#define MV16_WAVES 8       // 4: two independent 256-thread workgroups per CU (their gather / VALU phases overlap the
-#endif                     //    other's MFMA phases); 8: one 512-thread workgroup per CU (half the weight traffic)
-#ifndef MV16_PIPE_A
-#define MV16_PIPE_A 1      // A operands of k-step ks+1 requested before the MFMAs of ks (0: compiler-scheduled)
-#endif
-#ifndef MV16_ABL_AREUSE
-#define MV16_ABL_AREUSE 0  // timing-only: one LDS read per k-step instead of four (same A for all output blocks)
-#endif
-#ifndef MV16_ABL_CVT
-#define MV16_ABL_CVT 0     // timing-only: no relu / bf16 conversion of the hidden-layer B operands
-#endif
-#ifndef MV16_ABL_DMA
-#define MV16_ABL_DMA 0     // timing-only ablations (wrong results): no weight DMA after the prologue
-#endif
-#ifndef MV16_ABL_GATHER
-#define MV16_ABL_GATHER 0  // no table / feature gather
-#endif
-#ifndef MV16_ABL_PE
-#define MV16_ABL_PE 0      // no sin/cos
-#endif
-#ifndef MV16_ABL_BARRIER
-#define MV16_ABL_BARRIER 0 // no workgroup barrier at segment ends
-#endif
-constexpr int kWgWaves = MV16_WAVES;
-constexpr int kSegChunks = 2 * kWgWaves;                       // 16 or 8 chunks of 1 KiB
-constexpr int kKs = kSegChunks / 4;                            // k-steps (of 16 rows) per segment: 4 or 2
-#ifndef MV16_LDSDMA
-#define MV16_LDSDMA 1      // 1: LDS-DMA ring of 5 slots (default); 0: register-staged double buffer (round 2 A/B: equal at cfg2, 14 % slower at V = 3)
-#endif
-#if MV16_LDSDMA
+// The ring is LDS-DMA with 5 slots: a register-staged double buffer (two slots, no counted vmcnt) measured equal at cfg2 and
+// 14 % slower at V = 3 / 480x640 (profiles/r02_ab_bf16_staged_*.log).
+constexpr int kWgWaves = 8;                                    // one 512-thread workgroup per CU (see the top of this file)
+constexpr int kSegChunks = 2 * kWgWaves;                       // 16 chunks of 1 KiB
+constexpr int kKs = kSegChunks / 4;                            // k-steps (of 16 rows) per segment: 4
 constexpr int kRing = 5, kAhead = 3, kSegF4 = kSegChunks * 64;  // float4 per slot
-#else
-constexpr int kRing = 2, kSegF4 = kSegChunks * 64;              // float4 per slot
-#endif
 constexpr int kHiddenUnits = 192 / kSegChunks;                 // segments of 3 blocks (6 Dense layers x 32 chunks)
 
 struct Ring {
@@ -137,9 +108,6 @@ struct Ring {
     int p, P, V;
     int l0_units;       // layer-0 segments per view: PE + rgb only (texel table) or PE + rgb + 256 feature rows
     int tid, wave;
-#if !MV16_LDSDMA
-    f32x4 stg0, stg1;   // the next segment on its way to LDS (2 x 16 B per thread)
-#endif
 };
 
 __device__ __forceinline__ int ring_start_chunk(int p, int V, int l0_units) {
@@ -152,7 +120,6 @@ __device__ __forceinline__ int ring_start_chunk(int p, int V, int l0_units) {
     return q < kHiddenUnits ? kW16Hidden + 192 + q * kSegChunks : kW16Readout;
 }
 
-#if MV16_LDSDMA
 // issue the LDS-DMA of position p + ahead into slot (c + ahead) % kRing: 2 x 16 B per thread, 1 KiB per wave-instruction
 __device__ __forceinline__ void ring_issue(const Ring& r, int ahead) {
     int pp = r.p + ahead;
@@ -172,48 +139,12 @@ __device__ __forceinline__ const f32x4* ring_cur(const Ring& r) { return r.base 
 // issue ordinary loads or stores drain everything (their own waits are in-order with the DMA anyway).
 template <bool kDrain>
 __device__ __forceinline__ void ring_next(Ring& r) {
-#if MV16_ABL_BARRIER
-    if (kDrain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#else
     if (kDrain) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-#endif
     r.c = r.c + 1 == kRing ? 0 : r.c + 1;
     r.p = r.p + 1 == r.P ? 0 : r.p + 1;
-    if (!MV16_ABL_DMA) ring_issue(r, kAhead);          // slot (c + 3) % 5 was last read two segments ago; everyone is past that barrier
+    ring_issue(r, kAhead);                             // slot (c + 3) % 5 was last read two segments ago; everyone is past that barrier
 }
-#else
-// Weight stream through registers (round 2 experiment, -DMV16_LDSDMA=0): every thread loads 2 x 16 B of the NEXT segment
-// right after a barrier and stores them to the other LDS slot just before the following barrier (two slots instead of five,
-// no counted vmcnt).  Measured equal to the LDS-DMA ring at cfg2 and 14 % slower at V = 3 / 480x640
-// (profiles/r02_ab_bf16_staged_*.log): not the default.
-__device__ __forceinline__ void ring_load(Ring& r, int pp) {                      // position pp -> staging registers
-    if (pp >= r.P) pp -= r.P;
-    const f32x4* src = r.w16 + (long)ring_start_chunk(pp, r.V, r.l0_units) * 64 + r.tid;
-    r.stg0 = src[0];
-    r.stg1 = src[64 * kWgWaves];
-}
-
-__device__ __forceinline__ const f32x4* ring_cur(const Ring& r) { return r.base + r.c * kSegF4; }
-
-template <bool kDrain>
-__device__ __forceinline__ void ring_next(Ring& r) {
-    f32x4* dst = r.base + (r.c ^ 1) * kSegF4 + r.tid;                             // position p + 1, loaded during this segment
-    if (!MV16_ABL_DMA) {
-        dst[0] = r.stg0;
-        dst[64 * kWgWaves] = r.stg1;
-    }
-#if MV16_ABL_BARRIER
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-    r.c ^= 1;
-    r.p = r.p + 1 == r.P ? 0 : r.p + 1;
-    if (!MV16_ABL_DMA) ring_load(r, r.p + 1);
-}
-#endif
 
 __device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -336,25 +267,16 @@ __device__ __forceinline__ bf16x8 relu_to_bf16(const f32x16& v, int s) {
 template <typename BFn>
 __device__ __forceinline__ void segment_mfma(Ring& ring, int lane, BFn bfn, f32x16 (&acc)[4]) {
     const f32x4* wb = ring_cur(ring) + lane;
-#if !MV16_PIPE_A
-#pragma unroll
-    for (int ks = 0; ks < kKs; ++ks) {
-        const bf16x8 bq = bfn(ks);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma16(__builtin_bit_cast(bf16x8, wb[(ks * 4 + nb) * 64]), bq, acc[nb]);
-    }
-    return;
-#endif
     f32x4 a[4];
 #pragma unroll
-    for (int nb = 0; nb < 4; ++nb) a[nb] = wb[(MV16_ABL_AREUSE ? 0 : nb) * 64];
+    for (int nb = 0; nb < 4; ++nb) a[nb] = wb[nb * 64];
     bf16x8 b = bfn(0);
 #pragma unroll
     for (int ks = 0; ks < kKs; ++ks) {
         f32x4 an[4];
         if (ks < kKs - 1) {
 #pragma unroll
-            for (int nb = 0; nb < 4; ++nb) an[nb] = wb[((ks + 1) * 4 + (MV16_ABL_AREUSE ? 0 : nb)) * 64];
+            for (int nb = 0; nb < 4; ++nb) an[nb] = wb[((ks + 1) * 4 + nb) * 64];
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -373,10 +295,6 @@ __device__ __forceinline__ void dense128_bf16(Ring& ring, int lane, const f32x16
     for (int seg = 0; seg < 8 / kKs; ++seg) {
         segment_mfma(ring, lane, [&](int ks) {
             const int g = seg * kKs + ks;
-            if (MV16_ABL_CVT) {
-                const f32x4 raw = {in[g >> 1][8 * (g & 1)], in[g >> 1][8 * (g & 1) + 1], in[g >> 1][8 * (g & 1) + 2], in[g >> 1][8 * (g & 1) + 3]};
-                return __builtin_bit_cast(bf16x8, raw);
-            }
             return relu_to_bf16(in[g >> 1], g & 1);
         }, acc);
         ring_next<false>(ring);
@@ -417,7 +335,7 @@ constexpr int kStage16Row = 256;      // bytes per staged sample row: 128 channe
 template <bool kMultiView, bool kProj, bool kF16>
 __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(FieldParams p, const f32x4* __restrict__ w16) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem16[];
-    constexpr int kRingBytes = kRing * kSegF4 * 16;                       // 40 or 80 KiB
+    constexpr int kRingBytes = kRing * kSegF4 * 16;                       // 80 KiB
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned char* stage = smem16 + kRingBytes + wave * (32 * kStage16Row);   // 8 KiB per wave
@@ -436,19 +354,11 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
     ring.P = (ring.l0_units + kHiddenUnits) * p.V + kHiddenUnits + 1;
     ring.tid = tid;
     ring.wave = wave;
-#if MV16_LDSDMA
     ring_issue(ring, 0);
     ring_issue(ring, 1);
     ring_issue(ring, 2);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     ring_issue(ring, kAhead);
-#else
-    ring_load(ring, 0);
-    ring.base[tid] = ring.stg0;                                            // position 0 -> slot 0
-    ring.base[tid + 64 * kWgWaves] = ring.stg1;
-    ring_load(ring, 1);
-    __syncthreads();
-#endif
 
     const long n_groups = (p.n_tiles + kWgWaves - 1) / kWgWaves;
     for (long grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
@@ -506,10 +416,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
                 float sk = 0.0f, ck = 0.0f;
 #pragma unroll
                 for (int k = 0; k < kNFreq; ++k) {
-                    if (MV16_ABL_PE) {
-                        sk = a0;
-                        ck = a0 + 1.0f;
-                    } else if (k == 0 || k == 5) {
+                    if (k == 0 || k == 5) {
                         sincos_f32(a0 * (float)(1 << k), &sk, &ck);
                     } else {
                         const float s2 = sk + sk;
@@ -541,7 +448,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
                 for (int P = 0; P < 2; ++P) {                       // unrolled: x[2P + nbl] must be a static register index
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll 1
-                    for (int it0 = 0; it0 < (MV16_ABL_GATHER ? 0 : 8); it0 += 4) {
+                    for (int it0 = 0; it0 < 8; it0 += 4) {
                         f32x4 tv[4][4];
                         float axs[4], ays[4];
 #pragma unroll
@@ -598,7 +505,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
                     return r;
                 };
 #pragma unroll 1
-                for (int it0 = 0; it0 < (MV16_ABL_GATHER ? 0 : 16); it0 += 4) {
+                for (int it0 = 0; it0 < 16; it0 += 4) {
                     f32x4 tv[4][4];
                     float axs[4], ays[4];
 #pragma unroll

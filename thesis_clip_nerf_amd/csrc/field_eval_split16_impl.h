@@ -44,10 +44,6 @@
 #ifndef MVS16_F16
 #error "include through field_eval_split16.hip / field_eval_split16h.hip"
 #endif
-#ifndef MVS16_MIXLO
-#define MVS16_MIXLO 0      // fp16 form: 1: the cut of a value pair with v_fma_mixlo / mixhi_f16, six vector instructions instead of eight
-#endif                     //    (bit-identical: scripts/mixlo_probe.hip).  Measured +0.5 % (profiles/r03_ab_f16x3_ablations.log) - and the pieces
-                           //    are then written by inline asm, whose hazards in front of an MFMA the compiler does not track: left off
 #if MVS16_F16
 #define MVS16_BYTES packed_net_split16h_bytes
 #define MVS16_PACK launch_pack_net_split16h
@@ -152,20 +148,10 @@ __device__ __forceinline__ void cut_pair(float v0, float v1, int q, B16& b) {
     }
 #if MVS16_F16
     // p1 = B0 = rn16(v / 64), p3 = B1 = rn16(64 (v / 64 - B0)) = rn16(v - 64 B0): the remainder is exact in fp32, formed by one
-    // mixed-precision fma per value (v_fma_mix_f32 reads B0's halves as they lie); p2 is not used
-#if MVS16_MIXLO
-    // four instructions per pair: v_fma_mixlo / mixhi_f16 form the product v / 64 (or the remainder v - 64 B0) in fp32 and round it ONCE
-    // to the fp16 half they write (scripts/mixlo_probe.hip: bit-identical to multiply + convert / fma + convert)
-    unsigned h, l;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "=v"(h) : "v"(v0), "s"(0.015625f));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "+v"(h) : "v"(v1), "s"(0.015625f));
-    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(h), "s"(-64.0f), "v"(v0));
-    // (the s_nop: the compiler's hazard recognizer does not see an inline-asm VALU write in front of an MFMA that reads the register - without
-    // the wait states the first MFMA behind a cut reads the old B1)
-    asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\ts_nop 1" : "+v"(l) : "v"(h), "s"(-64.0f), "v"(v1));
-    b.p1[q] = h;
-    b.p3[q] = l;
-#else
+    // mixed-precision fma per value (v_fma_mix_f32 reads B0's halves as they lie); p2 is not used.  The remainders stay two
+    // v_fma_mix_f32 and a convert: forming and rounding them in one v_fma_mixlo / mixhi_f16 each (six instead of eight vector
+    // instructions per pair, bit-identical: scripts/mixlo_probe.hip) measured +0.5 % (profiles/r03_ab_f16x3_ablations.log), and its
+    // inline-asm writes need a hand-placed s_nop in front of the MFMA that reads them (the compiler's hazard recognizer does not see them)
     const f32x2 t = {v0 * 0.015625f, v1 * 0.015625f};     // (forced into one v_pk_mul_f32 by inline asm: 2 % slower - the scheduler no longer places it)
     const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(t, f16x2));
     float r0, r1;
@@ -174,7 +160,6 @@ __device__ __forceinline__ void cut_pair(float v0, float v1, int q, B16& b) {
     const f32x2 r = {r0, r1};
     b.p1[q] = h;
     b.p3[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-#endif
 #else
     const float r0 = v0 - __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v0) & 0xffff0000u);
     const float r1 = v1 - __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v1) & 0xffff0000u);
@@ -208,18 +193,6 @@ __device__ __forceinline__ void cut8(const float (&v)[8], B16& b) {
     for (int q = 0; q < 4; ++q) cut_pair<kRelu>(v[2 * q], v[2 * q + 1], q, b);
 }
 
-#ifndef MVS16_ORDER
-#define MVS16_ORDER 0      // order of the six products of a block (A/B experiment, see kstep16)
-#endif
-#ifndef MVS16_DMA_LATE
-#define MVS16_DMA_LATE 0   // LDS-DMA ring: 1: the barrier at the end of k-step p waits only for position p + 1 (s_waitcnt vmcnt(3): the three
-#endif                     //    requests of position p + 2, issued in k-step p, stay in flight for one more k-step); 0: vmcnt(0) - every k-step
-                           //    then ends behind its own weight request's L2 round trip.  Measured on the fp16 form (profiles/r03_ab_dma_late.log): 1 is 0.5 % SLOWER -
-                           //    the request has landed by the end of its k-step, and the A operands of row block 0 are better read a k-step early
-#ifndef MVS16_LDSDMA
-#define MVS16_LDSDMA 1     // 1: the weight stream reaches LDS by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write);
-#endif                     // 0: through registers (three dwordx4 loads per thread and k-step, stored one k-step later)
-
 // ---- the slot ring: one k-step (24 KiB) per slot, 3 slots -------------------------------------------------------------------------
 constexpr int kR16Slots = 3, kR16SlotF4 = kS16SlotChunks * 64;               // float4 per slot
 constexpr int kS16PerView = kS16Hidden / 2;                                   // 24 k-steps: 3 ResNet blocks
@@ -232,9 +205,7 @@ struct Ring16 {
     int p, P;
     const int* table;   // LDS: first chunk of every position of one tile
     int start_pf;       // first chunk of the position the next fetch loads (read one k-step ahead)
-    int off;            // this thread's first 16 B inside a slot (tid * 16); + 8192, + 16384
     int tid, wave;
-    f32x4 stg[3];       // register-staged ring only (kDma = false): the fetched bytes on their way to LDS
     u32x4 a0[3];        // A operands (3 pieces) of row block 0 of the CURRENT k-step, read during the previous one
 };
 
@@ -258,40 +229,19 @@ __device__ __forceinline__ void ring16_dma(const Ring16& r, int start_chunk, int
                                          (__attribute__((address_space(3))) void*)(dst + 512 * i), 16, 0, 0);
 }
 
-__device__ __forceinline__ void ring16_store(Ring16& r) {
+// The weight fetch of the k-step at position p (slot c), issued behind its first MFMA group: position p + 2 goes straight into slot
+// (c + 2) % 3 by LDS-DMA - the slot of position p - 1, which nobody reads any more since the last barrier; the vmcnt(0) in front of the
+// barrier at the k-step's end (ring16_next) lets it land before it is published; seven of the k-step's eight MFMA groups lie between the
+// request and that wait.  No staging registers, no ds_write.
+// The training forward uses this ring too, although its vmcnt(0) per k-step then also waits for the stash stores of the layer boundary
+// in front of it (vmcnt retires in order): on the fp16 form that costs less than the staging registers and LDS stores of a
+// register-staged ring (three dwordx4 loads per thread and k-step, stored one k-step later; train step 5.77 -> 5.74 ms,
+// scripts/ab_train_libs.sh).
+__device__ __forceinline__ void ring16_fetch(Ring16& r) {
     int slot = r.c + 2;
     slot = slot >= kR16Slots ? slot - kR16Slots : slot;
-    char* dst = reinterpret_cast<char*>(r.base) + slot * (kR16SlotF4 * 16) + r.off;
-    *reinterpret_cast<f32x4*>(dst) = r.stg[0];
-    *reinterpret_cast<f32x4*>(dst + 8192) = r.stg[1];
-    *reinterpret_cast<f32x4*>(dst + 16384) = r.stg[2];
-}
-
-__device__ __forceinline__ void ring16_load(Ring16& r, int start_chunk) {
-    const char* src = reinterpret_cast<const char*>(r.w) + (long)start_chunk * 1024 + r.off;
-    r.stg[0] = *reinterpret_cast<const f32x4*>(src);
-    r.stg[1] = *reinterpret_cast<const f32x4*>(src + 8192);
-    r.stg[2] = *reinterpret_cast<const f32x4*>(src + 16384);
-}
-
-// The weight fetch of the k-step at position p (slot c), issued behind its first MFMA group.
-// kDma (inference): position p + 2 goes straight into slot (c + 2) % 3 by LDS-DMA - the slot of position p - 1, which nobody reads any
-//   more since the last barrier; the vmcnt(0) in front of the barrier at the k-step's end (ring16_next) lets it land before it is published;
-//   seven of the k-step's eight MFMA groups lie between the request and that wait.  No staging registers, no ds_write.
-// !kDma (MVS16_STASH_DMA = 0; the training forward's first form): through registers - store what the previous k-step loaded (position p + 2), load position p + 3 - because vmcnt
-//   retires in order: behind the stash's buffer_stores a vmcnt(0) per k-step would wait for 16 KiB of HBM writes per wave, whereas the
-//   staged loads are older than the stores that follow them.
-template <bool kDma>
-__device__ __forceinline__ void ring16_fetch(Ring16& r) {
-    if (kDma) {
-        int slot = r.c + 2;
-        slot = slot >= kR16Slots ? slot - kR16Slots : slot;
-        ring16_dma(r, r.start_pf, slot);
-    } else {
-        ring16_store(r);
-        ring16_load(r, r.start_pf);
-    }
-    int pp = r.p + (kDma ? 3 : 4);                                      // table entry the NEXT k-step's fetch needs
+    ring16_dma(r, r.start_pf, slot);
+    int pp = r.p + 3;                                                   // table entry the NEXT k-step's fetch needs
     pp = pp >= r.P ? pp - r.P : pp;
     r.start_pf = r.table[pp];
 }
@@ -299,15 +249,11 @@ __device__ __forceinline__ void ring16_fetch(Ring16& r) {
 __device__ __forceinline__ const f32x4* ring16_cur(const Ring16& r) { return r.base + r.c * kR16SlotF4; }
 __device__ __forceinline__ const f32x4* ring16_nxt(const Ring16& r) { return r.base + (r.c + 1 == kR16Slots ? 0 : r.c + 1) * kR16SlotF4; }
 
-template <bool kDma>
+// The end of a k-step waits for all its weight requests (vmcnt(0)): waiting only for position p + 1 (vmcnt(3), the requests of position
+// p + 2 in flight for one more k-step, row block 0's A operands then read at the k-step's start) measured 0.5 % slower on the fp16 form
+// (profiles/r03_ab_dma_late.log) - the request has landed by the end of its k-step, and those A operands are better read a k-step early.
 __device__ __forceinline__ void ring16_next(Ring16& r) {
-    if (kDma && MVS16_DMA_LATE) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef MVS16_ABL_BARRIER
-    else if (kDma) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // timing-only ablation (races): no workgroup barrier per k-step
-#else
-    else if (kDma) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-    else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     r.c = r.c + 1 == kR16Slots ? 0 : r.c + 1;
     r.p = r.p + 1 == r.P ? 0 : r.p + 1;
 }
@@ -339,61 +285,30 @@ __device__ __forceinline__ void apply_bias_row(f32x4 (&row)[2], const f32x4& bv)
 // the NEXT k-step's row block 0 at rb = 7) are read from LDS and the vector ALU prepares what comes next:
 //   kMode 1: one value pair of the next k-step's B operands (nv[cb][0..7], pair rb & 3 of column block rb >> 2) is cut: 13 vector
 //            instructions per 12 MFMAs;
-//   kMode 2: the LAST k-step of a hidden layer: the NEXT layer's first B operands are cut from this layer's own output - row blocks
-//            0 and 1 of acc, final after groups 0 and 1 (relu, then the cut) - during groups 1..4, and the layer's input array, no
-//            longer needed, takes the bias work of the layer boundary (tail_bias: in[rb][cb] += bias row, or = bias row), one row
-//            block per group.  With it no vector work of a layer boundary is left outside the MFMA shadow.
-//   kMode 4: the last k-step of a hidden layer in the plain flow: only the bias half of kMode 2 (tail_bias onto the consumed input array).
+//   kMode 4: the last k-step of a hidden layer: the layer's input array, no longer needed, can take bias work of the layer boundary
+//            (tail_bias: in[rb][cb] += bias row, or = bias row), one row block per group.  The layer flow passes nullptr (applying
+//            the next layer's bias rows here measured +0.3 %, profiles/r03_ab_tailbias.log); the last k-step of every hidden layer
+//            is still scheduled with this mode's group pattern (one more LDS-read slot and vector slots per MFMA), not kMode 0's;
 //   kMode 0: nothing.
-template <bool kRelu, int kMode, bool kTailAdd, bool kDma>
+template <bool kRelu, int kMode, bool kTailAdd>
 __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16 (&b)[2], const float (&nv)[2][8], B16 (&bn)[2], f32x4 (&acc)[8][2],
                                         f32x4 (&in)[8][2], const float* __restrict__ tail_bias) {
     const f32x4* cur = ring16_cur(ring) + lane;
     const f32x4* nxt = ring16_nxt(ring) + lane;
     u32x4 a[3] = {ring.a0[0], ring.a0[1], ring.a0[2]};
-    if (kDma && MVS16_DMA_LATE) {
-        // position p + 1 is published only by the barrier that ends k-step p: row block 0's A chunks are read here, not one k-step early
-#pragma unroll
-        for (int q = 0; q < 3; ++q) a[q] = __builtin_bit_cast(u32x4, cur[q * 64]);
-    }
     f32x4 bv = {0.0f, 0.0f, 0.0f, 0.0f};
     // the lane's part of perm_f4, formed HERE (behind an empty asm): left to itself the compiler hoists the eight row addresses of every
     // layer's bias vector out of the tile loop and spills them
     int glane = (g & 1) * 16 + (g >> 1);
-    if (kMode == 2 || kMode == 4) asm volatile("" : "+v"(glane));
+    if (kMode == 4) asm volatile("" : "+v"(glane));
     const f32x4* tail_rows = reinterpret_cast<const f32x4*>(tail_bias) + glane;
 #pragma unroll
     for (int rb = 0; rb < 8; ++rb) {
         u32x4 an[3];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-#ifdef MVS16_ABL_A0S
-            if (q == 1) continue;                                  // timing-only ablation (wrong results): the A0 / 64 piece is not read from LDS
-#endif
-            if (rb < 7 || !(kDma && MVS16_DMA_LATE)) an[q] = __builtin_bit_cast(u32x4, rb < 7 ? cur[((rb + 1) * 3 + q) * 64] : nxt[q * 64]);
-            else an[q] = a[q];
-        }
-#ifdef MVS16_ABL_A0S
-        an[1] = an[0];
-#endif
-#ifdef MVS16_ABL_CUT
-        if (kMode == 1 && rb == 0) { bn[0] = b[0]; bn[1] = b[1]; }            // timing-only ablation (wrong results): no operand cut in the k-steps
-#else
+        for (int q = 0; q < 3; ++q) an[q] = __builtin_bit_cast(u32x4, rb < 7 ? cur[((rb + 1) * 3 + q) * 64] : nxt[q * 64]);
         if (kMode == 1) cut_pair<kRelu>(nv[rb >> 2][2 * (rb & 3)], nv[rb >> 2][2 * (rb & 3) + 1], rb & 3, bn[rb >> 2]);
-#endif
-        if (kMode == 2) {
-            if (rb >= 1 && rb <= 4) {              // pair q = rb - 1 of both column blocks: q < 2 from acc[0], q >= 2 from acc[1]
-                const int q = rb - 1;
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb) {
-                    cut_pair<true>(acc[q >> 1][cb][2 * (q & 1)], acc[q >> 1][cb][2 * (q & 1) + 1], q, bn[cb]);
-                    // pinned inside its group: this cut reads MFMA results, and left to itself the scheduler fills the group's vector
-                    // slots with the bias adds and sinks the whole cut behind the k-step's last MFMA
-                    pin_pieces(bn[cb], q);
-                }
-            }
-        }
-        if ((kMode == 2 || kMode == 4) && tail_bias) {
+        if (kMode == 4 && tail_bias) {
             // the bias row of row block rb is requested here and applied one group later (an LDS round trip inside a group would
             // hold this wave's MFMAs behind the wait); row 7 is applied behind the last group
             const f32x4 bv_new = tail_rows[(rb >> 1) * 4 + 2 * (rb & 1)];              // = [perm_f4(rb, g)]: the row block is an immediate offset
@@ -406,20 +321,6 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
         for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[1], b[cb].p3, acc[rb][cb]);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[2], b[cb].p1, acc[rb][cb]);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[0], b[cb].p1, acc[rb][cb]);
-#elif MVS16_ORDER == 1
-        // the A operand changes as rarely as possible: a2 (x2), a1 (x4), a0 (x6); per chain a2p1, a1p2, a1p1, a0p3, a0p2, a0p1
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[2], b[cb].p1, acc[rb][cb]);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[1], b[cb].p2, acc[rb][cb]);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[1], b[cb].p1, acc[rb][cb]);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[0], b[cb].p3, acc[rb][cb]);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[0], b[cb].p2, acc[rb][cb]);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[0], b[cb].p1, acc[rb][cb]);
 #else
@@ -439,19 +340,17 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
         // issue order inside the group: the first MFMA (its operands were requested one group ago), the LDS reads of the next group
         // (and the bias row), then vector instructions / MFMA alternating
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, (kMode == 2 || kMode == 4) ? 4 : 3, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, kMode == 4 ? 4 : 3, 0);
 #pragma unroll
         for (int m = 0; m < (MVS16_F16 ? 5 : 11); ++m) {
             if (kMode == 1) __builtin_amdgcn_sched_group_barrier(0x002, MVS16_F16 ? 2 : 1, 0);
-            if (kMode == 2) __builtin_amdgcn_sched_group_barrier(0x002, MVS16_F16 ? 6 : 3, 0);
             if (kMode == 4) __builtin_amdgcn_sched_group_barrier(0x002, MVS16_F16 ? 2 : 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         }
         if (kMode == 1) __builtin_amdgcn_sched_group_barrier(0x002, MVS16_F16 ? 3 : 2, 0);
-        if (kMode == 2) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (rb == 0) {   // the weight loads of two k-steps ahead
-            ring16_fetch<kDma>(ring);
+            ring16_fetch(ring);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -459,8 +358,8 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q) ring.a0[q] = a[q];
-    if ((kMode == 2 || kMode == 4) && tail_bias) apply_bias_row<kTailAdd>(in[7], bv);
-    if (kMode == 1 || kMode == 2) {
+    if (kMode == 4 && tail_bias) apply_bias_row<kTailAdd>(in[7], bv);
+    if (kMode == 1) {
         // pin the pieces of the next operand HERE (otherwise the machine sinker moves the cut behind the barrier)
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
@@ -480,22 +379,13 @@ __device__ __forceinline__ void first_operand_s16(const f32x4 (&in)[8][2], B16 (
     }
 }
 
-// acc += W^T relu(in) for one hidden layer: 4 k-steps; k-step t reads in[2t][cb] (jj < 4) and in[2t + 1][cb] (jj >= 4).
-// b: on entry the cut of relu(in[0..1]) (first_operand_s16, or the previous layer's exit value); on exit the cut of relu(acc[0..1]),
-// i.e. the next layer's entry value.  tail_bias (or nullptr): in the last k-step in[rb][cb] += / = that bias vector (32x32 accumulator
-// order) - `x += b2` while the first Dense of a block writes hid, `hid = b1 of the next block` while the second one writes x.
-#ifndef MVS16_TAILBIAS
-#define MVS16_TAILBIAS 0   // 1: plain flow with the bias rows of the next layer's accumulator applied in the last k-step of the current layer (kMode 4).
-                           //    Measured on the fp16 form (profiles/r03_ab_tailbias.log): +0.3 %, i.e. nothing - the layer boundaries' vector work is not what it waits for
-#endif
-#ifndef MVS16_TAIL
-#define MVS16_TAIL 0       // 1: layer boundaries prepared in the previous layer's last k-step (kMode 2); 0: their vector work (first operand's
-#endif                     //    cut, bias rows) stays between the layers.  Measured (profiles/r03_ab_tail*.log): 1 is 3-5 % SLOWER - see DESIGN.md 4.0
-
-// the plain form: acc += W^T relu(in), first operand cut at the layer's head.  tail_bias (or nullptr): during the last k-step, when every
-// row of `in` has been cut, in[rb][cb] += / = that bias vector (32x32 accumulator order) - `x += b2` while the first Dense of a block writes
-// hid, `hid = b1 of the next block` while the second one writes x: the bias rows of the NEXT layer's accumulator cost no exposed time.
-template <bool kDma, bool kTailAdd>
+// acc += W^T relu(in) for one hidden layer: 4 k-steps; k-step t reads in[2t][cb] (jj < 4) and in[2t + 1][cb] (jj >= 4).  The first
+// operand is cut at the layer's head, and the layer boundaries' vector work (that cut, the bias rows) stays between the layers:
+// preparing it in the previous layer's last k-step (the next layer's first cut from that layer's own output, the bias rows applied to
+// the consumed input array) needs 24 more live registers and measured 3-5 % slower (profiles/r03_ab_tail*.log).
+// tail_bias (or nullptr): during the last k-step, when every row of `in` has been cut, in[rb][cb] += / = that bias vector (32x32
+// accumulator order) - the kernels pass nullptr (kstep16, kMode 4).
+template <bool kTailAdd>
 __device__ __forceinline__ void dense128_s16_plain(Ring16& ring, int lane, int g, f32x4 (&in)[8][2], f32x4 (&acc)[8][2], const float* __restrict__ tail_bias) {
     B16 b[2], bn[2];
     first_operand_s16(in, b);
@@ -506,32 +396,11 @@ __device__ __forceinline__ void dense128_s16_plain(Ring16& ring, int lane, int g
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int q = 0; q < 8; ++q) nv[cb][q] = t < 3 ? in[2 * (t + 1) + (q >> 2)][cb][q & 3] : 0.0f;
-        if (t < 3) kstep16<true, 1, false, kDma>(ring, lane, g, b, nv, bn, acc, in, nullptr);
-        else kstep16<true, 4, kTailAdd, kDma>(ring, lane, g, b, nv, bn, acc, in, tail_bias);
+        if (t < 3) kstep16<true, 1, false>(ring, lane, g, b, nv, bn, acc, in, nullptr);
+        else kstep16<true, 4, kTailAdd>(ring, lane, g, b, nv, bn, acc, in, tail_bias);
         b[0] = bn[0];
         b[1] = bn[1];
-        ring16_next<kDma>(ring);
-    }
-}
-template <bool kAdd>
-__device__ __forceinline__ void bias16(const float* __restrict__ bperm, int g, f32x4 (&acc)[8][2]);
-
-template <bool kTailAdd>
-__device__ __forceinline__ void dense128_s16(Ring16& ring, int lane, int g, f32x4 (&in)[8][2], f32x4 (&acc)[8][2], B16 (&b)[2],
-                                             const float* __restrict__ tail_bias) {
-    B16 bn[2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        float nv[2][8];
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) nv[cb][q] = t < 3 ? in[2 * (t + 1) + (q >> 2)][cb][q & 3] : 0.0f;
-        if (t < 3) kstep16<true, 1, false, true>(ring, lane, g, b, nv, bn, acc, in, nullptr);
-        else kstep16<true, 2, kTailAdd, true>(ring, lane, g, b, nv, bn, acc, in, tail_bias);
-        b[0] = bn[0];
-        b[1] = bn[1];
-        ring16_next<true>(ring);
+        ring16_next(ring);
     }
 }
 
@@ -574,7 +443,7 @@ __device__ __forceinline__ void store_tl16(float* __restrict__ base, long tile, 
             for (int cb = 0; cb < 2; ++cb) {
                 const float val = x[rb][cb][i];
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, val), rsrc, voff + (i * 32 + 16 * cb) * 4,
-                                                      tile_off + rb * 2048, MV_STASH_AUX);
+                                                      tile_off + rb * 2048, kStashAux);
             }
 }
 
@@ -593,11 +462,6 @@ struct SampleGeo {
 template <bool kMultiView, bool kProj, bool kAux, bool kStash>
 __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x4* __restrict__ wsplit) {
     constexpr int kW = 8;
-#ifndef MVS16_STASH_DMA
-#define MVS16_STASH_DMA 1  // 1: the training forward's weight ring by LDS-DMA as well.  Its vmcnt(0) per k-step then also waits for the stash stores of
-#endif                     //    the layer boundary before it - on the fp16 form that costs less than the staging registers and LDS stores of the
-                           //    register-staged ring (train step 5.77 -> 5.74 ms, scripts/ab_train_libs.sh); 0: register-staged (round 3's first form)
-    constexpr bool kDma = MVS16_LDSDMA && (!kStash || MVS16_STASH_DMA);     // see ring16_fetch
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s16[];
     constexpr int kRingBytes = kR16Slots * kR16SlotF4 * 16;                 // 72 KiB
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, g = lane >> 4;
@@ -621,24 +485,12 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
     for (int i = tid; i < ring.P; i += 64 * kW) table[i] = ring16_start_chunk(i, p.V, l0_units);
     ring.table = table;
     __syncthreads();                                                        // the position table is written
-    ring.off = tid * 16;
     ring.tid = tid;
     ring.wave = wave;
-    if (kDma) {
-        ring16_dma(ring, table[0], 0);                                      // prologue: positions 0 and 1 into slots 0 and 1
-        ring16_dma(ring, table[1], 1);
-        ring.start_pf = table[2];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-        for (int q = 0; q < 2; ++q) {                                       // prologue: positions 0 and 1 into slots 0 and 1
-            ring16_load(ring, table[q]);
-            ring.c = (q + kR16Slots - 2) % kR16Slots;                       // ring16_store writes slot (c + 2) % 3
-            ring16_store(ring);
-        }
-        ring.c = 0;
-        ring16_load(ring, table[2]);
-        ring.start_pf = table[3 % ring.P];
-    }
+    ring16_dma(ring, table[0], 0);                                          // prologue: positions 0 and 1 into slots 0 and 1
+    ring16_dma(ring, table[1], 1);
+    ring.start_pf = table[2];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 3; ++q) ring.a0[q] = __builtin_bit_cast(u32x4, ring16_cur(ring)[q * 64 + lane]);
@@ -678,8 +530,6 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 
         f32x4 x[8][2], hid[8][2];
         f32x4 xsum[kMultiView ? 8 : 1][2];
-        B16 bop[2];                                                           // (MVS16_TAIL) the B operands of the next hidden layer's first k-step
-        (void)bop;
 
         // (a sample row of 128 floats: lane (n, g) holds features 16 rb + 4g + {0..3} of samples n (cb 0) and 16 + n (cb 1))
         // the launcher sends V = 1 to the !kMultiView variants.  Telling the compiler so takes the optional-output and stash variants from 92-132
@@ -731,13 +581,9 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
                     const float a1 = (gl < 3 ? cd : cam[1]) * 3.14159274101257324f;
                     const float a2 = cam[2] * 3.14159274101257324f;
                     float s0, c0, s1, c1, s2, c2;
-#ifdef MVS16_ABL_SINCOS
-                    s0 = a0; c0 = a1; s1 = a2; c1 = a0; s2 = a1; c2 = a2;        // timing-only ablation (wrong results): no accurate sin / cos
-#else
                     sincos_f32(a0 * (gl < 3 ? 1.0f : 256.0f), &s0, &c0);
                     sincos_f32(a1 * (gl < 3 ? 32.0f : 256.0f), &s1, &c1);
                     sincos_f32(a2 * 256.0f, &s2, &c2);
-#endif
                     auto dbl = [](float& sk, float& ck) {
                         const float t2 = sk + sk;
                         const float cn = fmaf(-t2, sk, 1.0f);              // cos 2t = 1 - 2 sin^2 t
@@ -791,10 +637,10 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
                 for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
                     for (int q = 0; q < 8; ++q) nv[cb][q] = pe[cb][8 + q];
-                kstep16<false, 1, false, kDma>(ring, lane, g, bq, nv, bqn, x, x, nullptr);
-                ring16_next<kDma>(ring);
-                kstep16<false, 0, false, kDma>(ring, lane, g, bqn, nv, bq, x, x, nullptr);
-                ring16_next<kDma>(ring);
+                kstep16<false, 1, false>(ring, lane, g, bq, nv, bqn, x, x, nullptr);
+                ring16_next(ring);
+                kstep16<false, 0, false>(ring, lane, g, bqn, nv, bq, x, x, nullptr);
+                ring16_next(ring);
             }
 
             // ---- layer 0's 256 feature rows through the wave-private fp32 stage ----
@@ -804,11 +650,7 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
             // rows [h][nb][16] (pass P = floats h*64 + P*32 + {0..31}), lerped rows ADD into the accumulators; direct: 4 passes
             // of 64 raw channels, the lerped rows are the B operands of 2 k-steps each.
 #pragma unroll
-#ifdef MVS16_ABL_GATHER
-            for (int P = 0; P < 0; ++P) {                                        // timing-only ablation (wrong results): no table / feature gather
-#else
             for (int P = 0; P < (kProj ? 2 : 4); ++P) {
-#endif
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 const f32x4* tbase = kProj ? reinterpret_cast<const f32x4*>(p.texel_table) + (nl >> 3) * 16 + (nl & 7) + P * 8
                                            : reinterpret_cast<const f32x4*>(p.features) + P * 16 + nl;
@@ -871,8 +713,8 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 #pragma unroll
                             for (int q = 0; q < 8; ++q) nv[cb][q] = 0.0f;
                         }
-                        kstep16<false, 0, false, kDma>(ring, lane, gl, bq, nv, bqn, x, x, nullptr);
-                        ring16_next<kDma>(ring);
+                        kstep16<false, 0, false>(ring, lane, gl, bq, nv, bqn, x, x, nullptr);
+                        ring16_next(ring);
                     }
                 }
             }
@@ -891,42 +733,18 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
                     }
             };
             if (kAux && p.acts_view) store_acc16(p.acts_view, vrow);
-            // ---- 24 k-steps: the three per-view ResNet blocks.  Only this entry is a layer boundary with exposed vector work (the
-            // first operand's cut and the first bias row): every later boundary is prepared in the previous layer's last k-step ----
-#if MVS16_TAIL
-            if (v == 0)
-#endif
-            bias16<false>(net + kPackBHidden, g, hid);      // exposed once per (tile, view); the later layers' bias rows are applied in k-step shadows
-#if MVS16_TAIL
-            first_operand_s16(x, bop);
-#endif
+            // ---- 24 k-steps: the three per-view ResNet blocks: hid = b1 + W1^T relu(x), x += b2 + W2^T relu(hid) ----
+            bias16<false>(net + kPackBHidden, g, hid);
 #pragma unroll 1
             for (int bi = 0; bi < 3; ++bi) {
                 const float* bias1 = net + kPackBHidden + 256 * bi;
-#if MVS16_TAIL
-                dense128_s16<true>(ring, lane, g, x, hid, bop, bias1 + 128);     // hid = b1 + W1^T relu(x); tail: x += b2
-                // x += W2^T relu(hid); tail: hid = b1 of the block that follows (the next view restarts at block 0)
-                const float* next_b1 = bi < 2 ? bias1 + 256 : net + kPackBHidden + ((kMultiView && v + 1 < p.V) ? 0 : 768);
-                dense128_s16<false>(ring, lane, g, hid, x, bop, next_b1);
-#else
-                // hid = b1 + W1^T relu(x), and in its last k-step x += b2; x += W2^T relu(hid), and in its last k-step hid = b1 of the
-                // block that follows (the last view hands over to fusion block 3)
-                // (a view that is followed by another one leaves hid alone: carried through the next view's sin / cos and gather it would be spilled)
-#if MVS16_TAILBIAS
-                const float* next_b1 = bi < 2 ? bias1 + 256 : (v + 1 == n_views ? net + kPackBHidden + 768 : nullptr);
-                dense128_s16_plain<kDma, true>(ring, lane, g, x, hid, bias1 + 128);
-                if (kStash && tile_ok) store_tl16(p.stash + (1 + 2 * bi) * p.stash_stride, vtile, n, g, hid);
-                dense128_s16_plain<kDma, false>(ring, lane, g, hid, x, next_b1);
-#else
                 if (bi > 0) bias16<false>(bias1, g, hid);
-                dense128_s16_plain<kDma, true>(ring, lane, g, x, hid, nullptr);
+                dense128_s16_plain<true>(ring, lane, g, x, hid, nullptr);
                 if (kStash && tile_ok) store_tl16(p.stash + (1 + 2 * bi) * p.stash_stride, vtile, n, g, hid);
                 bias16<true>(bias1 + 128, g, x);
-                dense128_s16_plain<kDma, false>(ring, lane, g, hid, x, nullptr);
-#endif
+                dense128_s16_plain<false>(ring, lane, g, hid, x, nullptr);
                 // (per-view slot 6 = x3 is not written: nothing reads it, as in field_eval_split_kernel)
                 if (kStash && tile_ok && bi < 2) store_tl16(p.stash + (2 + 2 * bi) * p.stash_stride, vtile, n, g, x);
-#endif
                 if (kAux && p.acts_view) store_acc16(p.acts_view + (bi + 1) * vslot, vrow);
             }
             if (kMultiView) {
@@ -969,29 +787,15 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
         if (kAux && p.acts_fused) store_fused16(p.acts_fused);               // complete_output: the view mean
         if (kStash && tile_ok) store_tl16(p.stash_fused, tile, n, g, x);      // fused slot 0: the view mean
         // ---- 24 k-steps: fusion blocks ----
-#if MVS16_TAIL
-        if (kMultiView) first_operand_s16(x, bop);                           // the view mean is new; V = 1: bop already is the cut of relu(x)
-#endif
 #pragma unroll 1
         for (int bi = 3; bi < 6; ++bi) {
             const float* bias1 = net + kPackBHidden + 256 * bi;
-#if MVS16_TAIL
-            dense128_s16<true>(ring, lane, g, x, hid, bop, bias1 + 128);
-            dense128_s16<false>(ring, lane, g, hid, x, bop, bi < 5 ? bias1 + 256 : nullptr);
-#else
-#if MVS16_TAILBIAS
-            dense128_s16_plain<kDma, true>(ring, lane, g, x, hid, bias1 + 128);
-            if (kStash && tile_ok) store_tl16(p.stash_fused + (1 + 2 * (bi - 3)) * p.stash_fused_stride, tile, n, g, hid);
-            dense128_s16_plain<kDma, false>(ring, lane, g, hid, x, bi < 5 ? bias1 + 256 : nullptr);
-#else
             bias16<false>(bias1, g, hid);
-            dense128_s16_plain<kDma, true>(ring, lane, g, x, hid, nullptr);
+            dense128_s16_plain<true>(ring, lane, g, x, hid, nullptr);
             if (kStash && tile_ok) store_tl16(p.stash_fused + (1 + 2 * (bi - 3)) * p.stash_fused_stride, tile, n, g, hid);
             bias16<true>(bias1 + 128, g, x);
-            dense128_s16_plain<kDma, false>(ring, lane, g, hid, x, nullptr);
-#endif
+            dense128_s16_plain<false>(ring, lane, g, hid, x, nullptr);
             if (kStash && tile_ok) store_tl16(p.stash_fused + (2 + 2 * (bi - 3)) * p.stash_fused_stride, tile, n, g, x);
-#endif
             if (kAux && p.acts_fused) store_fused16(p.acts_fused + (long)(bi - 2) * p.total * 128);
         }
         if (kAux && p.embedding) store_fused16(p.embedding);
@@ -1051,7 +855,6 @@ hipError_t MVS16_PACK(const float* net_keras, void* packed_split16, hipStream_t 
 }
 
 bool MVS16_SUPPORTS(const FieldParams& p) {
-    if (p.stash && MVS16_TAIL) return false;                                 // the stash stores are built into the plain layer flow only
     if (p.stash && (p.tap_idx || p.pix || p.embedding || p.acts_view || p.acts_fused)) return false;
     const int n_pos = ((p.texel_table ? kS16L0Pe : kS16L0Pe + kS16L0Feat) + kS16PerView) * p.V + kS16PerView;
     return n_pos <= kS16MaxPositions;

@@ -4,10 +4,6 @@
 
 #include "mvnerf_mfma.h"
 
-#ifndef MV_ABL_BIAS
-#define MV_ABL_BIAS 0
-#endif
-
 namespace mvnerf {
 
 constexpr int kTile = 32;            // samples per wavefront (MFMA N dimension)
@@ -15,15 +11,6 @@ constexpr int kStageRow = 128;       // floats per staged sample row (half of th
 
 template <bool kAdd>
 __device__ __forceinline__ void bias_to_acc(const float* __restrict__ bperm, int h, f32x16 (&acc)[4]) {
-#if MV_ABL_BIAS
-    if (!kAdd) {
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = (float)h;
-    }
-    return;
-#endif
     const f32x4* p = reinterpret_cast<const f32x4*>(bperm + h * 64);
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {

@@ -31,7 +31,7 @@ struct FieldParams {
     int B, V, R, S, H, W;
     long total;            // B*R*S samples
     long n_tiles;          // ceil(total / 32)
-    unsigned int* tile_counter;   // set by launch_field_eval
+    unsigned int* tile_counter;   // unused (was the ticket of a persistent field_eval_kernel form); kept: removing it shifts every kernel's arguments
     // forward-mode tangent kernel (query_ops.hip)
     const float* t_o;      // (B,R,3) tangent of rays_o
     const float* t_d;      // (B,R,3) tangent of rays_d

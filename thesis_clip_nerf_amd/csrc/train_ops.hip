@@ -195,7 +195,7 @@ hipError_t launch_dw_tile(const float* a_tl, int relu_a, const float* g_tl, int 
 // into LDS by LDS-DMA (global_load_lds_dwordx4) with the float4 chunks of a row XOR-swizzled on the SOURCE side, so that the
 // "lane = sample" dword reads and the "lane = feature" 16-byte reads of the image are conflict-free.
 //
-// What round 2 measured on the way (scripts/bwd_probe.hip, scripts/filler_probe.hip, profiles/r02_bwd_*.log):
+// What round 2 measured on the way (scripts/filler_probe.hip, profiles/r02_bwd_probe_split8.log, profiles/r02_bwd_kernel_experiments.log):
 //  * the first form kept the next tile in registers while streaming its weight quarter from L2 inside the tile: vmcnt retires in
 //    order, so the first weight wait of a tile also waited for the HBM prefetch issued just before it (340 us per 16384-tile launch);
 //  * weights resident in registers + tiles by LDS-DMA: 300 us; of a tile's 16.7 k cycles per wave 11 k were the MFMA section of
@@ -315,16 +315,6 @@ __device__ __forceinline__ void amax_publish(float* __restrict__ amax, float m) 
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
     if (amax && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<int*>(amax) + (blockIdx.x & (kAmaxSlots - 1)), __builtin_bit_cast(int, m));
 }
-
-#ifndef MVT_STAMP
-#define MVT_STAMP 0        // scripts/bwd_probe.hip: per-wave cycle totals of the phases of a tile (dense_bwd_split8_kernel)
-#endif
-#if MVT_STAMP
-__device__ unsigned long long g_bwd_stamp[256 * 8 * 8];
-#define STAMP(k) { const unsigned long long t_ = __builtin_readcyclecounter(); st_acc[k] += t_ - st_last; st_last = t_; }
-#else
-#define STAMP(k)
-#endif
 
 // ---- dL/da only (frozen trunk): a wave's quarter of the transposed weight stream stays in 64 registers for the whole launch, the
 // only vector-memory traffic inside the tile loop is the DMA of the NEXT tile into the other LDS buffer, the residual rows (wave-
@@ -546,10 +536,6 @@ __global__ __launch_bounds__(512, 1) void dense_bwd_split8_kernel(
         return dbv;
     };
     float dbacc = 0.0f;
-#if MVT_STAMP
-    unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0}, st_last = __builtin_readcyclecounter();
-    const unsigned long long st_begin = st_last;
-#endif
     dma_raw((int)blockIdx.x, 0);
 
     if (v < 4) {
@@ -589,9 +575,7 @@ __global__ __launch_bounds__(512, 1) void dense_bwd_split8_kernel(
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         int cur = 0;
         for (int tile = (int)blockIdx.x; tile < n_tiles32; tile += stride) {
-            STAMP(5)
             asm volatile("s_barrier" ::: "memory");             // B1: raw tile complete; pieces of the previous tile consumed
-            STAMP(0)
             {
                 const int nt = tile + stride < n_tiles32 ? tile + stride : tile;
                 dma_raw(nt, cur ^ 1);
@@ -608,9 +592,7 @@ __global__ __launch_bounds__(512, 1) void dense_bwd_split8_kernel(
             }
             dbacc = cut_g(cur, dbacc);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            STAMP(1)
             asm volatile("s_barrier" ::: "memory");             // B2: both piece images complete
-            STAMP(2)
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -653,10 +635,8 @@ __global__ __launch_bounds__(512, 1) void dense_bwd_split8_kernel(
                 }
             }
 #endif
-            STAMP(3)
             // the residual rows and the next raw tile have landed (they had the cut and the MFMA section); the previous stores too
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            STAMP(4)
             unsigned so = src_off;
             asm volatile("" : "+v"(so));
             const unsigned x = so >> 4;
@@ -706,18 +686,14 @@ __global__ __launch_bounds__(512, 1) void dense_bwd_split8_kernel(
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         int cur = 0;
         for (int tile = (int)blockIdx.x; tile < n_tiles32; tile += stride) {
-            STAMP(5)
             asm volatile("s_barrier" ::: "memory");             // B1
-            STAMP(0)
             {
                 const int nt = tile + stride < n_tiles32 ? tile + stride : tile;
                 dma_raw(nt, cur ^ 1);
             }
             dbacc = cut_g(cur, dbacc);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            STAMP(1)
             asm volatile("s_barrier" ::: "memory");             // B2
-            STAMP(2)
             // this wave's own A operand (rows 32u + i of relu(a)) is cut behind the barrier: nobody waits for it
             u32x4_t ap[2][3];
             const u32x4_t* pr = sP + kBwd8Prow + lane;
@@ -765,9 +741,7 @@ __global__ __launch_bounds__(512, 1) void dense_bwd_split8_kernel(
                 }
             }
 #endif
-            STAMP(3)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's part of the next raw tile has landed
-            STAMP(4)
             cur ^= 1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) aidx[e] ^= kBwd8Raw;
@@ -788,14 +762,6 @@ __global__ __launch_bounds__(512, 1) void dense_bwd_split8_kernel(
             for (int r = 0; r < 16; ++r) grad_out(dWo + (long)(32 * u + acc_row(r, hh)) * kHidden + 32 * nb + col, dwacc[nb][r], store);
 #endif
     }
-#if MVT_STAMP
-    if (lane == 0 && blockIdx.x < 256) {
-        unsigned long long* o = g_bwd_stamp + ((long)blockIdx.x * 8 + v) * 8;
-        for (int q = 0; q < 6; ++q) o[q] = st_acc[q];
-        o[6] = __builtin_readcyclecounter() - st_begin;
-        o[7] = v < 4 ? 0 : 1;
-    }
-#endif
 }
 
 hipError_t launch_dense_bwd_fused(const float* g_tl, const float* a_tl, const float* wstream, const float* resid_tl,
@@ -1236,9 +1202,6 @@ constexpr int kDw8XA = 0, kDw8PB = kDw8XA + 12 * 2 * 3 * 64, kDw8Raw = kDw8PB + 
 constexpr int kDw8Geom = kDw8Pe + (32 * kPe8Row + 3) / 4, kDw8GeomQ = kDw8Geom + 2 * 32 * 9 / 4;
 constexpr int kDw8LdsBytes = (kDw8GeomQ + 2 * 32) * 16;
 
-#ifndef MVT_DW0_ABL
-#define MVT_DW0_ABL 0      // timing-only ablations (wrong results), bits: 1 no feature gathers, 2 no PE / rgb / geometry, 4 no MFMAs, 8 no build
-#endif
 __global__ __launch_bounds__(512, 1) void dw0_split8_kernel(FieldParams p, const float* __restrict__ g0_tl, float* __restrict__ dW0,
                                                             float* __restrict__ db0, long part_stride, const float* __restrict__ amax_in) {
     extern __shared__ __attribute__((aligned(16))) f32x4 sbuf[];
@@ -1458,14 +1421,12 @@ __global__ __launch_bounds__(512, 1) void dw0_split8_kernel(FieldParams p, const
         const int tnn = tn + stride < view_tiles ? tn + stride : tn;
         __syncthreads();                                       // B_a: XA, PB of `tile` complete; geometry of tn in slot cur ^ 1
         dma_g(tn);
-        if (!(MVT_DW0_ABL & 1)) issue_gathers(cur ^ 1);
-        if (!(MVT_DW0_ABL & 2)) {
-            do_pe(cur ^ 1);
-            do_rgb(cur ^ 1);
-            do_geom(tnn, cur);
-        }
+        issue_gathers(cur ^ 1);
+        do_pe(cur ^ 1);
+        do_rgb(cur ^ 1);
+        do_geom(tnn, cur);
         // ---- 72 MFMAs: output block nb = v % 4 of row blocks 6 (v / 4) + {0..5} ----
-        if (!(MVT_DW0_ABL & 4)) {
+        {
             const int nb = v & 3;
             const u32x4_t* pb = sP + kDw8PB + lane;
             u32x4_t b[2][3];
@@ -1496,7 +1457,7 @@ __global__ __launch_bounds__(512, 1) void dw0_split8_kernel(FieldParams p, const
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // taps and G of the next tile have landed
         __syncthreads();                                       // B_b: every wave is done reading XA / PB; PE table of tn complete
-        if (!(MVT_DW0_ABL & 8)) build(cur ^ 1, tile + stride < view_tiles);
+        build(cur ^ 1, tile + stride < view_tiles);
     }
     __syncthreads();
     // ---- outputs ----
