@@ -329,6 +329,29 @@ def load_dense(lin, kernel_io, bias):
     lin.bias.data.copy_(_t(bias))
 
 
+def load_grasp_readout(readout, arrays):
+    """delta_ngf/layers.py:8-42 `GraspReadout.weights` (Keras creation order) -> `lmvnerf.GraspReadout`, copied in place:
+    activation_downscale_1..4 (kernel (128,64), bias each); combined_activation_downscale (kernel (256,64), bias); the `readout`
+    Sequential: ResNetMLPBlock (layer_0 kernel, bias; layer_1 kernel, bias; shortcut kernel, no bias; mvnerf/layers.py:262-298),
+    ResNetMLPBlock (layer_0, layer_1), Readout(1) (output_layer kernel, bias when the module has one)."""
+    dense = [(lin, True) for lin in (*readout.activation_downscale, readout.combined_activation_downscale)]
+    dense += [(readout.block_0.layer_0, True), (readout.block_0.layer_1, True), (readout.block_0.shortcut, False),
+              (readout.block_1.layer_0, True), (readout.block_1.layer_1, True),
+              (readout.output_layer, readout.output_layer.bias is not None)]
+    expected = []
+    for lin, has_bias in dense:
+        expected += [(lin.in_features, lin.out_features)] + ([(lin.out_features,)] if has_bias else [])
+    arrays = [np.asarray(a, dtype=np.float32) for a in arrays]
+    if [a.shape for a in arrays] != expected:
+        raise ValueError(f'grasp readout: variable shapes {[a.shape for a in arrays]} do not match the Keras creation order {expected}')
+    it = iter(arrays)
+    with torch.no_grad():
+        for lin, has_bias in dense:
+            lin.weight.copy_(_t(next(it)).T)
+            if has_bias:
+                lin.bias.copy_(_t(next(it)))
+
+
 def load_batchnorm(bn, gamma, beta, moving_mean, moving_var):
     bn.weight.data.copy_(_t(gamma))
     bn.bias.data.copy_(_t(beta))
@@ -499,4 +522,4 @@ def count_parameters(module):
 __all__ = ['FeatureProducer', 'VisualFeatures', 'CombineCLIPVisualV0', 'ConvolutionalEncoder', 'VisionTransformerEncoder',
            'VisionTransformer', 'TransformerBlock', 'SyntheticCLIPStage1', 'flat_net_from_keras', 'keras_from_flat_net',
            'make_encoder_optimizer', 'KerasAdam', 'convolutional_encoder_weights', 'warmup_lr_lambda', 'load_conv', 'load_conv_transpose', 'load_dense', 'load_batchnorm', 'load_mha',
-           'load_combine_clip_visual', 'load_convolutional_encoder', 'load_transformer_block', 'count_parameters']
+           'load_combine_clip_visual', 'load_grasp_readout', 'load_convolutional_encoder', 'load_transformer_block', 'count_parameters']

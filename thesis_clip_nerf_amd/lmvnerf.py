@@ -15,6 +15,7 @@ Names and argument meaning follow the reference (`_call`, `compute_matrices`, `s
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -385,6 +386,25 @@ def kl_divergence(y_true, y_pred):
     return (y_true * torch.log(y_true / y_pred)).sum(-1)
 
 
+def categorical_crossentropy_from_logits(y_true, y_pred):
+    """tf.keras.losses.CategoricalCrossentropy(from_logits=True) (train_language.py:56-57): -sum(y_true * log_softmax(logits)) over the
+    last axis, mean over the batch (SUM_OVER_BATCH_SIZE)."""
+    return -(y_true * torch.log_softmax(y_pred, -1)).sum(-1).mean()
+
+
+# ---- checkpoint files (model_v4.py:132-174) -----------------------------------------------------------------
+_BACKBONE_FILES = ('fine_embedding', 'fine_readout')        # what MVVNeRFRenderer.store writes for the fine MLP (model._SUBMODELS)
+
+
+def store_trunk(path, trunk_net):
+    """Write a flat Keras-order MLP (247 300 floats) as `{path}_fine_embedding.pt` / `{path}_fine_readout.pt`, the two fine-MLP files of
+    MVVNeRFRenderer.store, so either model's `load_backbone` / `load` reads them."""
+    flat = torch.as_tensor(trunk_net, dtype=torch.float32).reshape(-1).detach().cpu()
+    n_emb = flat.numel() - (128 * 4 + 4)          # model._EMB_PARAMS: the trunk; the rest is the (unused here) colour read-out
+    for name, t in zip(_BACKBONE_FILES, (flat[:n_emb], flat[n_emb:])):
+        torch.save(t.clone(), f'{path}_{name}.pt')
+
+
 def _quaternion_pose_map(offsets):
     """rotation_from_quaternion is a quadratic form in q = (x, y, z, w): R_ik = delta_ik + sum_ab q_a q_b A[ab, ik].  Folded with the gripper
     offsets, the query points and directions of ALL offsets are one product of the 16 pair products q_a q_b with a constant matrix:
@@ -446,6 +466,50 @@ class LanguageNeRF(nn.Module):
         if loss is not None:
             self.loss = loss
         self._graph_mode, self._graph, self._g_static, self._g_out, self._g_calls = bool(graph), None, None, None, 0
+
+    # -- checkpoints (model_v4.py:132-174): torch.save'd tensors, one file per sub-model, load() -> False when a file is missing --
+    # The reference also writes and reads `{path}_visual_features` / `{path}_combine_clip_visual`; here the feature map is an input
+    # (DESIGN.md 7), so those files are neither written nor read.  Loading copies IN PLACE into `trunk_net` and the read-out parameters:
+    # the Adam state, a captured training graph and DNGFOptimizer's bound views all hold those tensors.
+    def load_backbone(self, path, verbose=True):
+        """The frozen trunk from `{path}_fine_embedding.pt` + `{path}_fine_readout.pt` (MVVNeRFRenderer.store's fine MLP) -> True, or
+        False (nothing changed) if either file is missing."""
+        files = [f'{path}_{name}.pt' for name in _BACKBONE_FILES]
+        for f in files:
+            if not os.path.exists(f):
+                if verbose:
+                    print(f'{f} does not exist')
+                return False
+        flat = torch.cat([torch.load(f, weights_only=True).reshape(-1) for f in files])
+        if flat.numel() != self.trunk_net.numel():
+            raise ValueError(f'{path}: {flat.numel()} backbone parameters, expected {self.trunk_net.numel()}')
+        with torch.no_grad():
+            self.trunk_net.copy_(flat)
+        return True
+
+    def store(self, path):
+        """`{path}_fine_embedding.pt`, `{path}_fine_readout.pt` (the trunk) and `{path}_grasp_readout.pt` (the GraspReadout state dict)."""
+        store_trunk(path, self.trunk_net)
+        torch.save({k: v.detach().cpu().clone() for k, v in self.grasp_readout.state_dict().items()}, f'{path}_grasp_readout.pt')
+
+    def load(self, path):
+        """load_backbone + the read-out -> True, or False (nothing changed) if any of the three files is missing."""
+        readout_file = f'{path}_grasp_readout.pt'
+        if not all(os.path.exists(f'{path}_{name}.pt') for name in _BACKBONE_FILES):
+            print(f'backbone models at {path} do not exist')
+            return False
+        if not os.path.exists(readout_file):
+            print(f'{readout_file} does not exist')
+            return False
+        state = torch.load(readout_file, weights_only=True)
+        own = self.grasp_readout.state_dict()
+        if set(state) != set(own) or any(state[k].shape != own[k].shape for k in own):
+            raise ValueError(f'{readout_file}: the GraspReadout variables do not match this model')
+        self.load_backbone(path, verbose=False)
+        with torch.no_grad():
+            for k, t in own.items():                 # state_dict() tensors share the parameters' storage
+                t.copy_(state[k])
+        return True
 
     def set_pose(self, translations, rotations):
         with torch.no_grad():
