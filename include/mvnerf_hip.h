@@ -408,10 +408,33 @@ int mvnerf_grasp_head_fwd(const float* acts, const float* packed, const float* b
  * weight gradients are skinny GEMMs: dW_c = g_v^T c, db_c = sum g_v, dW_k = g_u[:, 64k:64k+64]^T a_k, db_k = sum g_u[:, 64k:64k+64]. */
 int mvnerf_grasp_head_vjp(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_v, float* q, float* g_u,
                           float* g_acts, mvnerf_stream_t stream);
+/* mvnerf_grasp_head_vjp for a frozen read-out (the grasp-pose optimiser): the same products in the same order, only g_acts (4, N, 128) is
+ * written - bit-identical to mvnerf_grasp_head_vjp's g_acts, without the 576 floats per point of g_v, q, g_u. */
+int mvnerf_grasp_head_vjp_acts(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_acts,
+                               mvnerf_stream_t stream);
 /* The derivative of mvnerf_grasp_head_vjp: t_acts (4, N, 128) = dL/d(g_acts) -> out_gy (N, 64) = dL/d(g_y) and r (N, 256), m (N, 64),
  * p (N, 256) with dL/dW_k = g_u_k^T t_k + p_k^T a_k, dL/db_k = sum p_k, dL/dW_c = g_v^T r + m^T c, dL/db_c = sum m. */
 int mvnerf_grasp_head_vjp_bwd(const float* t_acts, const float* g_y, const float* c, const float* y, const float* q, const float* packed, long N,
                               float* out_gy, float* r, float* m, float* p, mvnerf_stream_t stream);
+
+/* ---- the per-pose part of GraspReadout (delta_ngf/layers.py:24-28, 39-41; ResNetMLPBlock, mvnerf/layers.py:262-298) with frozen weights:
+ * for M = B * P rows x (M, K = 64 n5) = the head's y viewed 'b np n5 d -> (b np) (n5 d)',
+ *     h0 = elu(x) W0^T + b0 (K -> 128);  x1 = x Ws^T + elu(h0) W1^T + b1 (-> 64);  h1 = elu(x1) W0'^T + b0';  x2 = x1 + elu(h1) W1'^T + b1';
+ *     success = relu(x2) . w_out + b_out.
+ * fp32 (v_mfma_f32_32x32x2_f32), one workgroup per 32 rows, no sums across workgroups: the same bits from run to run.  Any M >= 1, n5 >= 1.
+ * Weights in torch layout [out, in]: w0 (128, K), b0 (128), w1 (64, 128), b1 (64), ws (64, K) = block_0's shortcut, w0b, w1b (64, 64),
+ * b0b, b1b (64) = block_1, w_out (64), b_out (1) or NULL (a read-out without bias).  packed: mvnerf_grasp_tail_packed_floats(n5) floats. */
+size_t mvnerf_grasp_tail_packed_floats(int n5);
+int mvnerf_grasp_tail_pack(const float* w0, const float* b0, const float* w1, const float* b1, const float* ws, const float* w0b, const float* b0b,
+                           const float* w1b, const float* b1b, const float* w_out, const float* b_out, int n5, float* packed,
+                           mvnerf_stream_t stream);
+/* x (M, 64 n5) -> success (M).  stash (optional): (M, 320) floats = the pre-activations [h0 | x1 | h1 | x2] mvnerf_grasp_tail_vjp reads;
+ * NULL = value only.  x, packed, stash 16-byte aligned. */
+int mvnerf_grasp_tail_fwd(const float* x, const float* packed, long M, int n5, float* success, float* stash, mvnerf_stream_t stream);
+/* g_s (M) = d L / d success (NULL = ones: L = sum of success) -> g_x (M, 64 n5) = (g_h0 W0) . elu'(x) + g_x1 Ws, with elu' taken from x
+ * and g_h0, g_x1 from the stashed chain.  x, stash: as given to / written by mvnerf_grasp_tail_fwd. */
+int mvnerf_grasp_tail_vjp(const float* x, const float* g_s, const float* stash, const float* packed, long M, int n5, float* g_x,
+                          mvnerf_stream_t stream);
 
 /* ---- the grasp-pose optimiser (DNGFOptimizer, lmvnerf/grasp_optimizer.py:28-184; its loop, utils/optimization.py:40-152): the pose side
  * of one optimisation step.  P poses: t (P, 3), rot (P, 4) quaternion (x, y, z, w; rep 0) or (P, 6) 6d ([r1 | r2]; rep 1); offsets (n5, 4, 4)
@@ -444,6 +467,51 @@ typedef struct mvnerf_pose_adam_config {
 /* cfg is [host]; g_t, m_t, v_t, t: (P, 3); g_rot, m_r, v_r, rot: (P, 4|6).  In place on t, rot, m_*, v_*, counters. */
 int mvnerf_pose_adam_step(const mvnerf_pose_adam_config* cfg, int rep, int P, const int* train_flags, int* counters, const float* g_t,
                           const float* g_rot, float* m_t, float* v_t, float* m_r, float* v_r, float* t, float* rot, mvnerf_stream_t stream);
+
+/* ---- one grasp-pose optimisation step behind one call (DNGFOptimizer.optimize_pose, lmvnerf/grasp_optimizer.py:158-184, through
+ * LanguageNeRF._call, lmvnerf/model_v4.py:208-265): poses -> query points -> frozen trunk with stash -> GraspReadout (head, per-pose tail) ->
+ * success, and back: tail VJP -> head VJP -> trunk VJP -> pose VJP -> clip, Keras Adam, post_process.  Nothing is allocated, nothing
+ * synchronises with the host, every launch goes to `stream`: a step can be captured in a HIP graph (the phase switches through the
+ * device-resident train_flags).  For V > 1 every scene's P * n5 rows are padded to whole 32-point tiles inside the workspace (the last point
+ * repeated, its cotangents zero). */
+typedef struct mvnerf_grasp_call {
+    /* the scene: device pointers, layouts as in mvnerf_query_vjp */
+    const float* images;          /* (B,V,H,W,3) */
+    const float* features;        /* (B,V,H,W,256) */
+    const float* intrinsics;      /* (B,V,4,4) */
+    const float* extrinsics_inv;  /* (B,V,4,4) */
+    int B, V, H, W;
+    /* the frozen trunk */
+    const float* packed_net;      /* mvnerf_pack_net */
+    const void* split;            /* mvnerf_pack_net_split */
+    const float* bwd_streams;     /* mvnerf_pack_bwd_streams */
+    /* the frozen read-out */
+    const float* head_packed;     /* mvnerf_grasp_head_pack */
+    const float* head_b4;         /* (4, 64) */
+    const float* head_bc;         /* (64) */
+    const float* tail_packed;     /* mvnerf_grasp_tail_pack for the same n5 */
+    const float* offsets;         /* (n5, 4, 4) transforms_to_check */
+    int rep, P, n5;               /* rep: 0 quaternion (x, y, z, w), 1 6d */
+    /* the pose state (updated in place by mvnerf_grasp_opt_step) and the outputs */
+    float* t;                     /* (P, 3) */
+    float* rot;                   /* (P, 4 | 6) */
+    float* success;               /* (B, P): the poses' predicted success per scene, before the step */
+    float* g_t;                   /* (P, 3)     d(-sum success) / d t     (not needed by mvnerf_grasp_success) */
+    float* g_rot;                 /* (P, 4 | 6) d(-sum success) / d rot   (likewise) */
+    void* workspace;              /* 256-byte aligned, >= mvnerf_grasp_workspace_bytes(B, V, P, n5) */
+    size_t workspace_bytes;
+} mvnerf_grasp_call;
+
+/* Bytes of workspace: points, dirs, zero depths and the field kernel's output and scratch, the trunk stash, the fused activations, the head's
+ * c and y, the tail stash, g_x, g_acts, the trunk VJP's scratch and d_points / d_dirs.  0 for non-positive sizes. */
+size_t mvnerf_grasp_workspace_bytes(int B, int V, int P, int n5);
+/* Stages 1-4, value only: success (B, P)  (DNGFOptimizer.compute_current_grasp_success before its sum over scenes). */
+int mvnerf_grasp_success(const mvnerf_grasp_call* call, mvnerf_stream_t stream);
+/* Stages 1-7: success, and g_t, g_rot = d(-sum success) / d(t, rot) (grasp_optimizer.py:171-178). */
+int mvnerf_grasp_success_and_gradients(const mvnerf_grasp_call* call, mvnerf_stream_t stream);
+/* Stages 1-8: the above followed by mvnerf_pose_adam_step on t, rot (arguments as there; cfg is [host]). */
+int mvnerf_grasp_opt_step(const mvnerf_grasp_call* call, const mvnerf_pose_adam_config* cfg, const int* train_flags, int* counters, float* m_t,
+                          float* v_t, float* m_r, float* v_r, mvnerf_stream_t stream);
 
 /* ---- the whole training step behind one call (MVVNeRFRenderer.train_step, model_v0.py:186-197: GradientTape over call(),
  * loss = MSE(y, rgb) + MSE(y, fine_rgb) :193, gradients :194, optimize() :195 = nerf_utils.py:8-12) ----

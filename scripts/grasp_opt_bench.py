@@ -8,8 +8,11 @@ Reports (device events after warm-up):
   step graph       the same step as one HIP graph replay (compile(graph=True))
   trunk fwd / vjp  query_stash (+ stash_fused_acts) and query_vjp alone on the same query points (the floor of the step)
   compute_results  wall time of the whole validation call (16 + 16 steps, graph mode), ending in a device synchronise
-Usage: python scripts/grasp_opt_bench.py [--poses 4096] [--images 3] [--size 480 640] [--steps 16] [--reps 10] [--trace N]
---trace N: only N eager steps after two warm-up steps (for rocprofv3 --kernel-trace: calls / N = launches per step)."""
+Usage: python scripts/grasp_opt_bench.py [--poses 4096] [--images 3] [--size 480 640] [--steps 16] [--reps 10] [--step torch fused] [--trace N]
+--step: which step runs - torch (stage 4 as torch modules + autograd, the default) and / or fused (compile(fused=True): the whole step
+one call of mvnerf_grasp_opt_step).  With both, the four legs (torch / fused x eager / graph) alternate inside every round of one process;
+the fused legs report as step_fused_eager_ms / step_fused_graph_ms.
+--trace N: only N eager steps of the first --step leg after two warm-up steps (for rocprofv3 --kernel-trace: calls / N = launches per step)."""
 import argparse
 import json
 import os
@@ -32,6 +35,7 @@ ap.add_argument('--size', type=int, nargs=2, default=[480, 640])
 ap.add_argument('--steps', type=int, default=16, help='n_optimization_steps per phase')
 ap.add_argument('--reps', type=int, default=10, help='timed steps per leg')
 ap.add_argument('--trace', type=int, default=0)
+ap.add_argument('--step', nargs='+', choices=['torch', 'fused'], default=['torch'], help='step legs to time (alternating rounds)')
 args = ap.parse_args()
 dev = torch.device('cuda:0')
 h, w = args.size
@@ -48,9 +52,9 @@ torch.manual_seed(0)
 model = LanguageNeRF(sc['fine'], n_views=1, rotation_representation='6d', device=dev)
 
 
-def optimiser(graph):
+def optimiser(graph, fused=False):
     opt = DNGFOptimizer(model, BOUNDS, n_initial_guesses=P, n_images=NI, clip_translation=True, rotation_representation='6d')
-    opt.compile(graph=graph)
+    opt.compile(graph=graph, fused=fused)
     opt.set_initial_guesses([g[:1] for g in opt.generate_initial_guesses(rng=np.random.default_rng(0))])
     opt.bind(inputs, feats)
     return opt
@@ -67,32 +71,41 @@ def timed(fn, reps):
 
 
 if args.trace:
-    opt = optimiser(False)
+    opt = optimiser(False, args.step[0] == 'fused')
     for _ in range(2):
         opt.optimize_pose(inputs, feats, [True, False])
     torch.cuda.synchronize()
     for i in range(args.trace):
         opt.optimize_pose(inputs, feats, [i % 2 == 0, i % 2 == 1])
     torch.cuda.synchronize()
-    print(json.dumps({'trace_steps': args.trace, 'poses': P, 'images': NI}))
+    print(json.dumps({'trace_steps': args.trace, 'step': args.step[0], 'poses': P, 'images': NI}))
     sys.exit(0)
 
 n_query = NI * P * model.n_transforms_to_check
 res = {'poses': P, 'images': NI, 'views': 1, 'size': [h, w], 'rotation': '6d', 'query_points_per_step': n_query}
-opt_e = optimiser(False)
-for _ in range(3):
-    opt_e.optimize_pose(inputs, feats, [True, False])
-opt_g = optimiser(True)
-for _ in range(4):
-    opt_g.optimize_pose(inputs, feats, [True, False])
-# the two legs alternate (5 rounds each): the GPU is shared, so a difference counts only against the spread of its own rounds
-legs = {'eager': [], 'graph': []}
+steps = list(dict.fromkeys(args.step))
+res['step'] = steps
+opts = {}
+for step in steps:
+    prefix = '' if step == 'torch' else 'fused_'
+    opts[prefix + 'eager'] = optimiser(False, step == 'fused')
+    for _ in range(3):
+        opts[prefix + 'eager'].optimize_pose(inputs, feats, [True, False])
+    opts[prefix + 'graph'] = optimiser(True, step == 'fused')
+    for _ in range(4):
+        opts[prefix + 'graph'].optimize_pose(inputs, feats, [True, False])
+first = '' if steps[0] == 'torch' else 'fused_'
+opt_e, opt_g = opts[first + 'eager'], opts[first + 'graph']
+# the legs alternate (5 rounds each): the GPU is shared, so a difference counts only against the spread of its own rounds
+legs = {leg: [] for leg in opts}
 for _ in range(5):
-    for leg, opt in (('eager', opt_e), ('graph', opt_g)):
+    for leg, opt in opts.items():
         legs[leg].append(timed(lambda: opt.optimize_pose(inputs, feats, [True, False]), args.reps))
 for leg, v in legs.items():
     res[f'step_{leg}_ms'] = float(np.median(v))
     res[f'step_{leg}_ms_rounds'] = [round(x, 4) for x in v]
+if 'fused' in steps:
+    res['grasp_workspace_bytes'] = ops.grasp_workspace_bytes(NI, 1, P, model.n_transforms_to_check)
 
 # the trunk alone on the bound query points of the eager optimiser
 bd, st = opt_e._bound, opt_e._bound['state']
@@ -109,7 +122,7 @@ ops.query_vjp(bd['points'], bd['dirs'], *st.geo, st.bwd_streams, bd['stash'], g_
 res['trunk_fwd_stash_ms'] = timed(trunk_fwd, args.reps)
 res['trunk_vjp_ms'] = timed(lambda: ops.query_vjp(bd['points'], bd['dirs'], *st.geo, st.bwd_streams, bd['stash'], g_acts), args.reps)
 
-for leg, opt in (('graph', opt_g), ('eager', opt_e)):
+for leg, opt in ((first + 'graph', opt_g), (first + 'eager', opt_e)):
     compute_results(opt, inputs, feats, False, rng=np.random.default_rng(1), n_optimization_steps=2, **CFG)      # warm (same shapes)
     torch.cuda.synchronize()
     t0 = time.time()
@@ -120,9 +133,9 @@ for leg, opt in (('graph', opt_g), ('eager', opt_e)):
     res[f'compute_results_{leg}_duration_s'] = duration
     res[f'mean_success_after_t_{leg}'] = float(np.mean(losses_t))
     res[f'mean_success_after_r_{leg}'] = float(np.mean(losses_r))
-res['pose_steps_per_s'] = P / (res['step_graph_ms'] * 1e-3)
-res['query_points_per_s'] = n_query / (res['step_graph_ms'] * 1e-3)
-res['step_over_trunk'] = res['step_graph_ms'] / (res['trunk_fwd_stash_ms'] + res['trunk_vjp_ms'])
+res['pose_steps_per_s'] = P / (res[f'step_{first}graph_ms'] * 1e-3)
+res['query_points_per_s'] = n_query / (res[f'step_{first}graph_ms'] * 1e-3)
+res['step_over_trunk'] = res[f'step_{first}graph_ms'] / (res['trunk_fwd_stash_ms'] + res['trunk_vjp_ms'])
 res['stash_bytes'] = int(bd['stash'].numel())
 res['max_memory_allocated_bytes'] = int(torch.cuda.max_memory_allocated(dev))
 print(json.dumps(res))

@@ -41,6 +41,16 @@ class PoseAdamConfig(ctypes.Structure):
                 ('clip_translation', c_int), ('lo', c_float * 3), ('hi', c_float * 3)]
 
 
+class GraspCall(ctypes.Structure):
+    """mvnerf_grasp_call (include/mvnerf_hip.h): one grasp-pose optimisation problem, field for field."""
+    _fields_ = ([(n, c_void_p) for n in ('images', 'features', 'intrinsics', 'extrinsics_inv')] +
+                [(n, c_int) for n in ('B', 'V', 'H', 'W')] +
+                [(n, c_void_p) for n in ('packed_net', 'split', 'bwd_streams', 'head_packed', 'head_b4', 'head_bc', 'tail_packed', 'offsets')] +
+                [(n, c_int) for n in ('rep', 'P', 'n5')] +
+                [(n, c_void_p) for n in ('t', 'rot', 'success', 'g_t', 'g_rot', 'workspace')] +
+                [('workspace_bytes', c_size_t)])
+
+
 class GemmTnBatch(ctypes.Structure):
     """mvnerf_gemm_tn_batch (include/mvnerf_hip.h)."""
     _fields_ = ([(n, c_void_p) for n in ('g', 'a', 'g2', 'a2')] +
@@ -115,10 +125,19 @@ SIGNATURES = {
     'mvnerf_grasp_head_pack': (c_int, [c_void_p] * 4),
     'mvnerf_grasp_head_fwd': (c_int, [c_void_p] * 4 + [c_long] + [c_void_p] * 3),
     'mvnerf_grasp_head_vjp': (c_int, [c_void_p] * 4 + [c_long] + [c_void_p] * 5),
+    'mvnerf_grasp_head_vjp_acts': (c_int, [c_void_p] * 4 + [c_long] + [c_void_p] * 2),
     'mvnerf_grasp_head_vjp_bwd': (c_int, [c_void_p] * 6 + [c_long] + [c_void_p] * 5),
+    'mvnerf_grasp_tail_packed_floats': (c_size_t, [c_int]),
+    'mvnerf_grasp_tail_pack': (c_int, [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
+    'mvnerf_grasp_tail_fwd': (c_int, [c_void_p] * 2 + [c_long, c_int] + [c_void_p] * 3),
+    'mvnerf_grasp_tail_vjp': (c_int, [c_void_p] * 4 + [c_long, c_int] + [c_void_p] * 2),
     'mvnerf_pose_query_points': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
     'mvnerf_pose_query_vjp': (c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_long, c_float, c_void_p, c_void_p, c_void_p]),
     'mvnerf_pose_adam_step': (c_int, [ctypes.POINTER(PoseAdamConfig), c_int, c_int] + [c_void_p] * 11),
+    'mvnerf_grasp_workspace_bytes': (c_size_t, [c_int] * 4),
+    'mvnerf_grasp_success': (c_int, [ctypes.POINTER(GraspCall), c_void_p]),
+    'mvnerf_grasp_success_and_gradients': (c_int, [ctypes.POINTER(GraspCall), c_void_p]),
+    'mvnerf_grasp_opt_step': (c_int, [ctypes.POINTER(GraspCall), ctypes.POINTER(PoseAdamConfig)] + [c_void_p] * 7),
     'mvnerf_train_workspace_bytes': (c_size_t, [c_int] * 8),
     'mvnerf_loss_and_grads': (c_int, [ctypes.POINTER(TrainCall), c_void_p]),
     'mvnerf_apply_gradients': (c_int, [ctypes.POINTER(TrainCall), ctypes.POINTER(AdamState), c_void_p]),

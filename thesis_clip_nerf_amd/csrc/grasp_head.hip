@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mvnerf_hip.h"
+#include "mvnerf_blocks.h"
 #include "mvnerf_kernels.h"
 #include "mvnerf_mfma.h"
 
@@ -59,69 +60,6 @@ __global__ void grasp_head_pack_kernel(const float* __restrict__ w4 /*(4,64,128)
     dst[idx] = val;
 }
 
-// acc[nbo] += A^T-product over KB input blocks held in accumulator order.  The A chunks of step (kb, t) + 1 are requested before the
-// MFMAs of step (kb, t) are issued and pinned there (the weights come from L2: a round trip is as long as a step's 4 x NBO MFMAs).
-template <int KB, int NBO>
-__device__ __forceinline__ void dense_blocks(const float* __restrict__ packed, int lane, const f32x16 (&in)[KB], f32x16 (&acc)[NBO]) {
-    const f32x4* w = reinterpret_cast<const f32x4*>(packed) + lane;
-    f32x4 a[NBO], an[NBO];
-#pragma unroll
-    for (int nbo = 0; nbo < NBO; ++nbo) a[nbo] = w[nbo * 64];
-#pragma unroll
-    for (int st = 0; st < KB * 4; ++st) {
-        const int kb = st >> 2, t = st & 3;
-        if (st + 1 < KB * 4) {
-#pragma unroll
-            for (int nbo = 0; nbo < NBO; ++nbo) an[nbo] = w[((st + 1) * NBO + nbo) * 64];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int nbo = 0; nbo < NBO; ++nbo) acc[nbo] = mfma(a[nbo][e], in[kb][4 * t + e], acc[nbo]);
-        if (st + 1 < KB * 4) {
-#pragma unroll
-            for (int nbo = 0; nbo < NBO; ++nbo) a[nbo] = an[nbo];
-        }
-    }
-}
-
-// block nb (32 features) of row `point` of a row-major (N, F) tensor, in accumulator order: lane (j, h) register 4q + c = feature
-// 32 nb + 8 q + 4 h + c
-__device__ __forceinline__ f32x16 load_block(const float* __restrict__ rows, long point, int F, int nb, int h) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(rows + point * F + 32 * nb + 4 * h);
-    f32x16 v;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x4 t4 = p[2 * q];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[4 * q + c] = t4[c];
-    }
-    return v;
-}
-
-__device__ __forceinline__ void store_block(float* __restrict__ rows, long point, int F, int nb, int h, const f32x16& v) {
-    f32x4* p = reinterpret_cast<f32x4*>(rows + point * F + 32 * nb + 4 * h);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x4 t4 = {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
-        p[2 * q] = t4;
-    }
-}
-
-// bias (F floats, plain order) of block nb in accumulator order
-__device__ __forceinline__ f32x16 bias_block(const float* __restrict__ bias, int nb, int h) {
-    f32x16 v;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = bias[32 * nb + (r & 3) + 8 * (r >> 2) + 4 * h];
-    return v;
-}
-
-__device__ __forceinline__ float elu1(float x) { return x > 0.0f ? x : expm1f(x); }
-// derivatives of elu in terms of its OUTPUT e = elu(u): elu'(u) = u > 0 ? 1 : e + 1 ; elu''(u) = u > 0 ? 0 : e + 1   (e > 0 <=> u > 0)
-__device__ __forceinline__ float delu(float e) { return e > 0.0f ? 1.0f : e + 1.0f; }
-__device__ __forceinline__ float ddelu(float e) { return e > 0.0f ? 0.0f : e + 1.0f; }
-
 // ---- value: acts (4, N, 128) -> c (N, 256) = [elu(u_k)], y (N, 64) ------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void grasp_head_fwd_kernel(const float* __restrict__ acts, const float* __restrict__ packed,
                                                               const float* __restrict__ b4, const float* __restrict__ bc, long N,
@@ -159,6 +97,8 @@ __global__ __launch_bounds__(256) void grasp_head_fwd_kernel(const float* __rest
 // ---- vector-Jacobian product: g_y (N, 64) -> g_v (N, 64), q (N, 256), g_u (N, 256), g_acts (4, N, 128) ---------------------------------
 //   g_v = g_y . elu'(v);  q_k = W_c[:,k]^T g_v;  g_u_k = q_k . elu'(u_k);  g_a_k = W_k^T g_u_k
 //   (weight gradients afterwards: dW_c = g_v^T c, db_c = sum g_v, dW_k = g_u_k^T a_k, db_k = sum g_u_k)
+//   kAll = false: the frozen read-out's form (the grasp-pose optimiser) - the same products in the same order, only g_acts is stored
+template <bool kAll>
 __global__ __launch_bounds__(256) void grasp_head_vjp_kernel(const float* __restrict__ g_y, const float* __restrict__ c, const float* __restrict__ y,
                                                               const float* __restrict__ packed, long N, float* __restrict__ g_v_out,
                                                               float* __restrict__ q_out, float* __restrict__ g_u_out, float* __restrict__ g_acts) {
@@ -174,7 +114,7 @@ __global__ __launch_bounds__(256) void grasp_head_vjp_kernel(const float* __rest
         const f32x16 gy = load_block(g_y, pt, 64, nb, h), yy = load_block(y, pt, 64, nb, h);
 #pragma unroll
         for (int r = 0; r < 16; ++r) gv[nb][r] = gy[r] * delu(yy[r]);
-        if (ok) store_block(g_v_out, pt, 64, nb, h, gv[nb]);
+        if (kAll && ok) store_block(g_v_out, pt, 64, nb, h, gv[nb]);
     }
 #pragma unroll 1
     for (int k = 0; k < 4; ++k) {
@@ -190,7 +130,7 @@ __global__ __launch_bounds__(256) void grasp_head_vjp_kernel(const float* __rest
             const f32x16 ck = load_block(c, pt, 256, 2 * k + nb, h);
 #pragma unroll
             for (int r = 0; r < 16; ++r) gu[nb][r] = q[nb][r] * delu(ck[r]);
-            if (ok) {
+            if (kAll && ok) {
                 store_block(q_out, pt, 256, 2 * k + nb, h, q[nb]);
                 store_block(g_u_out, pt, 256, 2 * k + nb, h, gu[nb]);
             }
@@ -312,7 +252,13 @@ hipError_t launch_grasp_head_fwd(const float* acts, const float* packed, const f
 
 hipError_t launch_grasp_head_vjp(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_v, float* q, float* g_u,
                                  float* g_acts, hipStream_t st) {
-    hipLaunchKernelGGL(grasp_head_vjp_kernel, dim3(head_grid(N)), dim3(256), 0, st, g_y, c, y, packed, N, g_v, q, g_u, g_acts);
+    hipLaunchKernelGGL(grasp_head_vjp_kernel<true>, dim3(head_grid(N)), dim3(256), 0, st, g_y, c, y, packed, N, g_v, q, g_u, g_acts);
+    return hipGetLastError();
+}
+
+hipError_t launch_grasp_head_vjp_acts(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_acts, hipStream_t st) {
+    float* none = nullptr;
+    hipLaunchKernelGGL(grasp_head_vjp_kernel<false>, dim3(head_grid(N)), dim3(256), 0, st, g_y, c, y, packed, N, none, none, none, g_acts);
     return hipGetLastError();
 }
 
@@ -354,6 +300,14 @@ int mvnerf_grasp_head_vjp(const float* g_y, const float* c, const float* y, cons
     if (!al16(g_y) || !al16(c) || !al16(y) || !al16(packed) || !al16(g_v) || !al16(q) || !al16(g_u) || !al16(g_acts))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_head_vjp: every buffer must be 16-byte aligned");
     return hs(mvnerf::launch_grasp_head_vjp(g_y, c, y, packed, N, g_v, q, g_u, g_acts, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_vjp");
+}
+
+int mvnerf_grasp_head_vjp_acts(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_acts, mvnerf_stream_t stream) {
+    if (!g_y || !c || !y || !packed || !g_acts) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_vjp_acts: null pointer");
+    if (N <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_vjp_acts: N=%ld", N);
+    if (!al16(g_y) || !al16(c) || !al16(y) || !al16(packed) || !al16(g_acts))
+        return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_head_vjp_acts: every buffer must be 16-byte aligned");
+    return hs(mvnerf::launch_grasp_head_vjp_acts(g_y, c, y, packed, N, g_acts, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_vjp_acts");
 }
 
 int mvnerf_grasp_head_vjp_bwd(const float* t_acts, const float* g_y, const float* c, const float* y, const float* q, const float* packed, long N,

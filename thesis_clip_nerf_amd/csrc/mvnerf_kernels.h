@@ -82,8 +82,16 @@ hipError_t launch_grasp_head_pack(const float* w4, const float* wc, float* packe
 hipError_t launch_grasp_head_fwd(const float* acts, const float* packed, const float* b4, const float* bc, long N, float* c, float* y, hipStream_t st);
 hipError_t launch_grasp_head_vjp(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_v, float* q, float* g_u,
                                  float* g_acts, hipStream_t st);
+hipError_t launch_grasp_head_vjp_acts(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_acts, hipStream_t st);
 hipError_t launch_grasp_head_vjp_bwd(const float* t_acts, const float* g_y, const float* c, const float* y, const float* q, const float* packed,
                                      long N, float* out_gy, float* r, float* m, float* p, hipStream_t st);
+
+// grasp_tail.hip: the per-pose part of GraspReadout with frozen weights (value, VJP).  w: the 11 tensors of mvnerf_grasp_tail_pack in its order
+size_t grasp_tail_packed_floats(int n5);
+size_t grasp_tail_stash_floats();
+hipError_t launch_grasp_tail_pack(const float* const* w, int n5, float* packed, hipStream_t st);
+hipError_t launch_grasp_tail_fwd(const float* x, const float* packed, long M, int n5, float* success, float* stash, hipStream_t st);
+hipError_t launch_grasp_tail_vjp(const float* x, const float* g_s, const float* stash, const float* packed, long M, int n5, float* g_x, hipStream_t st);
 
 hipError_t launch_get_rays(const double* m9, const double* origin3, const float* u, const float* v, int n_rays,
                            int width, int normalize, float* rays_o, float* rays_d, double* rays_d64,

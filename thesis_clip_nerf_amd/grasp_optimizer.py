@@ -15,7 +15,10 @@ One step is an explicit pipeline, not autograd over the whole model:
   7. mvnerf_pose_query_vjp          -> d(-success)/d(t, rot), fixed-order per-pose sums
   8. mvnerf_pose_adam_step          clip, Adam with the decayed rate computed on the device, post_process
 Nothing per step comes from the host, so `compile(graph=True)` captures one step and replays it for both phases (the phase is a
-device-side flag pair).  TF / scipy semantics restated here are parity-unpinned, like the other third-party definitions.
+device-side flag pair).  `compile(fused=True)` runs the same eight stages behind the C ABI instead - stage 4 as the HIP kernels of
+csrc/grasp_tail.hip, stage 5 writing g_acts only, the whole step one call of mvnerf_grasp_opt_step on a workspace allocated in `bind()` -
+so that no torch module, autograd graph or per-step allocation is left in it.  TF / scipy semantics restated here are
+parity-unpinned, like the other third-party definitions.
 """
 from __future__ import annotations
 
@@ -94,14 +97,19 @@ class DNGFOptimizer:
         self.optimizer = None
         self._adam_cfg = None
         self._graph_mode = False
+        self._fused = False
         self._bound = None
         self._graph, self._g_out, self._g_calls, self._g_cfg = None, None, 0, None
 
     # -- reference API --
-    def compile(self, optimizer=None, graph=None):
+    def compile(self, optimizer=None, graph=None, fused=None):
         """optimizer: [translations, rotations] as two `KerasAdam` (the reference passes two keras Adams, optimization.py:61-62), or one
         for both.  A new optimiser starts fresh: moments and step counters are zeroed.  graph=True: `optimize_pose` runs two steps
-        eagerly, captures the third as a HIP graph and replays it from then on (None keeps the current mode)."""
+        eagerly, captures the third as a HIP graph and replays it from then on (None keeps the current mode).  fused=True: the step,
+        `success_and_gradients` and `compute_current_grasp_success` are single calls of the C entry points mvnerf_grasp_opt_step /
+        _success_and_gradients / _success (None keeps the current mode; changing it drops a captured graph)."""
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f'fused: expected None, True or False, got {fused!r}')
         if optimizer is None:
             optimizer = [KerasAdam(), KerasAdam()]
         if isinstance(optimizer, KerasAdam):
@@ -117,6 +125,9 @@ class DNGFOptimizer:
             buf.zero_()
         if graph is not None:
             self._graph_mode = bool(graph)
+        if fused is not None and fused != self._fused:
+            self._fused = fused
+            self._graph, self._g_out, self._g_calls = None, None, 0
         key = self._cfg_key()
         if self._g_cfg != key:                 # the captured launch holds the configuration as kernel arguments
             self._graph, self._g_out, self._g_calls = None, None, 0
@@ -222,6 +233,8 @@ class DNGFOptimizer:
             for old, new in ((bd['state'].packed, state.packed), (bd['state'].packed_split, state.packed_split),
                              (bd['state'].bwd_streams, state.bwd_streams), (bd['head'], head), (bd['b4'], b4), (bd['bc'], bc)):
                 old.copy_(new)
+            if 'fused' in bd:
+                self._pack_tail(out=bd['fused']['tail'])
             return bd
         b, v = self.batch_size, g.n_views
         n5 = g.n_transforms_to_check
@@ -236,7 +249,32 @@ class DNGFOptimizer:
                            tail={name: {k_: p.detach() for k_, p in getattr(ro, name).named_parameters()}
                                  for name in ('block_0', 'block_1', 'output_layer')})
         self._graph, self._g_out, self._g_calls = None, None, 0
+        if self._fused:
+            self._fused_state()
         return self._bound
+
+    def _pack_tail(self, out=None):
+        ro = self.nerf_grasper.grasp_readout
+        d = lambda lin: (lin.weight.detach().contiguous(), None if lin.bias is None else lin.bias.detach().contiguous())
+        (w0, b0), (w1, b1), (ws, _) = d(ro.block_0.layer_0), d(ro.block_0.layer_1), d(ro.block_0.shortcut)
+        (w0b, b0b), (w1b, b1b) = d(ro.block_1.layer_0), d(ro.block_1.layer_1)
+        return ops.grasp_tail_pack((w0, b0, w1, b1, ws), (w0b, b0b, w1b, b1b), d(ro.output_layer), out=out)
+
+    def _fused_state(self):
+        """The fused step's buffers for the bound inputs: the packed tail, the workspace, success (B, P) and the filled mvnerf_grasp_call.
+        Built once per binding (in `bind()` when fused is on, or at the first fused call after it was switched on)."""
+        bd, g = self._bound, self.nerf_grasper
+        if 'fused' not in bd:
+            st, b, p = bd['state'], self.batch_size, self.n_initial_guesses
+            dev = self.device_
+            tail = self._pack_tail()
+            ws = torch.empty(ops.grasp_workspace_bytes(b, g.n_views, p, bd['n5']), dtype=torch.uint8, device=dev)
+            success = torch.zeros((b, p), dtype=torch.float32, device=dev)
+            offsets = g.transforms_to_check.contiguous()
+            call = ops.grasp_call(*st.geo, st.packed, st.packed_split, st.bwd_streams, bd['head'], bd['b4'], bd['bc'], tail, offsets,
+                                  self.translations, self.rotations, success, self._g_t, self._g_r, ws)
+            bd['fused'] = dict(tail=tail, ws=ws, success=success, offsets=offsets, call=call)
+        return bd['fused']
 
     def _readout_tail(self, x):
         """GraspReadout after the fused head (delta_ngf/layers.py:38-42) with the bound, detached weights: x (B, P, n5 * 64) -> (B, P)."""
@@ -261,6 +299,10 @@ class DNGFOptimizer:
 
     def success_and_gradients(self):
         """Steps 1-7 on the bound inputs: -> success (B, P), and d(-sum success)/d(t, rot) in the step's gradient buffers (P, 3), (P, 4|6)."""
+        if self._fused:
+            fs = self._fused_state()
+            ops.grasp_success_and_gradients(fs['call'], self.translations)
+            return fs['success'].clone(), self._g_t, self._g_r
         bd, g = self._bound, self.nerf_grasper
         st, n, ld, b, n5 = bd['state'], bd['n'], bd['ld'], self.batch_size, bd['n5']
         c, y = self._forward()
@@ -278,6 +320,11 @@ class DNGFOptimizer:
         return success.detach(), self._g_t, self._g_r
 
     def _step(self):
+        if self._fused:
+            fs = self._fused_state()
+            ops.grasp_opt_step(fs['call'], self._adam_cfg, self._flags, self._counters, self._m_t, self._v_t, self._m_r, self._v_r,
+                               self.translations)
+            return fs['success']
         success, g_t, g_r = self.success_and_gradients()
         ops.pose_adam_step(self._adam_cfg, self._flags, self._counters, g_t, g_r, self._m_t, self._v_t, self._m_r, self._v_r,
                            self.translations, self.rotations)
@@ -328,6 +375,10 @@ class DNGFOptimizer:
         if self._bound is None or self._bound['key'] != tuple((t.data_ptr(), tuple(t.shape)) for t in self.regroup(inputs, features)):
             self.bind(inputs, features)
         b, n5 = self.batch_size, self._bound['n5']
+        if self._fused:
+            fs = self._fused_state()
+            ops.grasp_success(fs['call'], self.translations)
+            return fs['success'].sum(0)[:, None]
         with torch.no_grad():
             _, y = self._forward()
             success = self._readout_tail(y.reshape(b, self.n_initial_guesses, n5 * 64))

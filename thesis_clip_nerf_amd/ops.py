@@ -588,6 +588,19 @@ def grasp_head_vjp(g_y, c, y, packed):
     return g_v, q, g_u, g_acts
 
 
+def grasp_head_vjp_acts(g_y, c, y, packed, out=None):
+    """mvnerf_grasp_head_vjp_acts: g_y (N,64) -> g_acts (4,N,128) only (a frozen read-out), bit-identical to grasp_head_vjp(...)[3]."""
+    _chk(g_y, 'g_y', shape=(None, 64))
+    n = g_y.shape[0]
+    _chk(c, 'c', shape=(n, 256))
+    _chk(y, 'y', shape=(n, 64))
+    _chk(packed, 'packed', shape=(int(_lib.lib().mvnerf_grasp_head_packed_floats()),))
+    g_acts = torch.empty((4, n, 128), dtype=torch.float32, device=g_y.device) if out is None else _chk(out, 'out', shape=(4, n, 128))
+    with torch.cuda.device(g_y.device):
+        _lib.check(_lib.lib().mvnerf_grasp_head_vjp_acts(_p(g_y), _p(c), _p(y), _p(packed), n, _p(g_acts), _stream(g_y)), 'grasp_head_vjp_acts')
+    return g_acts
+
+
 def grasp_head_vjp_bwd(t_acts, g_y, c, y, q, packed):
     """t_acts (4,N,128) = dL/d(g_acts) -> out_gy (N,64) = dL/d(g_y), r (N,256), m (N,64), p (N,256) (see include/mvnerf_hip.h)."""
     _chk(t_acts, 't_acts', shape=(4, None, 128))
@@ -606,6 +619,147 @@ def grasp_head_vjp_bwd(t_acts, g_y, c, y, q, packed):
         _lib.check(_lib.lib().mvnerf_grasp_head_vjp_bwd(_p(t_acts), _p(g_y), _p(c), _p(y), _p(q), _p(packed), n, _p(out_gy), _p(r), _p(m),
                                                         _p(p_), _stream(t_acts)), 'grasp_head_vjp_bwd')
     return out_gy, r, m, p_
+
+
+# ---- the per-pose part of GraspReadout with frozen weights (csrc/grasp_tail.hip; delta_ngf/layers.py:24-28, 39-41) -------------------------
+TAIL_STASH = 320          # floats per row: the pre-activations h0 (128) | x1 | h1 | x2 (64 each)
+
+
+def grasp_tail_packed_floats(n5):
+    return int(_lib.lib().mvnerf_grasp_tail_packed_floats(int(n5)))
+
+
+def grasp_tail_pack(block_0, block_1, output_layer, out=None):
+    """The weights of GraspReadout's block_0 = (layer_0.weight (128, K), layer_0.bias, layer_1.weight (64, 128), layer_1.bias, shortcut.weight
+    (64, K)), block_1 = (layer_0.weight (64, 64), layer_0.bias, layer_1.weight (64, 64), layer_1.bias) and output_layer = (weight (1, 64) or
+    (64,), bias (1,) or None), torch [out, in] layout, K = 64 n5 -> the kernels' operand image.  out: a packed buffer to refill in place."""
+    w0, b0, w1, b1, ws = block_0
+    w0b, b0b, w1b, b1b = block_1
+    w_out, b_out = output_layer
+    _chk(w0, 'block_0.layer_0.weight', shape=(128, None))
+    k = w0.shape[1]
+    if k <= 0 or k % 64 != 0:
+        raise ValueError(f'block_0.layer_0.weight: {k} inputs, expected a multiple of 64 (n5 offsets x 64)')
+    n5 = k // 64
+    for t, name, shape in ((b0, 'block_0.layer_0.bias', (128,)), (w1, 'block_0.layer_1.weight', (64, 128)), (b1, 'block_0.layer_1.bias', (64,)),
+                           (ws, 'block_0.shortcut.weight', (64, k)), (w0b, 'block_1.layer_0.weight', (64, 64)), (b0b, 'block_1.layer_0.bias', (64,)),
+                           (w1b, 'block_1.layer_1.weight', (64, 64)), (b1b, 'block_1.layer_1.bias', (64,))):
+        _chk(t, name, shape=shape)
+    _chk(w_out, 'output_layer.weight')
+    if w_out.numel() != 64:
+        raise ValueError(f'output_layer.weight: shape {tuple(w_out.shape)}, expected (1, 64)')
+    if b_out is not None:
+        _chk(b_out, 'output_layer.bias', shape=(1,))
+    n = grasp_tail_packed_floats(n5)
+    packed = torch.empty(n, dtype=torch.float32, device=w0.device) if out is None else _chk(out, 'out', shape=(n,))
+    with torch.cuda.device(w0.device):
+        rc = _lib.lib().mvnerf_grasp_tail_pack(_p(w0), _p(b0), _p(w1), _p(b1), _p(ws), _p(w0b), _p(b0b), _p(w1b), _p(b1b), _p(w_out), _p(b_out),
+                                               n5, _p(packed), _stream(w0))
+    _lib.check(rc, 'grasp_tail_pack')
+    return packed
+
+
+def _tail_shapes(x, packed):
+    _chk(x, 'x', shape=(None, None))
+    m, k = x.shape
+    if m <= 0 or k <= 0 or k % 64 != 0:
+        raise ValueError(f'x: shape {tuple(x.shape)}, expected (M >= 1, 64 n5)')
+    _chk(packed, 'packed', shape=(grasp_tail_packed_floats(k // 64),))
+    return m, k // 64
+
+
+def grasp_tail_fwd(x, packed, stash=True, out=None):
+    """mvnerf_grasp_tail_fwd: x (M, 64 n5) -> success (M,) [, stash (M, 320) for grasp_tail_vjp].  stash: True allocates one, False / None
+    runs the value only, a tensor is written in place; out: a success tensor to write into."""
+    m, n5 = _tail_shapes(x, packed)
+    success = torch.empty(m, dtype=torch.float32, device=x.device) if out is None else _chk(out, 'out', shape=(m,))
+    if stash is True:
+        stash = torch.empty((m, TAIL_STASH), dtype=torch.float32, device=x.device)
+    elif stash is False:
+        stash = None
+    if stash is not None:
+        _chk(stash, 'stash', shape=(m, TAIL_STASH))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().mvnerf_grasp_tail_fwd(_p(x), _p(packed), m, n5, _p(success), _p(stash), _stream(x)), 'grasp_tail_fwd')
+    return success if stash is None else (success, stash)
+
+
+def grasp_tail_vjp(x, stash, packed, g_s=None, out=None):
+    """mvnerf_grasp_tail_vjp: cotangent g_s (M,) of success (None: ones) -> g_x (M, 64 n5)."""
+    m, n5 = _tail_shapes(x, packed)
+    _chk(stash, 'stash', shape=(m, TAIL_STASH))
+    if g_s is not None:
+        _chk(g_s, 'g_s', shape=(m,))
+    g_x = torch.empty_like(x) if out is None else _chk(out, 'out', shape=(m, 64 * n5))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().mvnerf_grasp_tail_vjp(_p(x), _p(g_s), _p(stash), _p(packed), m, n5, _p(g_x), _stream(x)), 'grasp_tail_vjp')
+    return g_x
+
+
+# ---- one grasp-pose optimisation step behind the C ABI (csrc/grasp_api.hip; lmvnerf/grasp_optimizer.py:158-184) ------------------------------
+def grasp_workspace_bytes(b, v, p, n5):
+    return int(_lib.lib().mvnerf_grasp_workspace_bytes(int(b), int(v), int(p), int(n5)))
+
+
+def grasp_call(images, features, intrinsics, extrinsics_inv, packed_net, split, bwd_streams, head_packed, head_b4, head_bc, tail_packed, offsets,
+               t, rot, success, g_t, g_rot, workspace):
+    """Fill a mvnerf_grasp_call (include/mvnerf_hip.h) from device tensors after checking shapes; the caller keeps the tensors alive."""
+    _chk(images, 'images', shape=(None, None, None, None, 3))
+    b, v, h, w, _ = images.shape
+    _chk(features, 'features', shape=(b, v, h, w, 256))
+    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
+    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
+    _chk(packed_net, 'packed_net', shape=(packed_net_floats(),))
+    _chk(split, 'split', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_packed_net_split_bytes()),))
+    _chk(bwd_streams, 'bwd_streams', shape=(15 * 16384,))
+    _chk(head_packed, 'head_packed', shape=(int(_lib.lib().mvnerf_grasp_head_packed_floats()),))
+    _chk(head_b4, 'head_b4', shape=(4, 64))
+    _chk(head_bc, 'head_bc', shape=(64,))
+    _chk(offsets, 'offsets', shape=(None, 4, 4))
+    n5 = offsets.shape[0]
+    _chk(tail_packed, 'tail_packed', shape=(grasp_tail_packed_floats(n5),))
+    p, rep, rd = _pose_shapes(t, rot)
+    _chk(success, 'success', shape=(b, p))
+    _chk(g_t, 'g_t', shape=(p, 3))
+    _chk(g_rot, 'g_rot', shape=(p, rd))
+    _chk(workspace, 'workspace', dtype=torch.uint8)
+    c = _lib.GraspCall()
+    for name, x in (('images', images), ('features', features), ('intrinsics', intrinsics), ('extrinsics_inv', extrinsics_inv),
+                    ('packed_net', packed_net), ('split', split), ('bwd_streams', bwd_streams), ('head_packed', head_packed),
+                    ('head_b4', head_b4), ('head_bc', head_bc), ('tail_packed', tail_packed), ('offsets', offsets), ('t', t), ('rot', rot),
+                    ('success', success), ('g_t', g_t), ('g_rot', g_rot), ('workspace', workspace)):
+        setattr(c, name, x.data_ptr())
+    c.B, c.V, c.H, c.W = b, v, h, w
+    c.rep, c.P, c.n5 = rep, p, n5
+    c.workspace_bytes = workspace.numel()
+    return c
+
+
+def grasp_success(call, stream_of):
+    """mvnerf_grasp_success: stages 1-4 on a filled grasp_call -> its success (B, P)."""
+    with torch.cuda.device(stream_of.device):
+        _lib.check(_lib.lib().mvnerf_grasp_success(ctypes.byref(call), _stream(stream_of)), 'grasp_success')
+
+
+def grasp_success_and_gradients(call, stream_of):
+    """mvnerf_grasp_success_and_gradients: stages 1-7 -> success, g_t, g_rot of the call."""
+    with torch.cuda.device(stream_of.device):
+        _lib.check(_lib.lib().mvnerf_grasp_success_and_gradients(ctypes.byref(call), _stream(stream_of)), 'grasp_success_and_gradients')
+
+
+def grasp_opt_step(call, cfg, train_flags, counters, m_t, v_t, m_r, v_r, stream_of):
+    """mvnerf_grasp_opt_step: stages 1-8, in place on the call's t, rot and on the Adam state (arguments as pose_adam_step)."""
+    p, rd = call.P, (4, 6)[call.rep]
+    _chk(train_flags, 'train_flags', dtype=torch.int32, shape=(2,))
+    _chk(counters, 'counters', dtype=torch.int32, shape=(2, p))
+    for x, n, width in ((m_t, 'm_t', 3), (v_t, 'v_t', 3), (m_r, 'm_r', rd), (v_r, 'v_r', rd)):
+        _chk(x, n)
+        if x.numel() != width * p:
+            raise ValueError(f'{n}: {x.numel()} floats, expected {width * p}')
+    with torch.cuda.device(stream_of.device):
+        rc = _lib.lib().mvnerf_grasp_opt_step(ctypes.byref(call), ctypes.byref(cfg), _p(train_flags), _p(counters), _p(m_t), _p(v_t), _p(m_r),
+                                              _p(v_r), _stream(stream_of))
+    _lib.check(rc, 'grasp_opt_step')
 
 
 def train_workspace_bytes(b, v, r, s, h, w, use_tables, want_d_features):

@@ -532,6 +532,8 @@ def main(argv=None):
     ap.add_argument('--decay-r', type=float, default=0.09)
     ap.add_argument('--valid-samples', type=int, nargs='+', default=[0, 4, 7], help='validation.valid_sample_indices')
     ap.add_argument('--graph', action='store_true', help='compile(graph=True) on the grasp model and the pose optimiser')
+    ap.add_argument('--fused-validation', action='store_true',
+                    help='compile(fused=True) on the validation pose optimiser: its step as one C call (mvnerf_grasp_opt_step)')
     ap.add_argument('--size', default='32', help='image size: H or HxW (reference 480x640)')
     ap.add_argument('--n-scenes', type=int, default=16)
     ap.add_argument('--n-perspectives', type=int, default=5)
@@ -563,7 +565,7 @@ def main(argv=None):
     print(f'Model loaded from {checkpoint}.' if model.load(checkpoint) else 'New model initialized.')
     optimizer = DNGFOptimizer(model, workspace_bounds=bounds, n_initial_guesses=args.n_initial_guesses, n_images=args.n_images,
                               clip_translation=True, rotation_representation=args.rotation_representation)
-    optimizer.compile(graph=args.graph)
+    optimizer.compile(graph=args.graph, fused=args.fused_validation)
     valid_data = [get_inputs(valid, i, args.n_images, device=dev) for i in args.valid_samples]
     optimization_config = dict(n_optimization_steps=args.n_optimization_steps, init_lr_t=args.init_lr_t, init_lr_r=args.init_lr_r,
                                decay_t=args.decay_t, decay_r=args.decay_r)
