@@ -1,6 +1,8 @@
 // extern "C" surface of libmvnerf_hip.so (include/mvnerf_hip.h): argument validation, launch
 // orchestration, error reporting.  No allocation, no host synchronisation, no global state besides
 // the thread-local error string; safe to call from one process per GPU on any stream.
+// Of several faults in one call the first in this order is reported: null pointers, sizes, int32 index
+// ranges, alignment.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -13,22 +15,7 @@
 #include "mvnerf_pack.h"
 
 namespace {
-
 thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int hip_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    return fail((int)e, "%s: %s", what, hipGetErrorString(e));
-}
-
 }  // namespace
 
 namespace mvnerf {
@@ -42,6 +29,13 @@ int api_fail(int code, const char* fmt, ...) {
 }  // namespace mvnerf
 
 namespace {
+
+constexpr auto& fail = mvnerf::api_fail;
+
+int hip_status(hipError_t e, const char* what) {
+    if (e == hipSuccess) return 0;
+    return fail((int)e, "%s: %s", what, hipGetErrorString(e));
+}
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -62,6 +56,83 @@ Workspace carve(void* base, long n_rays, int V, int S) {
     w.dir_bias = p;     p += (size_t)n_rays * V * 128;
     w.bytes = (size_t)(p - static_cast<float*>(base)) * sizeof(float);
     return w;
+}
+
+// ---- one field pass: the arguments of the seven mvnerf_field_eval* entry points in one shape -------------------
+struct FieldArgs {
+    const float *rays_o, *rays_d, *z, *images, *features, *texel_table, *intrinsics, *extrinsics_inv, *packed_net;
+    const void* second;          // the bf16 / split weight stream of the kernels that read one
+    int B, V, R, S, H, W;
+    float* rgbs;                 // outputs an entry point does not have stay NULL
+    int32_t* tap_idx;
+    float *pix, *embedding, *acts_per_view, *acts_fused, *stash;
+    void* workspace;
+};
+
+enum FieldKernel { kFieldFp32, kFieldBf16, kFieldBf16Maps, kFieldSplit };      // every kernel but the first reads `second`
+
+struct FieldKind {
+    FieldKernel kernel;
+    bool stash;                  // training-mode pass: `stash` is required and sets its own limits
+    int hw_code;                 // H < 2 or W < 2 is MVNERF_E_SHAPE, from the stash pair MVNERF_E_ARG
+};
+
+// Checks the arguments (null, sizes, index range, alignment) and fills the kernels' FieldParams; 0 or the error code.
+int field_params(const char* who, const FieldArgs& a, FieldKind kind, mvnerf::FieldParams* out) {
+    if (!a.rays_o || !a.rays_d || !a.z || !a.images || !a.features || !a.intrinsics || !a.extrinsics_inv || !a.packed_net || !a.rgbs ||
+        !a.workspace || (kind.kernel != kFieldFp32 && !a.second) || (kind.stash && !a.stash))
+        return fail(MVNERF_E_ARG, "%s: null pointer", who);
+    if (a.B <= 0 || a.V <= 0 || a.R <= 0 || a.S <= 0) return fail(MVNERF_E_ARG, "%s: B=%d V=%d R=%d S=%d", who, a.B, a.V, a.R, a.S);
+    if (a.H < 2 || a.W < 2) return fail(kind.hw_code, "%s: source image %dx%d, need H,W >= 2 (bilinear taps)", who, a.H, a.W);
+    if (kind.stash && a.V > 1 && ((long)a.R * a.S) % 32 != 0)
+        return fail(MVNERF_E_SHAPE, "%s: R*S=%ld must be a multiple of 32 when V > 1", who, (long)a.R * a.S);
+    const long total = (long)a.B * a.R * a.S, n_tiles = (total + 31) / 32;
+    if (total >= (1L << 31) || (long)a.B * a.V * a.H * a.W >= (1L << 31))
+        return fail(MVNERF_E_SHAPE, "%s: B*R*S=%ld or B*V*H*W too large for int32 indices", who, total);
+    if (kind.stash && (long)a.V * n_tiles >= (1L << 18))      // stash slots are addressed with 32-bit byte offsets (16 KiB per tile)
+        return fail(MVNERF_E_SHAPE, "%s: V*B*R*S/32 = %ld tiles per stash slot, at most 262143", who, (long)a.V * n_tiles);
+    if (!aligned16(a.features) || !aligned16(a.texel_table) || !aligned16(a.packed_net) || !aligned16(a.second) || !aligned16(a.rgbs) ||
+        !aligned16(a.tap_idx) || !aligned16(a.embedding) || !aligned16(a.acts_per_view) || !aligned16(a.acts_fused) || !aligned16(a.stash) ||
+        !aligned16(a.workspace))           // (NULL counts as aligned: the optional ones are checked when given)
+        return fail(MVNERF_E_ALIGN, "%s: features, texel_table, packed nets, rgbs, tap_idx, embedding, acts, stash, workspace must be 16-byte aligned", who);
+    mvnerf::FieldParams p = {};
+    p.rays_o = a.rays_o; p.rays_d = a.rays_d; p.z = a.z; p.images = a.images; p.features = a.features;
+    p.texel_table = a.texel_table;
+    p.k4 = a.intrinsics; p.einv = a.extrinsics_inv; p.net = a.packed_net; p.rgbs = a.rgbs; p.tap_idx = a.tap_idx; p.pix = a.pix;
+    p.embedding = a.embedding; p.acts_view = a.acts_per_view; p.acts_fused = a.acts_fused;
+    p.dir_bias = static_cast<float*>(a.workspace);
+    p.B = a.B; p.V = a.V; p.R = a.R; p.S = a.S; p.H = a.H; p.W = a.W;
+    p.total = total;
+    p.n_tiles = n_tiles;
+    if (a.stash) {
+        p.stash = a.stash;
+        p.stash_stride = (long)a.V * n_tiles * 4096;
+        p.stash_fused = a.stash + 7 * p.stash_stride;
+        p.stash_fused_stride = n_tiles * 4096;
+    }
+    *out = p;
+    return 0;
+}
+
+int field_pass(const char* who, const FieldArgs& a, FieldKind kind, mvnerf_stream_t stream) {
+    mvnerf::FieldParams p;
+    if (const int rc = field_params(who, a, kind, &p)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (kind.kernel == kFieldFp32) return hip_status(mvnerf::launch_field_eval(p, st), who);
+    if (kind.kernel == kFieldSplit) return hip_status(mvnerf::launch_field_eval_split(p, a.second, st), who);
+    return hip_status(mvnerf::launch_field_eval_bf16(p, a.second, st, kind.kernel == kFieldBf16Maps), who);
+}
+
+// The arguments the three mvnerf_project_texels* entry points share; 0 or the error code.
+int texels_check(const char* who, const void* features, const void* net, const void* net_b, int B, int V, int H, int W,
+                 const float* texel_table, const float* texel_table_b) {
+    if (!features || !net || !texel_table) return fail(MVNERF_E_ARG, "%s: null pointer", who);
+    if ((net_b == nullptr) != (texel_table_b == nullptr)) return fail(MVNERF_E_ARG, "%s: the second net and the second table go together", who);
+    if (B <= 0 || V <= 0 || H < 2 || W < 2) return fail(MVNERF_E_ARG, "%s: B=%d V=%d H=%d W=%d", who, B, V, H, W);
+    if ((long)B * V * H * W >= (1L << 31)) return fail(MVNERF_E_SHAPE, "%s: B*V*H*W too large for int32 indices", who);
+    if (!aligned16(features) || !aligned16(net) || !aligned16(net_b) || !aligned16(texel_table) || !aligned16(texel_table_b))
+        return fail(MVNERF_E_ALIGN, "%s: features, packed nets, texel tables must be 16-byte aligned", who);
+    return 0;
 }
 
 }  // namespace
@@ -100,40 +171,14 @@ int mvnerf_stratified_depths(const float* u, int n_rays, int n_samples, double n
                       "mvnerf_stratified_depths");
 }
 
-static int field_eval_impl(const float* rays_o, const float* rays_d, const float* z, const float* images,
-                           const float* features, const float* texel_table, const float* intrinsics,
-                           const float* extrinsics_inv, const float* packed_net, int B, int V, int R, int S, int H, int W,
-                           float* rgbs, int32_t* tap_idx, float* pix, float* embedding, float* acts_per_view,
-                           float* acts_fused, void* workspace, mvnerf_stream_t stream) {
-    if (texel_table && !aligned16(texel_table)) return fail(MVNERF_E_ALIGN, "mvnerf_field_eval_table: texel_table must be 16-byte aligned");
-    if (!rays_o || !rays_d || !z || !images || !features || !intrinsics || !extrinsics_inv || !packed_net || !rgbs || !workspace)
-        return fail(MVNERF_E_ARG, "mvnerf_field_eval: null pointer");
-    if (B <= 0 || V <= 0 || R <= 0 || S <= 0) return fail(MVNERF_E_ARG, "mvnerf_field_eval: B=%d V=%d R=%d S=%d", B, V, R, S);
-    if (H < 2 || W < 2) return fail(MVNERF_E_SHAPE, "mvnerf_field_eval: source image %dx%d, need H,W >= 2 (bilinear taps)", H, W);
-    const long total = (long)B * R * S;
-    if (total >= (1L << 31) || (long)B * V * H * W >= (1L << 31))
-        return fail(MVNERF_E_SHAPE, "mvnerf_field_eval: B*R*S=%ld or B*V*H*W too large for int32 indices", total);
-    if (!aligned16(features) || !aligned16(packed_net) || !aligned16(rgbs) || (tap_idx && !aligned16(tap_idx)) ||
-        (embedding && !aligned16(embedding)) || (acts_per_view && !aligned16(acts_per_view)) ||
-        (acts_fused && !aligned16(acts_fused)) || !aligned16(workspace))
-        return fail(MVNERF_E_ALIGN, "mvnerf_field_eval: features, packed_net, rgbs, tap_idx, embedding must be 16-byte aligned");
-    mvnerf::FieldParams p = {};
-    p.texel_table = texel_table;
-    p.rays_o = rays_o; p.rays_d = rays_d; p.z = z; p.images = images; p.features = features;
-    p.k4 = intrinsics; p.einv = extrinsics_inv; p.net = packed_net; p.rgbs = rgbs; p.tap_idx = tap_idx; p.pix = pix; p.embedding = embedding; p.acts_view = acts_per_view; p.acts_fused = acts_fused; p.dir_bias = static_cast<float*>(workspace); p.stash = nullptr; p.stash_stride = 0;
-    p.B = B; p.V = V; p.R = R; p.S = S; p.H = H; p.W = W;
-    p.total = total;
-    p.n_tiles = (total + 31) / 32;
-    return hip_status(mvnerf::launch_field_eval(p, static_cast<hipStream_t>(stream)), "mvnerf_field_eval");
-}
-
 int mvnerf_field_eval(const float* rays_o, const float* rays_d, const float* z, const float* images,
                       const float* features, const float* intrinsics, const float* extrinsics_inv,
                       const float* packed_net, int B, int V, int R, int S, int H, int W, float* rgbs,
                       int32_t* tap_idx, float* pix, float* embedding, float* acts_per_view, float* acts_fused,
                       void* workspace, mvnerf_stream_t stream) {
-    return field_eval_impl(rays_o, rays_d, z, images, features, nullptr, intrinsics, extrinsics_inv, packed_net, B, V, R, S,
-                           H, W, rgbs, tap_idx, pix, embedding, acts_per_view, acts_fused, workspace, stream);
+    const FieldArgs a = {rays_o, rays_d, z, images, features, nullptr, intrinsics, extrinsics_inv, packed_net, nullptr, B, V, R, S, H, W,
+                         rgbs, tap_idx, pix, embedding, acts_per_view, acts_fused, nullptr, workspace};
+    return field_pass("mvnerf_field_eval", a, {kFieldFp32, false, MVNERF_E_SHAPE}, stream);
 }
 
 size_t mvnerf_texel_table_bytes(int B, int V, int H, int W) {
@@ -143,15 +188,7 @@ size_t mvnerf_texel_table_bytes(int B, int V, int H, int W) {
 
 int mvnerf_project_texels2(const float* features, const float* packed_net, const float* packed_net_b, int B, int V, int H, int W,
                            float* texel_table, float* texel_table_b, mvnerf_stream_t stream) {
-    if (!features || !packed_net || !texel_table) return fail(MVNERF_E_ARG, "mvnerf_project_texels: null pointer");
-    if ((packed_net_b == nullptr) != (texel_table_b == nullptr))
-        return fail(MVNERF_E_ARG, "mvnerf_project_texels2: the second net and the second table go together");
-    if ((packed_net_b && !aligned16(packed_net_b)) || (texel_table_b && !aligned16(texel_table_b)))
-        return fail(MVNERF_E_ALIGN, "mvnerf_project_texels2: packed_net_b, texel_table_b must be 16-byte aligned");
-    if (B <= 0 || V <= 0 || H < 2 || W < 2) return fail(MVNERF_E_ARG, "mvnerf_project_texels: B=%d V=%d H=%d W=%d", B, V, H, W);
-    if ((long)B * V * H * W >= (1L << 31)) return fail(MVNERF_E_SHAPE, "mvnerf_project_texels: B*V*H*W too large for int32 indices");
-    if (!aligned16(features) || !aligned16(packed_net) || !aligned16(texel_table))
-        return fail(MVNERF_E_ALIGN, "mvnerf_project_texels: features, packed_net, texel_table must be 16-byte aligned");
+    if (const int rc = texels_check("mvnerf_project_texels", features, packed_net, packed_net_b, B, V, H, W, texel_table, texel_table_b)) return rc;
     return hip_status(mvnerf::launch_project_texels(features, packed_net, packed_net_b, (long)B * V * H * W, texel_table,
                                                     texel_table_b, static_cast<hipStream_t>(stream)),
                       "mvnerf_project_texels");
@@ -168,8 +205,9 @@ int mvnerf_field_eval_table(const float* rays_o, const float* rays_d, const floa
                             float* rgbs, int32_t* tap_idx, float* pix, float* embedding, float* acts_per_view,
                             float* acts_fused, void* workspace, mvnerf_stream_t stream) {
     if (!texel_table) return fail(MVNERF_E_ARG, "mvnerf_field_eval_table: null texel_table");
-    return field_eval_impl(rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, B, V, R,
-                           S, H, W, rgbs, tap_idx, pix, embedding, acts_per_view, acts_fused, workspace, stream);
+    const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, nullptr, B, V, R, S, H, W,
+                         rgbs, tap_idx, pix, embedding, acts_per_view, acts_fused, nullptr, workspace};
+    return field_pass("mvnerf_field_eval", a, {kFieldFp32, false, MVNERF_E_SHAPE}, stream);
 }
 
 size_t mvnerf_packed_net_bf16_bytes(void) { return mvnerf::packed_net_bf16_bytes(); }
@@ -182,63 +220,16 @@ int mvnerf_pack_net_bf16(const float* net_keras, void* packed16, mvnerf_stream_t
 
 int mvnerf_project_texels_bf16(const float* features, const void* packed16, const void* packed16_b, int B, int V, int H, int W,
                                float* texel_table, float* texel_table_b, mvnerf_stream_t stream) {
-    if (!features || !packed16 || !texel_table) return fail(MVNERF_E_ARG, "mvnerf_project_texels_bf16: null pointer");
-    if ((packed16_b == nullptr) != (texel_table_b == nullptr))
-        return fail(MVNERF_E_ARG, "mvnerf_project_texels_bf16: the second net and the second table go together");
-    if ((packed16_b && !aligned16(packed16_b)) || (texel_table_b && !aligned16(texel_table_b)))
-        return fail(MVNERF_E_ALIGN, "mvnerf_project_texels_bf16: packed16_b, texel_table_b must be 16-byte aligned");
-    if (B <= 0 || V <= 0 || H < 2 || W < 2) return fail(MVNERF_E_ARG, "mvnerf_project_texels_bf16: B=%d V=%d H=%d W=%d", B, V, H, W);
-    if ((long)B * V * H * W >= (1L << 31)) return fail(MVNERF_E_SHAPE, "mvnerf_project_texels_bf16: B*V*H*W too large for int32 indices");
-    if (!aligned16(features) || !aligned16(packed16) || !aligned16(texel_table))
-        return fail(MVNERF_E_ALIGN, "mvnerf_project_texels_bf16: features, packed16, texel_table must be 16-byte aligned");
+    if (const int rc = texels_check("mvnerf_project_texels_bf16", features, packed16, packed16_b, B, V, H, W, texel_table, texel_table_b)) return rc;
     return hip_status(mvnerf::launch_project_texels_bf16(features, packed16, packed16_b, (long)B * V * H * W, texel_table, texel_table_b,
                                                          static_cast<hipStream_t>(stream)),
                       "mvnerf_project_texels_bf16");
 }
 
-}  // extern "C"
-
-static int field_eval_bf16_impl(const char* who, bool maps_bf16, const float* rays_o, const float* rays_d, const float* z, const float* images,
-                           const float* features, const float* texel_table, const float* intrinsics, const float* extrinsics_inv,
-                           const float* packed_net, const void* packed16, int B, int V, int R, int S, int H, int W,
-                           float* rgbs, int32_t* tap_idx, float* embedding, float* acts_fused, void* workspace,
-                           mvnerf_stream_t stream) {
-    if (acts_fused && !aligned16(acts_fused)) return fail(MVNERF_E_ALIGN, "%s: acts_fused must be 16-byte aligned", who);
-    if (texel_table && !aligned16(texel_table)) return fail(MVNERF_E_ALIGN, "%s: texel_table must be 16-byte aligned", who);
-    if (!rays_o || !rays_d || !z || !images || !features || !intrinsics || !extrinsics_inv || !packed_net || !packed16 || !rgbs || !workspace)
-        return fail(MVNERF_E_ARG, "%s: null pointer", who);
-    if (B <= 0 || V <= 0 || R <= 0 || S <= 0) return fail(MVNERF_E_ARG, "%s: B=%d V=%d R=%d S=%d", who, B, V, R, S);
-    if (H < 2 || W < 2) return fail(MVNERF_E_SHAPE, "%s: source image %dx%d, need H,W >= 2", who, H, W);
-    const long total = (long)B * R * S;
-    if (total >= (1L << 31) || (long)B * V * H * W >= (1L << 31)) return fail(MVNERF_E_SHAPE, "%s: sizes too large for int32 indices", who);
-    if (!aligned16(features) || !aligned16(packed_net) || !aligned16(packed16) || !aligned16(rgbs) || (tap_idx && !aligned16(tap_idx)) ||
-        (embedding && !aligned16(embedding)) || !aligned16(workspace))
-        return fail(MVNERF_E_ALIGN, "%s: features, packed nets, rgbs, tap_idx, embedding, workspace must be 16-byte aligned", who);
-    mvnerf::FieldParams p = {};
-    p.rays_o = rays_o; p.rays_d = rays_d; p.z = z; p.images = images; p.features = features;
-    p.k4 = intrinsics; p.einv = extrinsics_inv; p.net = packed_net; p.rgbs = rgbs; p.tap_idx = tap_idx; p.embedding = embedding;
-    p.acts_fused = acts_fused;
-    p.texel_table = texel_table;
-    p.dir_bias = static_cast<float*>(workspace);
-    p.B = B; p.V = V; p.R = R; p.S = S; p.H = H; p.W = W;
-    p.total = total;
-    p.n_tiles = (total + 31) / 32;
-    return hip_status(mvnerf::launch_field_eval_bf16(p, packed16, static_cast<hipStream_t>(stream), maps_bf16), who);
-}
-
-extern "C" {
-
 int mvnerf_project_texels_bf16maps(const void* features_bf16, const void* packed16, const void* packed16_b, int B, int V, int H, int W,
                                    float* texel_table, float* texel_table_b, mvnerf_stream_t stream) {
-    if (!features_bf16 || !packed16 || !texel_table) return fail(MVNERF_E_ARG, "mvnerf_project_texels_bf16maps: null pointer");
-    if ((packed16_b == nullptr) != (texel_table_b == nullptr))
-        return fail(MVNERF_E_ARG, "mvnerf_project_texels_bf16maps: the second net and the second table go together");
-    if ((packed16_b && !aligned16(packed16_b)) || (texel_table_b && !aligned16(texel_table_b)))
-        return fail(MVNERF_E_ALIGN, "mvnerf_project_texels_bf16maps: packed16_b, texel_table_b must be 16-byte aligned");
-    if (B <= 0 || V <= 0 || H < 2 || W < 2) return fail(MVNERF_E_ARG, "mvnerf_project_texels_bf16maps: B=%d V=%d H=%d W=%d", B, V, H, W);
-    if ((long)B * V * H * W >= (1L << 31)) return fail(MVNERF_E_SHAPE, "mvnerf_project_texels_bf16maps: B*V*H*W too large for int32 indices");
-    if (!aligned16(features_bf16) || !aligned16(packed16) || !aligned16(texel_table))
-        return fail(MVNERF_E_ALIGN, "mvnerf_project_texels_bf16maps: features_bf16, packed16, texel_table must be 16-byte aligned");
+    if (const int rc = texels_check("mvnerf_project_texels_bf16maps", features_bf16, packed16, packed16_b, B, V, H, W, texel_table, texel_table_b))
+        return rc;
     return hip_status(mvnerf::launch_project_texels_bf16maps(features_bf16, packed16, packed16_b, (long)B * V * H * W, texel_table, texel_table_b,
                                                              static_cast<hipStream_t>(stream)),
                       "mvnerf_project_texels_bf16maps");
@@ -249,8 +240,9 @@ int mvnerf_field_eval_bf16(const float* rays_o, const float* rays_d, const float
                            const float* packed_net, const void* packed16, int B, int V, int R, int S, int H, int W,
                            float* rgbs, int32_t* tap_idx, float* embedding, float* acts_fused, void* workspace,
                            mvnerf_stream_t stream) {
-    return field_eval_bf16_impl("mvnerf_field_eval_bf16", false, rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv,
-                                packed_net, packed16, B, V, R, S, H, W, rgbs, tap_idx, embedding, acts_fused, workspace, stream);
+    const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, packed16, B, V, R, S, H, W,
+                         rgbs, tap_idx, nullptr, embedding, nullptr, acts_fused, nullptr, workspace};
+    return field_pass("mvnerf_field_eval_bf16", a, {kFieldBf16, false, MVNERF_E_SHAPE}, stream);
 }
 
 int mvnerf_field_eval_bf16maps(const float* rays_o, const float* rays_d, const float* z, const float* images,
@@ -258,9 +250,9 @@ int mvnerf_field_eval_bf16maps(const float* rays_o, const float* rays_d, const f
                                const float* packed_net, const void* packed16, int B, int V, int R, int S, int H, int W,
                                float* rgbs, int32_t* tap_idx, float* embedding, float* acts_fused, void* workspace,
                                mvnerf_stream_t stream) {
-    return field_eval_bf16_impl("mvnerf_field_eval_bf16maps", true, rays_o, rays_d, z, images, static_cast<const float*>(features_bf16), texel_table,
-                                intrinsics, extrinsics_inv, packed_net, packed16, B, V, R, S, H, W, rgbs, tap_idx, embedding, acts_fused,
-                                workspace, stream);
+    const FieldArgs a = {rays_o, rays_d, z, images, static_cast<const float*>(features_bf16), texel_table, intrinsics, extrinsics_inv, packed_net,
+                         packed16, B, V, R, S, H, W, rgbs, tap_idx, nullptr, embedding, nullptr, acts_fused, nullptr, workspace};
+    return field_pass("mvnerf_field_eval_bf16maps", a, {kFieldBf16Maps, false, MVNERF_E_SHAPE}, stream);
 }
 
 size_t mvnerf_packed_net_split_bytes(void) { return mvnerf::packed_net_split_bytes(); }
@@ -276,27 +268,9 @@ int mvnerf_field_eval_split(const float* rays_o, const float* rays_d, const floa
                             const float* packed_net, const void* packed_split, int B, int V, int R, int S, int H, int W,
                             float* rgbs, int32_t* tap_idx, float* pix, float* embedding, float* acts_per_view, float* acts_fused,
                             void* workspace, mvnerf_stream_t stream) {
-    if (!rays_o || !rays_d || !z || !images || !features || !intrinsics || !extrinsics_inv || !packed_net || !packed_split || !rgbs || !workspace)
-        return fail(MVNERF_E_ARG, "mvnerf_field_eval_split: null pointer");
-    if (B <= 0 || V <= 0 || R <= 0 || S <= 0) return fail(MVNERF_E_ARG, "mvnerf_field_eval_split: B=%d V=%d R=%d S=%d", B, V, R, S);
-    if (H < 2 || W < 2) return fail(MVNERF_E_SHAPE, "mvnerf_field_eval_split: source image %dx%d, need H,W >= 2 (bilinear taps)", H, W);
-    const long total = (long)B * R * S;
-    if (total >= (1L << 31) || (long)B * V * H * W >= (1L << 31))
-        return fail(MVNERF_E_SHAPE, "mvnerf_field_eval_split: B*R*S=%ld or B*V*H*W too large for int32 indices", total);
-    if (!aligned16(features) || !aligned16(packed_net) || !aligned16(packed_split) || !aligned16(rgbs) || !aligned16(workspace) ||
-        (texel_table && !aligned16(texel_table)) || (tap_idx && !aligned16(tap_idx)) || (embedding && !aligned16(embedding)) ||
-        (acts_per_view && !aligned16(acts_per_view)) || (acts_fused && !aligned16(acts_fused)))
-        return fail(MVNERF_E_ALIGN, "mvnerf_field_eval_split: features, packed nets, texel_table, rgbs, tap_idx, embedding, acts, workspace must be 16-byte aligned");
-    mvnerf::FieldParams p = {};
-    p.rays_o = rays_o; p.rays_d = rays_d; p.z = z; p.images = images; p.features = features;
-    p.k4 = intrinsics; p.einv = extrinsics_inv; p.net = packed_net; p.rgbs = rgbs; p.tap_idx = tap_idx; p.pix = pix;
-    p.embedding = embedding; p.acts_view = acts_per_view; p.acts_fused = acts_fused;
-    p.texel_table = texel_table;
-    p.dir_bias = static_cast<float*>(workspace);
-    p.B = B; p.V = V; p.R = R; p.S = S; p.H = H; p.W = W;
-    p.total = total;
-    p.n_tiles = (total + 31) / 32;
-    return hip_status(mvnerf::launch_field_eval_split(p, packed_split, static_cast<hipStream_t>(stream)), "mvnerf_field_eval_split");
+    const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, packed_split, B, V, R, S, H, W,
+                         rgbs, tap_idx, pix, embedding, acts_per_view, acts_fused, nullptr, workspace};
+    return field_pass("mvnerf_field_eval_split", a, {kFieldSplit, false, MVNERF_E_SHAPE}, stream);
 }
 
 int mvnerf_composite(const float* z, const float* rgbs, int n_rays, int S, float* rgb, float* depth, float* weights,
@@ -442,60 +416,18 @@ int mvnerf_field_eval_stash(const float* rays_o, const float* rays_d, const floa
                             const float* features, const float* texel_table, const float* intrinsics,
                             const float* extrinsics_inv, const float* packed_net, int B, int V, int R, int S, int H, int W,
                             float* rgbs, float* stash, void* workspace, mvnerf_stream_t stream) {
-    if (texel_table && !aligned16(texel_table)) return fail(MVNERF_E_ALIGN, "mvnerf_field_eval_stash: texel_table must be 16-byte aligned");
-    if (!rays_o || !rays_d || !z || !images || !features || !intrinsics || !extrinsics_inv || !packed_net || !rgbs || !stash || !workspace)
-        return fail(MVNERF_E_ARG, "mvnerf_field_eval_stash: null pointer");
-    if (B <= 0 || V <= 0 || R <= 0 || S <= 0 || H < 2 || W < 2) return fail(MVNERF_E_ARG, "mvnerf_field_eval_stash: B=%d V=%d R=%d S=%d H=%d W=%d", B, V, R, S, H, W);
-    if (V > 1 && ((long)R * S) % 32 != 0) return fail(MVNERF_E_SHAPE, "mvnerf_field_eval_stash: R*S=%ld must be a multiple of 32 when V > 1", (long)R * S);
-    const long total = (long)B * R * S;
-    if (total >= (1L << 31)) return fail(MVNERF_E_SHAPE, "mvnerf_field_eval_stash: B*R*S too large");
-    if ((long)V * ((total + 31) / 32) >= (1L << 18))      // stash slots are addressed with 32-bit byte offsets (16 KiB per tile)
-        return fail(MVNERF_E_SHAPE, "mvnerf_field_eval_stash: V*B*R*S/32 = %ld tiles per stash slot, at most 262143", (long)V * ((total + 31) / 32));
-    if (!aligned16(features) || !aligned16(packed_net) || !aligned16(rgbs) || !aligned16(stash) || !aligned16(workspace))
-        return fail(MVNERF_E_ALIGN, "mvnerf_field_eval_stash: features, packed_net, rgbs, stash, workspace must be 16-byte aligned");
-    mvnerf::FieldParams p = {};
-    p.rays_o = rays_o; p.rays_d = rays_d; p.z = z; p.images = images; p.features = features;
-    p.k4 = intrinsics; p.einv = extrinsics_inv; p.net = packed_net; p.rgbs = rgbs;
-    p.texel_table = texel_table;
-    p.dir_bias = static_cast<float*>(workspace);
-    p.B = B; p.V = V; p.R = R; p.S = S; p.H = H; p.W = W;
-    p.total = total;
-    p.n_tiles = (total + 31) / 32;
-    p.stash = stash;
-    p.stash_stride = (long)V * p.n_tiles * 4096;
-    p.stash_fused = stash + 7 * p.stash_stride;
-    p.stash_fused_stride = p.n_tiles * 4096;
-    return hip_status(mvnerf::launch_field_eval(p, static_cast<hipStream_t>(stream)), "mvnerf_field_eval_stash");
+    const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, nullptr, B, V, R, S, H, W,
+                         rgbs, nullptr, nullptr, nullptr, nullptr, nullptr, stash, workspace};
+    return field_pass("mvnerf_field_eval_stash", a, {kFieldFp32, true, MVNERF_E_ARG}, stream);
 }
 
 int mvnerf_field_eval_stash_split(const float* rays_o, const float* rays_d, const float* z, const float* images,
                                   const float* features, const float* texel_table, const float* intrinsics,
                                   const float* extrinsics_inv, const float* packed_net, const void* packed_split, int B, int V, int R,
                                   int S, int H, int W, float* rgbs, float* stash, void* workspace, mvnerf_stream_t stream) {
-    if (texel_table && !aligned16(texel_table)) return fail(MVNERF_E_ALIGN, "mvnerf_field_eval_stash_split: texel_table must be 16-byte aligned");
-    if (!rays_o || !rays_d || !z || !images || !features || !intrinsics || !extrinsics_inv || !packed_net || !packed_split || !rgbs || !stash || !workspace)
-        return fail(MVNERF_E_ARG, "mvnerf_field_eval_stash_split: null pointer");
-    if (B <= 0 || V <= 0 || R <= 0 || S <= 0 || H < 2 || W < 2) return fail(MVNERF_E_ARG, "mvnerf_field_eval_stash_split: B=%d V=%d R=%d S=%d H=%d W=%d", B, V, R, S, H, W);
-    if (V > 1 && ((long)R * S) % 32 != 0) return fail(MVNERF_E_SHAPE, "mvnerf_field_eval_stash_split: R*S=%ld must be a multiple of 32 when V > 1", (long)R * S);
-    const long total = (long)B * R * S;
-    if (total >= (1L << 31)) return fail(MVNERF_E_SHAPE, "mvnerf_field_eval_stash_split: B*R*S too large");
-    if ((long)V * ((total + 31) / 32) >= (1L << 18))      // stash slots are addressed with 32-bit byte offsets (16 KiB per tile)
-        return fail(MVNERF_E_SHAPE, "mvnerf_field_eval_stash_split: V*B*R*S/32 = %ld tiles per stash slot, at most 262143", (long)V * ((total + 31) / 32));
-    if (!aligned16(features) || !aligned16(packed_net) || !aligned16(packed_split) || !aligned16(rgbs) || !aligned16(stash) || !aligned16(workspace))
-        return fail(MVNERF_E_ALIGN, "mvnerf_field_eval_stash_split: features, packed nets, rgbs, stash, workspace must be 16-byte aligned");
-    mvnerf::FieldParams p = {};
-    p.rays_o = rays_o; p.rays_d = rays_d; p.z = z; p.images = images; p.features = features;
-    p.k4 = intrinsics; p.einv = extrinsics_inv; p.net = packed_net; p.rgbs = rgbs;
-    p.texel_table = texel_table;
-    p.dir_bias = static_cast<float*>(workspace);
-    p.B = B; p.V = V; p.R = R; p.S = S; p.H = H; p.W = W;
-    p.total = total;
-    p.n_tiles = (total + 31) / 32;
-    p.stash = stash;
-    p.stash_stride = (long)V * p.n_tiles * 4096;
-    p.stash_fused = stash + 7 * p.stash_stride;
-    p.stash_fused_stride = p.n_tiles * 4096;
-    return hip_status(mvnerf::launch_field_eval_split(p, packed_split, static_cast<hipStream_t>(stream)), "mvnerf_field_eval_stash_split");
+    const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, packed_split, B, V, R, S, H, W,
+                         rgbs, nullptr, nullptr, nullptr, nullptr, nullptr, stash, workspace};
+    return field_pass("mvnerf_field_eval_stash_split", a, {kFieldSplit, true, MVNERF_E_ARG}, stream);
 }
 
 int mvnerf_pack_bwd_streams(const float* net_keras, float* bwd_streams, mvnerf_stream_t stream) {
@@ -817,19 +749,20 @@ size_t mvnerf_render_workspace_bytes(int B, int V, int R, int S) {
     return carve(nullptr, (long)B * R, V, S).bytes;
 }
 
-int mvnerf_render_fwd(const float* rays_o, const float* rays_d, const float* images, const float* features,
-                      const float* intrinsics, const float* extrinsics_inv, const float* packed_coarse,
-                      const float* packed_fine, const float* u_coarse, const float* u_fine, int B, int V, int R,
-                      int S, int H, int W, double near_, double far_, int q7_mode, float* rgb, float* depth,
-                      float* fine_rgb, float* fine_depth, void* workspace, float* texel_tables, int tables_ready,
-                      mvnerf_stream_t stream) {
-    if (!u_coarse || !u_fine || !rgb || !depth || !fine_rgb || !fine_depth || !workspace || !packed_fine)
-        return fail(MVNERF_E_ARG, "mvnerf_render_fwd: null pointer");
-    if (S != 64) return fail(MVNERF_E_SHAPE, "mvnerf_render_fwd: S=%d, only the reference's n_samples=64 is built", S);
-    if (B <= 0 || R <= 0) return fail(MVNERF_E_ARG, "mvnerf_render_fwd: B=%d R=%d", B, R);
-    if (!aligned16(workspace)) return fail(MVNERF_E_ALIGN, "mvnerf_render_fwd: workspace must be 16-byte aligned");
+// mvnerf_render_fwd and mvnerf_render_fwd_split: the same two-pass composition; `split` says which field kernel runs the passes
+static int render_fwd(const char* who, bool split, const float* rays_o, const float* rays_d, const float* images, const float* features,
+                      const float* intrinsics, const float* extrinsics_inv, const float* packed_coarse, const float* packed_fine,
+                      const void* split_coarse, const void* split_fine, const float* u_coarse, const float* u_fine, int B, int V, int R,
+                      int S, int H, int W, double near_, double far_, int q7_mode, float* rgb, float* depth, float* fine_rgb,
+                      float* fine_depth, void* workspace, float* texel_tables, int tables_ready, mvnerf_stream_t stream) {
+    if (!u_coarse || !u_fine || !rgb || !depth || !fine_rgb || !fine_depth || !workspace || !packed_fine ||
+        (split && (!split_coarse || !split_fine)))
+        return fail(MVNERF_E_ARG, "%s: null pointer", who);
+    if (S != 64) return fail(MVNERF_E_SHAPE, "%s: S=%d, only the reference's n_samples=64 is built", who, S);
+    if (B <= 0 || R <= 0) return fail(MVNERF_E_ARG, "%s: B=%d R=%d", who, B, R);
+    if (!aligned16(workspace)) return fail(MVNERF_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
     const long n_rays = (long)B * R;
-    if (n_rays * 2 * S >= (1L << 31)) return fail(MVNERF_E_SHAPE, "mvnerf_render_fwd: B*R*2S too large");
+    if (n_rays * 2 * S >= (1L << 31)) return fail(MVNERF_E_SHAPE, "%s: B*R*2S too large", who);
     const Workspace w = carve(workspace, n_rays, V, S);
     int rc;
     const float *table_c = nullptr, *table_f = nullptr;
@@ -841,17 +774,30 @@ int mvnerf_render_fwd(const float* rays_o, const float* rays_d, const float* ima
         table_c = texel_tables;
         table_f = tf;
     }
+    const char* field_who = split ? "mvnerf_field_eval_split" : "mvnerf_field_eval";
+    const FieldKind kind = {split ? kFieldSplit : kFieldFp32, false, MVNERF_E_SHAPE};
+    const FieldArgs coarse = {rays_o, rays_d, w.z, images, features, table_c, intrinsics, extrinsics_inv, packed_coarse, split_coarse, B, V, R, S,
+                              H, W, w.rgbs_c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, w.dir_bias};
+    const FieldArgs fine = {rays_o, rays_d, w.z_all, images, features, table_f, intrinsics, extrinsics_inv, packed_fine, split_fine, B, V, R,
+                            2 * S, H, W, w.rgbs_f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, w.dir_bias};
     if ((rc = mvnerf_stratified_depths(u_coarse, (int)n_rays, S, near_, far_, w.z, stream))) return rc;
-    if ((rc = field_eval_impl(rays_o, rays_d, w.z, images, features, table_c, intrinsics, extrinsics_inv, packed_coarse, B, V,
-                              R, S, H, W, w.rgbs_c, nullptr, nullptr, nullptr, nullptr, nullptr, w.dir_bias, stream)))
-        return rc;
+    if ((rc = field_pass(field_who, coarse, kind, stream))) return rc;
     if ((rc = mvnerf_composite(w.z, w.rgbs_c, (int)n_rays, S, rgb, depth, w.weights, stream))) return rc;
     if ((rc = mvnerf_resample(w.z, w.weights, u_fine, (int)n_rays, S, q7_mode, w.z_all, nullptr, nullptr, nullptr, nullptr, stream)))
         return rc;
-    if ((rc = field_eval_impl(rays_o, rays_d, w.z_all, images, features, table_f, intrinsics, extrinsics_inv, packed_fine, B,
-                              V, R, 2 * S, H, W, w.rgbs_f, nullptr, nullptr, nullptr, nullptr, nullptr, w.dir_bias, stream)))
-        return rc;
+    if ((rc = field_pass(field_who, fine, kind, stream))) return rc;
     return mvnerf_composite(w.z_all, w.rgbs_f, (int)n_rays, 2 * S, fine_rgb, fine_depth, nullptr, stream);
+}
+
+int mvnerf_render_fwd(const float* rays_o, const float* rays_d, const float* images, const float* features,
+                      const float* intrinsics, const float* extrinsics_inv, const float* packed_coarse,
+                      const float* packed_fine, const float* u_coarse, const float* u_fine, int B, int V, int R,
+                      int S, int H, int W, double near_, double far_, int q7_mode, float* rgb, float* depth,
+                      float* fine_rgb, float* fine_depth, void* workspace, float* texel_tables, int tables_ready,
+                      mvnerf_stream_t stream) {
+    return render_fwd("mvnerf_render_fwd", false, rays_o, rays_d, images, features, intrinsics, extrinsics_inv, packed_coarse, packed_fine,
+                      nullptr, nullptr, u_coarse, u_fine, B, V, R, S, H, W, near_, far_, q7_mode, rgb, depth, fine_rgb, fine_depth, workspace,
+                      texel_tables, tables_ready, stream);
 }
 
 int mvnerf_render_fwd_split(const float* rays_o, const float* rays_d, const float* images, const float* features,
@@ -860,35 +806,9 @@ int mvnerf_render_fwd_split(const float* rays_o, const float* rays_d, const floa
                             const float* u_fine, int B, int V, int R, int S, int H, int W, double near_, double far_, int q7_mode,
                             float* rgb, float* depth, float* fine_rgb, float* fine_depth, void* workspace, float* texel_tables,
                             int tables_ready, mvnerf_stream_t stream) {
-    if (!u_coarse || !u_fine || !rgb || !depth || !fine_rgb || !fine_depth || !workspace || !packed_fine || !split_coarse || !split_fine)
-        return fail(MVNERF_E_ARG, "mvnerf_render_fwd_split: null pointer");
-    if (S != 64) return fail(MVNERF_E_SHAPE, "mvnerf_render_fwd_split: S=%d, only the reference's n_samples=64 is built", S);
-    if (B <= 0 || R <= 0) return fail(MVNERF_E_ARG, "mvnerf_render_fwd_split: B=%d R=%d", B, R);
-    if (!aligned16(workspace)) return fail(MVNERF_E_ALIGN, "mvnerf_render_fwd_split: workspace must be 16-byte aligned");
-    const long n_rays = (long)B * R;
-    if (n_rays * 2 * S >= (1L << 31)) return fail(MVNERF_E_SHAPE, "mvnerf_render_fwd_split: B*R*2S too large");
-    const Workspace w = carve(workspace, n_rays, V, S);
-    int rc;
-    const float *table_c = nullptr, *table_f = nullptr;
-    if (texel_tables) {                                       // [coarse net | fine net], mvnerf_texel_table_bytes each
-        float* tf = texel_tables + mvnerf_texel_table_bytes(B, V, H, W) / sizeof(float);
-        if (!tables_ready) {
-            if ((rc = mvnerf_project_texels2(features, packed_coarse, packed_fine, B, V, H, W, texel_tables, tf, stream))) return rc;
-        }
-        table_c = texel_tables;
-        table_f = tf;
-    }
-    if ((rc = mvnerf_stratified_depths(u_coarse, (int)n_rays, S, near_, far_, w.z, stream))) return rc;
-    if ((rc = mvnerf_field_eval_split(rays_o, rays_d, w.z, images, features, table_c, intrinsics, extrinsics_inv, packed_coarse, split_coarse,
-                                      B, V, R, S, H, W, w.rgbs_c, nullptr, nullptr, nullptr, nullptr, nullptr, w.dir_bias, stream)))
-        return rc;
-    if ((rc = mvnerf_composite(w.z, w.rgbs_c, (int)n_rays, S, rgb, depth, w.weights, stream))) return rc;
-    if ((rc = mvnerf_resample(w.z, w.weights, u_fine, (int)n_rays, S, q7_mode, w.z_all, nullptr, nullptr, nullptr, nullptr, stream)))
-        return rc;
-    if ((rc = mvnerf_field_eval_split(rays_o, rays_d, w.z_all, images, features, table_f, intrinsics, extrinsics_inv, packed_fine, split_fine,
-                                      B, V, R, 2 * S, H, W, w.rgbs_f, nullptr, nullptr, nullptr, nullptr, nullptr, w.dir_bias, stream)))
-        return rc;
-    return mvnerf_composite(w.z_all, w.rgbs_f, (int)n_rays, 2 * S, fine_rgb, fine_depth, nullptr, stream);
+    return render_fwd("mvnerf_render_fwd_split", true, rays_o, rays_d, images, features, intrinsics, extrinsics_inv, packed_coarse,
+                      packed_fine, split_coarse, split_fine, u_coarse, u_fine, B, V, R, S, H, W, near_, far_, q7_mode, rgb, depth, fine_rgb,
+                      fine_depth, workspace, texel_tables, tables_ready, stream);
 }
 
 }  // extern "C"

@@ -9,10 +9,9 @@
 // (half a coarse ray, a quarter of a fine ray), waves are independent (no workgroup barrier).
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
 #include "mvnerf_field_common.h"
 #include "mvnerf_kernels.h"
+#include "mvnerf_launch.h"
 #include "mvnerf_math.h"
 #include "mvnerf_pack.h"
 
@@ -436,11 +435,6 @@ hipError_t launch_pack_net(const float* net_keras, float* packed, hipStream_t st
     return hipGetLastError();
 }
 
-namespace {
-bool g_attr_set[16] = {};            // per device: the kernels' LDS limits are raised
-std::mutex g_dev_mutex;
-}  // namespace
-
 hipError_t launch_dir_bias(const FieldParams& p, hipStream_t stream) {
     const long rows = (long)p.B * p.V * p.R;
     hipLaunchKernelGGL(dir_bias_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, p);
@@ -448,29 +442,13 @@ hipError_t launch_dir_bias(const FieldParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_field_eval(const FieldParams& p, hipStream_t stream) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static DeviceSetup setup;
+    const int lds_sv = kWaves * kTile * kStageRow * 4, lds_mv = 4 * kTile * kStageRow * 4;
+    hipError_t e = device_setup(setup, {{&field_eval_kernel<false, false, false>, lds_sv}, {&field_eval_kernel<false, false, true>, lds_sv},
+                                        {&field_eval_kernel<false, true, false>, lds_sv}, {&field_eval_kernel<false, true, true>, lds_sv},
+                                        {&field_eval_kernel<true, false, false>, lds_mv}, {&field_eval_kernel<true, false, true>, lds_mv},
+                                        {&field_eval_kernel<true, true, false>, lds_mv}, {&field_eval_kernel<true, true, true>, lds_mv}});
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16) return hipErrorInvalidDevice;
-    {
-        std::lock_guard<std::mutex> lock(g_dev_mutex);
-        if (!g_attr_set[dev]) {
-            const int lds_sv = kWaves * kTile * kStageRow * 4, lds_mv = 4 * kTile * kStageRow * 4;
-            const struct { const void* fn; int bytes; } kernels[] = {
-                {reinterpret_cast<const void*>(&field_eval_kernel<false, false, false>), lds_sv},
-                {reinterpret_cast<const void*>(&field_eval_kernel<false, false, true>), lds_sv},
-                {reinterpret_cast<const void*>(&field_eval_kernel<false, true, false>), lds_sv},
-                {reinterpret_cast<const void*>(&field_eval_kernel<false, true, true>), lds_sv},
-                {reinterpret_cast<const void*>(&field_eval_kernel<true, false, false>), lds_mv},
-                {reinterpret_cast<const void*>(&field_eval_kernel<true, false, true>), lds_mv},
-                {reinterpret_cast<const void*>(&field_eval_kernel<true, true, false>), lds_mv},
-                {reinterpret_cast<const void*>(&field_eval_kernel<true, true, true>), lds_mv},
-            };
-            for (const auto& k : kernels)
-                if ((e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes)) != hipSuccess) return e;
-            g_attr_set[dev] = true;
-        }
-    }
     if ((e = launch_dir_bias(p, stream)) != hipSuccess) return e;
     const int waves = p.V > 1 ? 4 : kWaves;
     const unsigned wgs = (unsigned)((p.n_tiles + waves - 1) / waves);

@@ -18,9 +18,9 @@
 
 #include <cstdlib>
 
-#include <mutex>
 
 #include "mvnerf_kernels.h"
+#include "mvnerf_launch.h"
 #include "mvnerf_math.h"
 #include "mvnerf_mfma.h"
 
@@ -629,34 +629,16 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
 hipError_t launch_field_eval_bf16(const FieldParams& p, const void* packed16, hipStream_t stream, bool maps_bf16) {
     if (bf16x_enabled() && field_eval_bf16x_supports(p))
         return launch_field_eval_bf16x(p, static_cast<const unsigned char*>(packed16) + (size_t)kW16Chunks * 1024, stream);
-    static std::mutex mtx;
-    static bool attr_done[16] = {};
-    static int cus[16] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16) return hipErrorInvalidDevice;
+    static DeviceSetup setup;
     const int lds_bytes = kRing * kSegF4 * 16 + kWgWaves * 32 * kStage16Row + (kPackBr + 8 - kPackB0) * 4;
-    {
-        std::lock_guard<std::mutex> lock(mtx);
-        if (!attr_done[dev]) {
-            hipDeviceProp_t prop;
-            if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-            cus[dev] = prop.multiProcessorCount;
-            const void* fns[6] = {reinterpret_cast<const void*>(&field_eval_bf16_kernel<false, false, false>),
-                                  reinterpret_cast<const void*>(&field_eval_bf16_kernel<false, true, false>),
-                                  reinterpret_cast<const void*>(&field_eval_bf16_kernel<true, false, false>),
-                                  reinterpret_cast<const void*>(&field_eval_bf16_kernel<true, true, false>),
-                                  reinterpret_cast<const void*>(&field_eval_bf16_kernel<false, false, true>),
-                                  reinterpret_cast<const void*>(&field_eval_bf16_kernel<true, false, true>)};
-            for (const void* fn : fns)
-                if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess) return e;
-            attr_done[dev] = true;
-        }
-    }
+    int cus = 0;
+    hipError_t e = device_setup(setup, {{&field_eval_bf16_kernel<false, false, false>, lds_bytes}, {&field_eval_bf16_kernel<false, true, false>, lds_bytes},
+                                        {&field_eval_bf16_kernel<true, false, false>, lds_bytes}, {&field_eval_bf16_kernel<true, true, false>, lds_bytes},
+                                        {&field_eval_bf16_kernel<false, false, true>, lds_bytes}, {&field_eval_bf16_kernel<true, false, true>, lds_bytes}}, &cus);
+    if (e != hipSuccess) return e;
     if ((e = launch_dir_bias(p, stream)) != hipSuccess) return e;
     const long n_groups = (p.n_tiles + kWgWaves - 1) / kWgWaves;
-    const long resident = (long)cus[dev] * (8 / kWgWaves);                 // persistent: as many workgroups as fit at once
+    const long resident = (long)cus * (8 / kWgWaves);                 // persistent: as many workgroups as fit at once
     const unsigned wgs = (unsigned)(n_groups < resident ? n_groups : resident);
     const f32x4* w16 = static_cast<const f32x4*>(packed16);
 #define MV16_GO(MV, PROJ, F16) hipLaunchKernelGGL((field_eval_bf16_kernel<MV, PROJ, F16>), dim3(wgs), dim3(64 * kWgWaves), lds_bytes, stream, p, w16)

@@ -13,9 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
-#include <mutex>
 
 #include "mvnerf_kernels.h"
+#include "mvnerf_launch.h"
 #include "mvnerf_math.h"
 #include "mvnerf_mfma.h"
 
@@ -575,33 +575,16 @@ bool field_eval_bf16x_supports(const FieldParams& p) {
 }
 
 hipError_t launch_field_eval_bf16x(const FieldParams& p, const void* packed16x, hipStream_t stream) {
-    static std::mutex mtx;
-    static bool attr_done[16] = {};
-    static int cus[16] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16) return hipErrorInvalidDevice;
+    static DeviceSetup setup;
     if (!field_eval_bf16x_supports(p)) return hipErrorInvalidValue;
     const int lds_bytes = kXSlots * kXSlotF4 * 16 + 8 * 32 * kXStageRowBytes + (kPackBr + 8 - kPackB0) * 4 + kXMaxPositions * 4 + 512 * 4;
-    {
-        std::lock_guard<std::mutex> lock(mtx);
-        if (!attr_done[dev]) {
-            hipDeviceProp_t prop;
-            if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-            cus[dev] = prop.multiProcessorCount;
-            const void* fns[4] = {reinterpret_cast<const void*>(&field_eval_bf16x_kernel<false, false>),
-                                  reinterpret_cast<const void*>(&field_eval_bf16x_kernel<false, true>),
-                                  reinterpret_cast<const void*>(&field_eval_bf16x_kernel<true, false>),
-                                  reinterpret_cast<const void*>(&field_eval_bf16x_kernel<true, true>)};
-            for (const void* fn : fns)
-                if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess) return e;
-            attr_done[dev] = true;
-        }
-    }
+    int cus = 0;
+    hipError_t e = device_setup(setup, {{&field_eval_bf16x_kernel<false, false>, lds_bytes}, {&field_eval_bf16x_kernel<false, true>, lds_bytes},
+                                        {&field_eval_bf16x_kernel<true, false>, lds_bytes}, {&field_eval_bf16x_kernel<true, true>, lds_bytes}}, &cus);
+    if (e != hipSuccess) return e;
     if ((e = launch_dir_bias(p, stream)) != hipSuccess) return e;
     const long n_groups = (p.n_tiles + 7) / 8;
-    const long resident = (long)cus[dev];
+    const long resident = (long)cus;
     const unsigned wgs = (unsigned)(n_groups < resident ? n_groups : resident);
     const f32x4* w = static_cast<const f32x4*>(packed16x);
     const bool aux = p.tap_idx || p.embedding || p.acts_fused;

@@ -18,9 +18,9 @@
 
 #include <cstdlib>
 #include <atomic>
-#include <mutex>
 
 #include "mvnerf_kernels.h"
+#include "mvnerf_launch.h"
 #include "mvnerf_math.h"
 #include "mvnerf_mfma.h"
 
@@ -656,39 +656,20 @@ hipError_t launch_field_eval_split(const FieldParams& p, const void* packed_spli
     const char* base16 = static_cast<const char*>(packed_split) + (size_t)kSpChunks * 1024;
     if (which == kSplit16F16 && field_eval_split16h_supports(p)) return launch_field_eval_split16h(p, base16 + packed_net_split16_bytes(), stream);
     if (which != kSplit32 && field_eval_split16_supports(p)) return launch_field_eval_split16(p, base16, stream);
-    static std::mutex mtx;
-    static bool attr_done[16] = {};
-    static int cus[16] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16) return hipErrorInvalidDevice;
+    static DeviceSetup setup;
     const int n_pos = ((p.texel_table ? 4 : kSpL0Steps) + kHiddenUnits) * p.V + kHiddenUnits + 2;
     if (n_pos > kMaxPositions) return hipErrorInvalidValue;                  // V <= 14 (direct) / 18 (texel table)
     const int lds_bytes = kRing * kSlotF4 * 16 + kWgWaves * 32 * kStageRowBytes + (kPackBr + 8 - kPackB0) * 4 + kMaxPositions * 4;
-    {
-        std::lock_guard<std::mutex> lock(mtx);
-        if (!attr_done[dev]) {
-            hipDeviceProp_t prop;
-            if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-            cus[dev] = prop.multiProcessorCount;
-            const void* fns[8] = {reinterpret_cast<const void*>(&field_eval_split_kernel<false, false, false>),
-                                  reinterpret_cast<const void*>(&field_eval_split_kernel<false, true, false>),
-                                  reinterpret_cast<const void*>(&field_eval_split_kernel<true, false, false>),
-                                  reinterpret_cast<const void*>(&field_eval_split_kernel<true, true, false>),
-                                  reinterpret_cast<const void*>(&field_eval_split_kernel<false, false, true>),
-                                  reinterpret_cast<const void*>(&field_eval_split_kernel<false, true, true>),
-                                  reinterpret_cast<const void*>(&field_eval_split_kernel<true, false, true>),
-                                  reinterpret_cast<const void*>(&field_eval_split_kernel<true, true, true>)};
-            for (const void* fn : fns)
-                if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess) return e;
-            attr_done[dev] = true;
-        }
-    }
+    int cus = 0;
+    hipError_t e = device_setup(setup, {{&field_eval_split_kernel<false, false, false>, lds_bytes}, {&field_eval_split_kernel<false, true, false>, lds_bytes},
+                                        {&field_eval_split_kernel<true, false, false>, lds_bytes}, {&field_eval_split_kernel<true, true, false>, lds_bytes},
+                                        {&field_eval_split_kernel<false, false, true>, lds_bytes}, {&field_eval_split_kernel<false, true, true>, lds_bytes},
+                                        {&field_eval_split_kernel<true, false, true>, lds_bytes}, {&field_eval_split_kernel<true, true, true>, lds_bytes}}, &cus);
+    if (e != hipSuccess) return e;
     if ((e = launch_dir_bias(p, stream)) != hipSuccess) return e;
     const bool mv = p.V > 1;
     const long n_groups = (p.n_tiles + kWgWaves - 1) / kWgWaves;
-    const long resident = (long)cus[dev];                                   // persistent: one workgroup per CU
+    const long resident = (long)cus;                                        // persistent: one workgroup per CU
     const unsigned wgs = (unsigned)(n_groups < resident ? n_groups : resident);
     const f32x4* w = static_cast<const f32x4*>(packed_split);
     if (p.stash && p.V > 1 && ((long)p.R * p.S) % 32 != 0) return hipErrorInvalidValue;     // tiles must not straddle scenes

@@ -35,9 +35,8 @@
 //                  fp32 range).
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
 #include "mvnerf_kernels.h"
+#include "mvnerf_launch.h"
 #include "mvnerf_math.h"
 #include "mvnerf_mfma.h"
 
@@ -861,42 +860,21 @@ bool MVS16_SUPPORTS(const FieldParams& p) {
 }
 
 hipError_t MVS16_LAUNCH_FN(const FieldParams& p, const void* packed_split16, hipStream_t stream) {
-    static std::mutex mtx;
-    static bool attr_done[16] = {};
-    static int cus[16] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16) return hipErrorInvalidDevice;
+    static DeviceSetup setup;
     if (!MVS16_SUPPORTS(p)) return hipErrorInvalidValue;
     const int lds_bytes = kR16Slots * kR16SlotF4 * 16 + 8 * 32 * kS16StageRowBytes + (kPackBr + 8 - kPackB0) * 4 + kS16MaxPositions * 4 + 512 * 4;
-    {
-        std::lock_guard<std::mutex> lock(mtx);
-        if (!attr_done[dev]) {
-            hipDeviceProp_t prop;
-            if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-            cus[dev] = prop.multiProcessorCount;
-            const void* fns[12] = {reinterpret_cast<const void*>(&MVS16_KERNEL<false, false, false, false>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<false, true, false, false>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<true, false, false, false>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<true, true, false, false>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<false, false, true, false>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<false, true, true, false>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<true, false, true, false>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<true, true, true, false>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<false, false, false, true>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<false, true, false, true>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<true, false, false, true>),
-                                   reinterpret_cast<const void*>(&MVS16_KERNEL<true, true, false, true>)};
-            for (const void* fn : fns)
-                if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess) return e;
-            attr_done[dev] = true;
-        }
-    }
+    int cus = 0;
+    hipError_t e = device_setup(setup, {{&MVS16_KERNEL<false, false, false, false>, lds_bytes}, {&MVS16_KERNEL<false, true, false, false>, lds_bytes},
+                                        {&MVS16_KERNEL<true, false, false, false>, lds_bytes}, {&MVS16_KERNEL<true, true, false, false>, lds_bytes},
+                                        {&MVS16_KERNEL<false, false, true, false>, lds_bytes}, {&MVS16_KERNEL<false, true, true, false>, lds_bytes},
+                                        {&MVS16_KERNEL<true, false, true, false>, lds_bytes}, {&MVS16_KERNEL<true, true, true, false>, lds_bytes},
+                                        {&MVS16_KERNEL<false, false, false, true>, lds_bytes}, {&MVS16_KERNEL<false, true, false, true>, lds_bytes},
+                                        {&MVS16_KERNEL<true, false, false, true>, lds_bytes}, {&MVS16_KERNEL<true, true, false, true>, lds_bytes}}, &cus);
+    if (e != hipSuccess) return e;
     if ((e = launch_dir_bias(p, stream)) != hipSuccess) return e;
     const bool mv = p.V > 1;
     const long n_groups = (p.n_tiles + 7) / 8;
-    const long resident = (long)cus[dev];                                   // persistent: one workgroup per CU
+    const long resident = (long)cus;                                        // persistent: one workgroup per CU
     const unsigned wgs = (unsigned)(n_groups < resident ? n_groups : resident);
     const f32x4* w = static_cast<const f32x4*>(packed_split16);
     const dim3 grid(wgs), block(512);

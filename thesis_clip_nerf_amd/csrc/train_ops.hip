@@ -12,9 +12,8 @@
 // the sample positions, Adam with clip-by-value.  See DESIGN.md section 8.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "mvnerf_kernels.h"
+#include "mvnerf_launch.h"
 #include "mvnerf_math.h"
 #include "mvnerf_mfma.h"
 
@@ -769,18 +768,9 @@ hipError_t launch_dense_bwd_fused(const float* g_tl, const float* a_tl, const fl
                                   const float* amax_in, float* amax_out) {
     // `part` != nullptr (deterministic mode): every workgroup stores its partial of the span [dW | db] (db directly behind dW) and
     // launch_reduce_partials adds them in a fixed order; otherwise fp32 atomics straight onto the gradient.
-    static std::atomic<bool> attr_done[16];               // first call per device sets the dynamic-LDS limits (idempotent)
-    int dev = 0;
-    hipError_t ea = hipGetDevice(&dev);
+    static DeviceSetup setup;
+    const hipError_t ea = device_setup(setup, {{&dense_dx_kernel, kBwdLdsBytes}, {&dense_bwd_split8_kernel, kBwd8LdsBytes}});
     if (ea != hipSuccess) return ea;
-    if (dev < 0 || dev >= 16) return hipErrorInvalidDevice;
-    if (!attr_done[dev].load(std::memory_order_acquire)) {
-        ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kBwdLdsBytes);
-        if (ea == hipSuccess)
-            ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_split8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kBwd8LdsBytes);
-        if (ea != hipSuccess) return ea;
-        attr_done[dev].store(true, std::memory_order_release);
-    }
     if (n_tiles <= 0 || n_tiles > 0x7fffffffL) return hipErrorInvalidValue;                // tile indices are 32-bit inside the kernels
     if (!dW) {                                             // frozen trunk (query_vjp): two 256-thread workgroups per CU
         const unsigned wgs = (unsigned)(n_tiles < max_wgs ? n_tiles : max_wgs);
@@ -1487,15 +1477,9 @@ hipError_t launch_dw0(const FieldParams& p, const float* g0_tl, float* dW0, floa
     if (MVT_BWD_F16 && !amax_in) return hipErrorInvalidValue;                  // the fp16 products need the gradient's scale
     const long view_tiles = p.n_tiles * p.V;
     if (view_tiles <= 0 || view_tiles > 0x7fffffffL) return hipErrorInvalidValue;
-    static std::atomic<bool> attr_done[16];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static DeviceSetup setup;
+    hipError_t e = device_setup(setup, {{&dw0_split8_kernel, kDw8LdsBytes}});
     if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 16 && !attr_done[dev].load(std::memory_order_acquire)) {
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw0_split8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDw8LdsBytes)) != hipSuccess)
-            return e;
-        attr_done[dev].store(true, std::memory_order_release);
-    }
     if (!part || db0 != dW0 + kIn * kHidden) return hipErrorInvalidValue;      // one span [dW0 | db0], reduced from per-workgroup partials
     const int span = kIn * kHidden + kHidden;
     const unsigned wgs = (unsigned)(view_tiles < max_wgs / 2 ? view_tiles : max_wgs / 2);      // one 512-thread workgroup per CU
@@ -2050,16 +2034,9 @@ hipError_t launch_field_dz(const FieldParams& p, const float* g0_tl, const float
         return hipGetLastError();
     }
     const size_t lds_bytes = (size_t)4 * (32 * kDfeRow + 64) * sizeof(float);
-    static std::atomic<bool> attr_done[16];      // first call per device sets the dynamic-LDS limit (idempotent)
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static DeviceSetup setup;
+    const hipError_t e = device_setup(setup, {{&field_dz_kernel<false>, (int)lds_bytes}});
     if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 16 && !attr_done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&field_dz_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        attr_done[dev].store(true, std::memory_order_release);
-    }
     hipLaunchKernelGGL(field_dz_kernel<false>, dim3(wgs), dim3(256), lds_bytes, st, p, g0_tl, w0t_streams, d_z, d_o, d_d, d_features);
     return hipGetLastError();
 }

@@ -39,6 +39,17 @@ def _stream(t):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def _scene(images, features, intrinsics, extrinsics_inv, b=None, features_dtype=torch.float32):
+    """The source views of a field pass: images (B,V,H,W,3), features (B,V,H,W,256), intrinsics and extrinsics_inv (B,V,4,4)
+    -> (b, v, h, w).  b: the batch size the caller's rays or points have already fixed."""
+    _chk(images, 'images', shape=(b, None, None, None, 3))
+    b, v, h, w, _ = images.shape
+    _chk(features, 'features', dtype=features_dtype, shape=(b, v, h, w, 256))
+    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
+    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
+    return b, v, h, w
+
+
 def packed_net_floats():
     return int(_lib.lib().mvnerf_packed_net_floats())
 
@@ -91,6 +102,18 @@ def texel_table_pays(n_rays_per_scene, n_samples, h, w):
     return n_rays_per_scene * n_samples >= 2 * h * w
 
 
+def _auto_texel_tables(texel_tables, bvhw, n_rays_per_scene, n_samples, device):
+    """The texel_tables argument of the render_fwd* functions: 'auto' -> a (2,B,V,H,W,128) tensor to build when
+    texel_table_pays(), else None; None or a tensor is handed back."""
+    if not isinstance(texel_tables, str):
+        return texel_tables
+    if texel_tables != 'auto':
+        raise ValueError(f"texel_tables: {texel_tables!r}, expected None, 'auto' or a tensor")
+    if not texel_table_pays(n_rays_per_scene, n_samples, bvhw[2], bvhw[3]):
+        return None
+    return torch.empty((2,) + tuple(bvhw) + (128,), dtype=torch.float32, device=device)
+
+
 def project_texels(features, packed_net, out=None):
     """mvnerf_project_texels: features (B,V,H,W,256), one net's packed image -> table (B,V,H,W,128)
     (W0[123:379]^T features per texel, accumulator order) for field_eval(..., texel_table=table)."""
@@ -124,41 +147,36 @@ def project_texels2(features, packed_a, packed_b, out=None):
     return out
 
 
-def field_eval(rays_o, rays_d, z, images, features, intrinsics, extrinsics_inv, packed_net, return_taps=False,
-               return_pix=False, return_embedding=False, complete_output=False, texel_table=None):
-    """mvnerf_field_eval: -> rgbs (B,R,S,4) [+ tap_idx (B,V,R,S,4) int32] [+ pix (B,V,R,S,2)] [+ embedding (B,R,S,128)].
-    texel_table: project_texels(features, packed_net) of the SAME net -> mvnerf_field_eval_table."""
+def _field_pass(what, fn, rays_o, rays_d, z, scene, packed_net, second=None, texel_table=None, table_arg=True, wide=True,
+                features_dtype=torch.float32, return_taps=False, return_pix=False, return_embedding=False, complete_output=False,
+                return_fused_acts=False):
+    """The checks, output allocation, C call and result tuple of field_eval / field_eval_split / field_eval_bf16.
+    fn: the entry point; second: (tensor, name, bytes) of the weight stream it takes behind packed_net; table_arg: it takes a
+    texel_table; wide: it has the pix and per-view outputs (the bf16 entry points do not)."""
     _chk(rays_o, 'rays_o', shape=(None, None, 3))
     b, r, _ = rays_o.shape
     _chk(rays_d, 'rays_d', shape=(b, r, 3))
     _chk(z, 'z', shape=(b, r, None))
     s = z.shape[2]
-    _chk(images, 'images', shape=(b, None, None, None, 3))
-    _, v, h, w, _ = images.shape
-    _chk(features, 'features', shape=(b, v, h, w, 256))
-    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
-    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
+    _, v, h, w = _scene(*scene, b=b, features_dtype=features_dtype)
     _chk(packed_net, 'packed_net', shape=(packed_net_floats(),))
+    if second is not None:
+        _chk(second[0], second[1], dtype=torch.uint8, shape=(second[2],))
+    if texel_table is not None:
+        _chk(texel_table, 'texel_table', shape=(b, v, h, w, 128))
     dev = rays_o.device
     rgbs = torch.empty((b, r, s, 4), dtype=torch.float32, device=dev)
     taps = torch.empty((b, v, r, s, 4), dtype=torch.int32, device=dev) if return_taps else None
     pix = torch.empty((b, v, r, s, 2), dtype=torch.float32, device=dev) if return_pix else None
     emb = torch.empty((b, r, s, 128), dtype=torch.float32, device=dev) if return_embedding else None
     acts_v = torch.empty((4, b * v, r, s, 128), dtype=torch.float32, device=dev) if complete_output else None
-    acts_f = torch.empty((4, b, r, s, 128), dtype=torch.float32, device=dev) if complete_output else None
+    acts_f = torch.empty((4, b, r, s, 128), dtype=torch.float32, device=dev) if complete_output or return_fused_acts else None
     ws = torch.empty(int(_lib.lib().mvnerf_field_workspace_bytes(b, v, r)), dtype=torch.uint8, device=dev)
+    ins = [rays_o, rays_d, z, scene[0], scene[1]] + ([texel_table] if table_arg else []) + [scene[2], scene[3], packed_net]
+    outs = [rgbs, taps, pix, emb, acts_v, acts_f] if wide else [rgbs, taps, emb, acts_f]
     with torch.cuda.device(dev):
-        if texel_table is None:
-            rc = _lib.lib().mvnerf_field_eval(_p(rays_o), _p(rays_d), _p(z), _p(images), _p(features), _p(intrinsics),
-                                              _p(extrinsics_inv), _p(packed_net), b, v, r, s, h, w, _p(rgbs), _p(taps),
-                                              _p(pix), _p(emb), _p(acts_v), _p(acts_f), _p(ws), _stream(rays_o))
-        else:
-            _chk(texel_table, 'texel_table', shape=(b, v, h, w, 128))
-            rc = _lib.lib().mvnerf_field_eval_table(_p(rays_o), _p(rays_d), _p(z), _p(images), _p(features),
-                                                    _p(texel_table), _p(intrinsics), _p(extrinsics_inv), _p(packed_net),
-                                                    b, v, r, s, h, w, _p(rgbs), _p(taps), _p(pix), _p(emb), _p(acts_v),
-                                                    _p(acts_f), _p(ws), _stream(rays_o))
-    _lib.check(rc, 'field_eval')
+        rc = fn(*map(_p, ins + ([] if second is None else [second[0]])), b, v, r, s, h, w, *map(_p, outs + [ws]), _stream(rays_o))
+    _lib.check(rc, what)
     out = (rgbs,)
     if return_taps:
         out += (taps,)
@@ -168,7 +186,19 @@ def field_eval(rays_o, rays_d, z, images, features, intrinsics, extrinsics_inv, 
         out += (emb,)
     if complete_output:               # the reference's `outputs` list (layers.py:364-377): 4 per-view + 4 fused
         out += (list(acts_v.unbind(0)) + list(acts_f.unbind(0)),)
+    if return_fused_acts:
+        out += (acts_f,)
     return out if len(out) > 1 else rgbs
+
+
+def field_eval(rays_o, rays_d, z, images, features, intrinsics, extrinsics_inv, packed_net, return_taps=False,
+               return_pix=False, return_embedding=False, complete_output=False, texel_table=None):
+    """mvnerf_field_eval: -> rgbs (B,R,S,4) [+ tap_idx (B,V,R,S,4) int32] [+ pix (B,V,R,S,2)] [+ embedding (B,R,S,128)].
+    texel_table: project_texels(features, packed_net) of the SAME net -> mvnerf_field_eval_table."""
+    fn = _lib.lib().mvnerf_field_eval if texel_table is None else _lib.lib().mvnerf_field_eval_table
+    return _field_pass('field_eval', fn, rays_o, rays_d, z, (images, features, intrinsics, extrinsics_inv), packed_net,
+                       texel_table=texel_table, table_arg=texel_table is not None, return_taps=return_taps, return_pix=return_pix,
+                       return_embedding=return_embedding, complete_output=complete_output)
 
 
 def query_field(points, dirs, images, features, intrinsics, extrinsics_inv, packed_net, complete_output=False):
@@ -252,11 +282,7 @@ def render_fwd(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, pac
     _chk(rays_o, 'rays_o', shape=(None, None, 3))
     b, r, _ = rays_o.shape
     _chk(rays_d, 'rays_d', shape=(b, r, 3))
-    _chk(images, 'images', shape=(b, None, None, None, 3))
-    _, v, h, w, _ = images.shape
-    _chk(features, 'features', shape=(b, v, h, w, 256))
-    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
-    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
+    _, v, h, w = _scene(images, features, intrinsics, extrinsics_inv, b=b)
     _chk(u_coarse, 'u_coarse', shape=(b, r, None))
     s = u_coarse.shape[2]
     _chk(u_fine, 'u_fine', shape=(b, r, s))
@@ -275,11 +301,8 @@ def render_fwd(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, pac
                torch.empty((b, r, 3), dtype=torch.float32, device=dev), torch.empty((b, r), dtype=torch.float32, device=dev))
     rgb, depth, fine_rgb, fine_depth = out
     if isinstance(texel_tables, str):
-        if texel_tables != 'auto':
-            raise ValueError(f"texel_tables: {texel_tables!r}, expected None, 'auto' or a tensor")
-        texel_tables = (torch.empty((2, b, v, h, w, 128), dtype=torch.float32, device=dev)
-                        if texel_table_pays(r, s, h, w) else None)
         tables_ready = False
+    texel_tables = _auto_texel_tables(texel_tables, (b, v, h, w), r, s, dev)
     if texel_tables is not None:
         _chk(texel_tables, 'texel_tables', shape=(2, b, v, h, w, 128))
     with torch.cuda.device(dev):
@@ -444,11 +467,7 @@ def field_eval_stash(rays_o, rays_d, z, images, features, intrinsics, extrinsics
     _chk(rays_d, 'rays_d', shape=(b, r, 3))
     _chk(z, 'z', shape=(b, r, None))
     s = z.shape[2]
-    _chk(images, 'images', shape=(b, None, None, None, 3))
-    _, v, h, w, _ = images.shape
-    _chk(features, 'features', shape=(b, v, h, w, 256))
-    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
-    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
+    _, v, h, w = _scene(images, features, intrinsics, extrinsics_inv, b=b)
     _chk(packed_net, 'packed_net', shape=(packed_net_floats(),))
     dev = rays_o.device
     need = stash_bytes(b, v, r, s)
@@ -704,11 +723,7 @@ def grasp_workspace_bytes(b, v, p, n5):
 def grasp_call(images, features, intrinsics, extrinsics_inv, packed_net, split, bwd_streams, head_packed, head_b4, head_bc, tail_packed, offsets,
                t, rot, success, g_t, g_rot, workspace):
     """Fill a mvnerf_grasp_call (include/mvnerf_hip.h) from device tensors after checking shapes; the caller keeps the tensors alive."""
-    _chk(images, 'images', shape=(None, None, None, None, 3))
-    b, v, h, w, _ = images.shape
-    _chk(features, 'features', shape=(b, v, h, w, 256))
-    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
-    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
+    b, v, h, w = _scene(images, features, intrinsics, extrinsics_inv)
     _chk(packed_net, 'packed_net', shape=(packed_net_floats(),))
     _chk(split, 'split', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_packed_net_split_bytes()),))
     _chk(bwd_streams, 'bwd_streams', shape=(15 * 16384,))
@@ -775,11 +790,7 @@ def train_call(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, u_c
     _chk(rays_o, 'rays_o', shape=(None, None, 3))
     b, r, _ = rays_o.shape
     _chk(rays_d, 'rays_d', shape=(b, r, 3))
-    _chk(images, 'images', shape=(b, None, None, None, 3))
-    _, v, h, w, _ = images.shape
-    _chk(features, 'features', shape=(b, v, h, w, 256))
-    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
-    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
+    _, v, h, w = _scene(images, features, intrinsics, extrinsics_inv, b=b)
     _chk(u_coarse, 'u_coarse', shape=(b, r, None))
     s = u_coarse.shape[2]
     _chk(u_fine, 'u_fine', shape=(b, r, s))
@@ -997,33 +1008,28 @@ def field_eval_bf16(rays_o, rays_d, z, images, features, intrinsics, extrinsics_
     return_fused_acts: + (4,B,R,S,128) = view mean and the three fusion blocks (complete_output[4:]).
     features: fp32, or bfloat16 (B,V,H,W,256) -> mvnerf_field_eval_bf16maps (the gather reads bf16 texel rows)."""
     maps16 = isinstance(features, torch.Tensor) and features.dtype == torch.bfloat16
-    _chk(rays_o, 'rays_o', shape=(None, None, 3))
-    b, r, _ = rays_o.shape
-    _chk(rays_d, 'rays_d', shape=(b, r, 3))
-    _chk(z, 'z', shape=(b, r, None))
-    s = z.shape[2]
-    _chk(images, 'images', shape=(b, None, None, None, 3))
-    _, v, h, w, _ = images.shape
-    _chk(features, 'features', dtype=torch.bfloat16 if maps16 else torch.float32, shape=(b, v, h, w, 256))
-    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
-    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
-    _chk(packed_net, 'packed_net', shape=(packed_net_floats(),))
-    _chk(packed16, 'packed16', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_packed_net_bf16_bytes()),))
-    dev = rays_o.device
-    rgbs = torch.empty((b, r, s, 4), dtype=torch.float32, device=dev)
-    taps = torch.empty((b, v, r, s, 4), dtype=torch.int32, device=dev) if return_taps else None
-    emb = torch.empty((b, r, s, 128), dtype=torch.float32, device=dev) if return_embedding else None
-    fused = torch.empty((4, b, r, s, 128), dtype=torch.float32, device=dev) if return_fused_acts else None
-    if texel_table is not None:
-        _chk(texel_table, 'texel_table', shape=(b, v, h, w, 128))
-    ws = torch.empty(int(_lib.lib().mvnerf_field_workspace_bytes(b, v, r)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        fn = _lib.lib().mvnerf_field_eval_bf16maps if maps16 else _lib.lib().mvnerf_field_eval_bf16
-        rc = fn(_p(rays_o), _p(rays_d), _p(z), _p(images), _p(features), _p(texel_table), _p(intrinsics), _p(extrinsics_inv), _p(packed_net),
-                _p(packed16), b, v, r, s, h, w, _p(rgbs), _p(taps), _p(emb), _p(fused), _p(ws), _stream(rays_o))
-    _lib.check(rc, 'field_eval_bf16')
-    out = (rgbs,) + ((taps,) if return_taps else ()) + ((emb,) if return_embedding else ()) + ((fused,) if return_fused_acts else ())
-    return out if len(out) > 1 else rgbs
+    fn = _lib.lib().mvnerf_field_eval_bf16maps if maps16 else _lib.lib().mvnerf_field_eval_bf16
+    return _field_pass('field_eval_bf16', fn, rays_o, rays_d, z, (images, features, intrinsics, extrinsics_inv), packed_net,
+                       second=(packed16, 'packed16', int(_lib.lib().mvnerf_packed_net_bf16_bytes())), texel_table=texel_table, wide=False,
+                       features_dtype=torch.bfloat16 if maps16 else torch.float32, return_taps=return_taps,
+                       return_embedding=return_embedding, return_fused_acts=return_fused_acts)
+
+
+def _render_two_pass(field, build_tables, features, u_coarse, u_fine, near, far, q7_mode, texel_tables):
+    """`_call` (model_v0.py:113-184) as two field passes around the fp32 sampling, compositing and resampling.
+    field(z, k, texel_table) -> rgbs of net k (0 coarse, 1 fine); build_tables(out) fills and returns both nets' tables."""
+    tab_c = tab_f = None
+    b, r, s = u_coarse.shape
+    texel_tables = _auto_texel_tables(texel_tables, tuple(features.shape[:4]), r, s, features.device)
+    if texel_tables is not None:
+        tab_c, tab_f = build_tables(texel_tables).unbind(0)
+    z = stratified_depths(u_coarse, near, far)
+    rgbs_c = field(z, 0, tab_c)
+    rgb, depth, w = composite(z, rgbs_c)
+    z_all = resample(z, w, u_fine, q7_mode)
+    rgbs_f = field(z_all, 1, tab_f)
+    fine_rgb, fine_depth, _ = composite(z_all, rgbs_f, return_weights=False)
+    return rgb, depth, fine_rgb, fine_depth
 
 
 def render_fwd_bf16(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, packed_coarse, packed_fine, packed16_coarse,
@@ -1031,21 +1037,10 @@ def render_fwd_bf16(rays_o, rays_d, images, features, intrinsics, extrinsics_inv
     """`_call` with both field passes on the bf16 path (sampling, compositing and resampling stay fp32).
     texel_tables: 'auto' (build the two fp32 tables when texel_table_pays), None, or a (2,B,V,H,W,128) tensor to fill."""
     geo = (images, features, intrinsics, extrinsics_inv)
-    tab_c = tab_f = None
-    if isinstance(texel_tables, str):
-        b, r, s = u_coarse.shape
-        h, w_ = images.shape[2:4]
-        texel_tables = (torch.empty((2,) + tuple(features.shape[:4]) + (128,), dtype=torch.float32, device=features.device)
-                        if texel_table_pays(r, s, h, w_) else None)
-    if texel_tables is not None:
-        tab_c, tab_f = project_texels_bf16(features, packed16_coarse, out=texel_tables, packed16_b=packed16_fine).unbind(0)
-    z = stratified_depths(u_coarse, near, far)
-    rgbs_c = field_eval_bf16(rays_o, rays_d, z, *geo, packed_coarse, packed16_coarse, texel_table=tab_c)
-    rgb, depth, w = composite(z, rgbs_c)
-    z_all = resample(z, w, u_fine, q7_mode)
-    rgbs_f = field_eval_bf16(rays_o, rays_d, z_all, *geo, packed_fine, packed16_fine, texel_table=tab_f)
-    fine_rgb, fine_depth, _ = composite(z_all, rgbs_f, return_weights=False)
-    return rgb, depth, fine_rgb, fine_depth
+    nets, nets16 = (packed_coarse, packed_fine), (packed16_coarse, packed16_fine)
+    return _render_two_pass(lambda z, k, tab: field_eval_bf16(rays_o, rays_d, z, *geo, nets[k], nets16[k], texel_table=tab),
+                            lambda out: project_texels_bf16(features, packed16_coarse, out=out, packed16_b=packed16_fine),
+                            features, u_coarse, u_fine, near, far, q7_mode, texel_tables)
 
 
 # ---- fp32-grade field pass on the bf16 matrix pipe (three-piece operand split, csrc/field_eval_split.hip) ------------------
@@ -1062,43 +1057,10 @@ def field_eval_split(rays_o, rays_d, z, images, features, intrinsics, extrinsics
                      return_pix=False, return_embedding=False, complete_output=False, texel_table=None):
     """mvnerf_field_eval_split: field_eval (same outputs, same fp32 bar) with the Dense layers as split-bf16 MFMA products.
     texel_table: project_texels(features, packed_net) of the same net (fp32)."""
-    _chk(rays_o, 'rays_o', shape=(None, None, 3))
-    b, r, _ = rays_o.shape
-    _chk(rays_d, 'rays_d', shape=(b, r, 3))
-    _chk(z, 'z', shape=(b, r, None))
-    s = z.shape[2]
-    _chk(images, 'images', shape=(b, None, None, None, 3))
-    _, v, h, w, _ = images.shape
-    _chk(features, 'features', shape=(b, v, h, w, 256))
-    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
-    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
-    _chk(packed_net, 'packed_net', shape=(packed_net_floats(),))
-    _chk(packed_split, 'packed_split', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_packed_net_split_bytes()),))
-    dev = rays_o.device
-    rgbs = torch.empty((b, r, s, 4), dtype=torch.float32, device=dev)
-    taps = torch.empty((b, v, r, s, 4), dtype=torch.int32, device=dev) if return_taps else None
-    pix = torch.empty((b, v, r, s, 2), dtype=torch.float32, device=dev) if return_pix else None
-    emb = torch.empty((b, r, s, 128), dtype=torch.float32, device=dev) if return_embedding else None
-    acts_v = torch.empty((4, b * v, r, s, 128), dtype=torch.float32, device=dev) if complete_output else None
-    acts_f = torch.empty((4, b, r, s, 128), dtype=torch.float32, device=dev) if complete_output else None
-    if texel_table is not None:
-        _chk(texel_table, 'texel_table', shape=(b, v, h, w, 128))
-    ws = torch.empty(int(_lib.lib().mvnerf_field_workspace_bytes(b, v, r)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().mvnerf_field_eval_split(_p(rays_o), _p(rays_d), _p(z), _p(images), _p(features), _p(texel_table),
-                                                _p(intrinsics), _p(extrinsics_inv), _p(packed_net), _p(packed_split), b, v, r, s, h, w,
-                                                _p(rgbs), _p(taps), _p(pix), _p(emb), _p(acts_v), _p(acts_f), _p(ws), _stream(rays_o))
-    _lib.check(rc, 'field_eval_split')
-    out = (rgbs,)
-    if return_taps:
-        out += (taps,)
-    if return_pix:
-        out += (pix,)
-    if return_embedding:
-        out += (emb,)
-    if complete_output:
-        out += (list(acts_v.unbind(0)) + list(acts_f.unbind(0)),)
-    return out if len(out) > 1 else rgbs
+    return _field_pass('field_eval_split', _lib.lib().mvnerf_field_eval_split, rays_o, rays_d, z, (images, features, intrinsics, extrinsics_inv),
+                       packed_net, second=(packed_split, 'packed_split', int(_lib.lib().mvnerf_packed_net_split_bytes())),
+                       texel_table=texel_table, return_taps=return_taps, return_pix=return_pix, return_embedding=return_embedding,
+                       complete_output=complete_output)
 
 
 def render_fwd_split(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, packed_coarse, packed_fine, split_coarse,
@@ -1106,21 +1068,10 @@ def render_fwd_split(rays_o, rays_d, images, features, intrinsics, extrinsics_in
     """`_call` (model_v0.py:113-184) with both field passes on the split-bf16 kernel (fp32-grade products, 1e-4 bar).
     texel_tables: 'auto' (build the two fp32 tables when texel_table_pays), None, or a (2,B,V,H,W,128) tensor to fill."""
     geo = (images, features, intrinsics, extrinsics_inv)
-    tab_c = tab_f = None
-    if isinstance(texel_tables, str):
-        b, r, s = u_coarse.shape
-        h, w_ = images.shape[2:4]
-        texel_tables = (torch.empty((2,) + tuple(features.shape[:4]) + (128,), dtype=torch.float32, device=features.device)
-                        if texel_table_pays(r, s, h, w_) else None)
-    if texel_tables is not None:
-        tab_c, tab_f = project_texels2(features, packed_coarse, packed_fine, out=texel_tables).unbind(0)
-    z = stratified_depths(u_coarse, near, far)
-    rgbs_c = field_eval_split(rays_o, rays_d, z, *geo, packed_coarse, split_coarse, texel_table=tab_c)
-    rgb, depth, w = composite(z, rgbs_c)
-    z_all = resample(z, w, u_fine, q7_mode)
-    rgbs_f = field_eval_split(rays_o, rays_d, z_all, *geo, packed_fine, split_fine, texel_table=tab_f)
-    fine_rgb, fine_depth, _ = composite(z_all, rgbs_f, return_weights=False)
-    return rgb, depth, fine_rgb, fine_depth
+    nets, splits = (packed_coarse, packed_fine), (split_coarse, split_fine)
+    return _render_two_pass(lambda z, k, tab: field_eval_split(rays_o, rays_d, z, *geo, nets[k], splits[k], texel_table=tab),
+                            lambda out: project_texels2(features, packed_coarse, packed_fine, out=out),
+                            features, u_coarse, u_fine, near, far, q7_mode, texel_tables)
 
 
 # ---- the trunk as a differentiable field on query points (SURVEY.md 8f-1; lmvnerf/model_v4.py:208-265) -------------
@@ -1128,11 +1079,7 @@ def _query_shapes(points, dirs, images, features, intrinsics, extrinsics_inv):
     _chk(points, 'points', shape=(None, None, 3))
     b, n, _ = points.shape
     _chk(dirs, 'dirs', shape=(b, n, 3))
-    _chk(images, 'images', shape=(b, None, None, None, 3))
-    _, v, h, w, _ = images.shape
-    _chk(features, 'features', shape=(b, v, h, w, 256))
-    _chk(intrinsics, 'intrinsics', shape=(b, v, 4, 4))
-    _chk(extrinsics_inv, 'extrinsics_inv', shape=(b, v, 4, 4))
+    _, v, h, w = _scene(images, features, intrinsics, extrinsics_inv, b=b)
     return b, v, n, h, w
 
 
