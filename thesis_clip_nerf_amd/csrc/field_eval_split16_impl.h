@@ -68,6 +68,8 @@ using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+// read-only kernel inputs at a wave-uniform address, read through the constant address space: scalar loads
+using cfloat = const __attribute__((address_space(4))) float;
 
 // ---- weight stream: 1 KiB chunks [lane][8 bf16]; chunk = 24 * kstep + 3 * rb + piece ------------------------------------
 //   k-steps 0..1  : layer 0, PE(cam xyz) + rgb: lane group g, slot e = 8 t + jj (16 slots per group)
@@ -199,13 +201,14 @@ constexpr int kS16MaxPositions = 512;
 
 struct Ring16 {
     const f32x4* w;
-    f32x4* base;        // LDS
-    int c;              // ring slot of the current k-step
-    int p, P;
-    const int* table;   // LDS: first chunk of every position of one tile
-    int start_pf;       // first chunk of the position the next fetch loads (read one k-step ahead)
-    int tid, wave;
-    u32x4 a0[3];        // A operands (3 pieces) of row block 0 of the CURRENT k-step, read during the previous one
+    unsigned char* lds;        // LDS: slot 0
+    int cur, nxt, fill;        // byte offsets of the slots of positions p and p + 1 and of the slot the fetch of position p + 2 fills (the
+                               // slot of p - 1): rotated by ring16_next, scalar registers
+    const int* table;          // LDS: byte offset in the weight stream of every position of one tile
+    int pf4, P4;               // byte offset in `table` of the entry the next fetch reads (position p + 3), table size in bytes
+    int start_pf;              // that entry of the position the next fetch loads (read one k-step ahead; the same in every lane)
+    int lane_off, wave_off;    // 16 tid (source), 1024 wave (destination)
+    u32x4 a0[3];               // A operands (3 pieces) of row block 0 of the CURRENT k-step, read during the previous one
 };
 
 __device__ __forceinline__ int ring16_start_chunk(int p, int V, int l0_units) {
@@ -217,44 +220,49 @@ __device__ __forceinline__ int ring16_start_chunk(int p, int V, int l0_units) {
     return (kS16L0Pe + kS16L0Feat + kS16PerView + (p - per_view * V)) * kS16SlotChunks;
 }
 
-// LDS-DMA of one position (24 chunks of 1 KiB starting at `start_chunk`) into ring slot `slot`: three wave-instructions per wave, each
-// moving 1 KiB (lane l: 16 bytes at wave base + 16 l); wave w of the 8 covers bytes [1024 w, 1024 w + 1024) of each 8 KiB third.
-__device__ __forceinline__ void ring16_dma(const Ring16& r, int start_chunk, int slot) {
-    const f32x4* src = r.w + (long)start_chunk * 64 + r.tid;
-    f32x4* dst = r.base + slot * kR16SlotF4 + 64 * r.wave;
+// LDS-DMA of one position (24 chunks of 1 KiB starting `start` bytes into the stream, wave-uniform) into the ring slot at byte offset
+// `slot`: three wave-instructions per wave, each moving 1 KiB (lane l: 16 bytes at wave base + 16 l); wave w of the 8 covers bytes
+// [1024 w, 1024 w + 1024) of each 8 KiB third.  The source is a scalar base plus the lane's constant 32-bit offset (the instruction's
+// saddr form): no 64-bit vector address arithmetic per k-step.
+__device__ __forceinline__ void ring16_dma(const Ring16& r, int start, int slot) {
+    const unsigned char* src = reinterpret_cast<const unsigned char*>(r.w) + (unsigned)start;
+    const int dst = (int)(unsigned long)(__attribute__((address_space(3))) unsigned char*)r.lds + slot + r.wave_off;
+    // (inline asm: through the builtin the compiler widens the lane offset to 64 bits and adds it on the vector ALU per request; s_nop:
+    // the M0 write must be one instruction away from the request that reads it.  M0 is declared clobbered.)
 #pragma unroll
     for (int i = 0; i < 3; ++i)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 512 * i),
-                                         (__attribute__((address_space(3))) void*)(dst + 512 * i), 16, 0, 0);
+        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(r.lane_off), "s"(src + 8192 * i), "s"(dst + 8192 * i) : "memory", "m0");
 }
 
-// The weight fetch of the k-step at position p (slot c), issued behind its first MFMA group: position p + 2 goes straight into slot
-// (c + 2) % 3 by LDS-DMA - the slot of position p - 1, which nobody reads any more since the last barrier; the vmcnt(0) in front of the
-// barrier at the k-step's end (ring16_next) lets it land before it is published; seven of the k-step's eight MFMA groups lie between the
-// request and that wait.  No staging registers, no ds_write.
+// The weight fetch of the k-step at position p, issued behind its first MFMA group: position p + 2 goes straight into the slot of
+// position p - 1 by LDS-DMA, which nobody reads any more since the last barrier; the vmcnt(0) in front of the barrier at the k-step's
+// end (ring16_next) lets it land before it is published; seven of the k-step's eight MFMA groups lie between the request and that
+// wait.  No staging registers, no ds_write.
 // The training forward uses this ring too, although its vmcnt(0) per k-step then also waits for the stash stores of the layer boundary
 // in front of it (vmcnt retires in order): on the fp16 form that costs less than the staging registers and LDS stores of a
 // register-staged ring (three dwordx4 loads per thread and k-step, stored one k-step later; train step 5.77 -> 5.74 ms,
 // scripts/ab_train_libs.sh).
 __device__ __forceinline__ void ring16_fetch(Ring16& r) {
-    int slot = r.c + 2;
-    slot = slot >= kR16Slots ? slot - kR16Slots : slot;
-    ring16_dma(r, r.start_pf, slot);
-    int pp = r.p + 3;                                                   // table entry the NEXT k-step's fetch needs
-    pp = pp >= r.P ? pp - r.P : pp;
-    r.start_pf = r.table[pp];
+    ring16_dma(r, __builtin_amdgcn_readfirstlane(r.start_pf), r.fill);
+    r.start_pf = *reinterpret_cast<const int*>(reinterpret_cast<const unsigned char*>(r.table) + r.pf4);   // for the NEXT k-step's fetch
+    r.pf4 = r.pf4 + 4 == r.P4 ? 0 : r.pf4 + 4;
 }
 
-__device__ __forceinline__ const f32x4* ring16_cur(const Ring16& r) { return r.base + r.c * kR16SlotF4; }
-__device__ __forceinline__ const f32x4* ring16_nxt(const Ring16& r) { return r.base + (r.c + 1 == kR16Slots ? 0 : r.c + 1) * kR16SlotF4; }
+__device__ __forceinline__ const f32x4* ring16_cur(const Ring16& r) { return reinterpret_cast<const f32x4*>(r.lds + r.cur); }
+__device__ __forceinline__ const f32x4* ring16_nxt(const Ring16& r) { return reinterpret_cast<const f32x4*>(r.lds + r.nxt); }
 
 // The end of a k-step waits for all its weight requests (vmcnt(0)): waiting only for position p + 1 (vmcnt(3), the requests of position
 // p + 2 in flight for one more k-step, row block 0's A operands then read at the k-step's start) measured 0.5 % slower on the fp16 form
 // (profiles/r03_ab_dma_late.log) - the request has landed by the end of its k-step, and those A operands are better read a k-step early.
 __device__ __forceinline__ void ring16_next(Ring16& r) {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    r.c = r.c + 1 == kR16Slots ? 0 : r.c + 1;
-    r.p = r.p + 1 == r.P ? 0 : r.p + 1;
+    // the wait as a builtin: the compiler's own counter bookkeeping sees it (a wait inside inline asm it does not, and then waits again
+    // for row block 0's A operands - read a k-step ago - in front of the first MFMA behind the barrier, behind the new LDS reads)
+    __builtin_amdgcn_s_waitcnt(0x0070);                                     // vmcnt(0) lgkmcnt(0)
+    asm volatile("s_barrier" ::: "memory");
+    const int done = r.cur;
+    r.cur = r.nxt;
+    r.nxt = r.fill;
+    r.fill = done;
 }
 
 // position of feature 16 rb + 4 g (+ 0..3) inside a 128-float vector in the 32x32 accumulator order [h][nb][r] that the bias
@@ -289,9 +297,14 @@ __device__ __forceinline__ void apply_bias_row(f32x4 (&row)[2], const f32x4& bv)
 //            the next layer's bias rows here measured +0.3 %, profiles/r03_ab_tailbias.log); the last k-step of every hidden layer
 //            is still scheduled with this mode's group pattern (one more LDS-read slot and vector slots per MFMA), not kMode 0's;
 //   kMode 0: nothing.
-template <bool kRelu, int kMode, bool kTailAdd>
+// kInit: the first k-step of a layer whose accumulators start at its bias vector (init_bias, 32x32 accumulator order): the bias row
+// of row block rb is the C operand of the first MFMA of both chains of that row block (D = A B + C: the bits of acc = bias, then
+// acc += A B) instead of 64 v_mov in front of the layer; acc's old contents are not read.  The row of row block rb + 1 is requested
+// from LDS while group rb runs (as the tail rows below), row 0 (init0) by the caller in front of the layer's first cut.
+template <bool kRelu, int kMode, bool kTailAdd, bool kInit = false>
 __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16 (&b)[2], const float (&nv)[2][8], B16 (&bn)[2], f32x4 (&acc)[8][2],
-                                        f32x4 (&in)[8][2], const float* __restrict__ tail_bias) {
+                                        f32x4 (&in)[8][2], const float* __restrict__ tail_bias, const float* __restrict__ init_bias = nullptr,
+                                        f32x4 init0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}) {
     const f32x4* cur = ring16_cur(ring) + lane;
     const f32x4* nxt = ring16_nxt(ring) + lane;
     u32x4 a[3] = {ring.a0[0], ring.a0[1], ring.a0[2]};
@@ -299,14 +312,18 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
     // the lane's part of perm_f4, formed HERE (behind an empty asm): left to itself the compiler hoists the eight row addresses of every
     // layer's bias vector out of the tile loop and spills them
     int glane = (g & 1) * 16 + (g >> 1);
-    if (kMode == 4) asm volatile("" : "+v"(glane));
+    if (kMode == 4 || kInit) asm volatile("" : "+v"(glane));
     const f32x4* tail_rows = reinterpret_cast<const f32x4*>(tail_bias) + glane;
+    const f32x4* init_rows = reinterpret_cast<const f32x4*>(init_bias) + glane;
+    f32x4 ci = init0;
 #pragma unroll
     for (int rb = 0; rb < 8; ++rb) {
         u32x4 an[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) an[q] = __builtin_bit_cast(u32x4, rb < 7 ? cur[((rb + 1) * 3 + q) * 64] : nxt[q * 64]);
         if (kMode == 1) cut_pair<kRelu>(nv[rb >> 2][2 * (rb & 3)], nv[rb >> 2][2 * (rb & 3) + 1], rb & 3, bn[rb >> 2]);
+        f32x4 cin = ci;
+        if (kInit && rb < 7) cin = init_rows[((rb + 1) >> 1) * 4 + 2 * ((rb + 1) & 1)];    // = [perm_f4(rb + 1, g)]
         if (kMode == 4 && tail_bias) {
             // the bias row of row block rb is requested here and applied one group later (an LDS round trip inside a group would
             // hold this wave's MFMAs behind the wait); row 7 is applied behind the last group
@@ -317,14 +334,14 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
 #if MVS16_F16
         // three products per block, the two small ones first: A0s B1, A1 B0, A0 B0 (a = {A0, A0s, A1}, b = {p1: B0, p3: B1})
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[1], b[cb].p3, acc[rb][cb]);
+        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[1], b[cb].p3, kInit ? ci : acc[rb][cb]);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[2], b[cb].p1, acc[rb][cb]);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[0], b[cb].p1, acc[rb][cb]);
 #else
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[2], b[cb].p1, acc[rb][cb]);
+        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[2], b[cb].p1, kInit ? ci : acc[rb][cb]);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma1632(a[1], b[cb].p2, acc[rb][cb]);
 #pragma unroll
@@ -339,7 +356,7 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
         // issue order inside the group: the first MFMA (its operands were requested one group ago), the LDS reads of the next group
         // (and the bias row), then vector instructions / MFMA alternating
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, kMode == 4 ? 4 : 3, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, (kMode == 4 || kInit) ? 4 : 3, 0);
 #pragma unroll
         for (int m = 0; m < (MVS16_F16 ? 5 : 11); ++m) {
             if (kMode == 1) __builtin_amdgcn_sched_group_barrier(0x002, MVS16_F16 ? 2 : 1, 0);
@@ -349,11 +366,15 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
         if (kMode == 1) __builtin_amdgcn_sched_group_barrier(0x002, MVS16_F16 ? 3 : 2, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (rb == 0) {   // the weight loads of two k-steps ahead
+            // behind row block 0's MFMAs, whose operands are in registers when the barrier opens (the empty asm orders them: instruction
+            // selection otherwise emits the fetch first and the wave issues no MFMA until its three requests are out)
+            asm volatile("" : "+v"(acc[0][0]), "+v"(acc[0][1]));
             ring16_fetch(ring);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int q = 0; q < 3; ++q) a[q] = an[q];
+        ci = cin;
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q) ring.a0[q] = a[q];
@@ -384,9 +405,13 @@ __device__ __forceinline__ void first_operand_s16(const f32x4 (&in)[8][2], B16 (
 // the consumed input array) needs 24 more live registers and measured 3-5 % slower (profiles/r03_ab_tail*.log).
 // tail_bias (or nullptr): during the last k-step, when every row of `in` has been cut, in[rb][cb] += / = that bias vector (32x32
 // accumulator order) - the kernels pass nullptr (kstep16, kMode 4).
-template <bool kTailAdd>
-__device__ __forceinline__ void dense128_s16_plain(Ring16& ring, int lane, int g, f32x4 (&in)[8][2], f32x4 (&acc)[8][2], const float* __restrict__ tail_bias) {
+// kInit: acc = init_bias + W^T relu(in) (acc's contents on entry are ignored; kstep16, kInit), otherwise acc += W^T relu(in).
+template <bool kTailAdd, bool kInit>
+__device__ __forceinline__ void dense128_s16_plain(Ring16& ring, int lane, int g, f32x4 (&in)[8][2], f32x4 (&acc)[8][2], const float* __restrict__ tail_bias,
+                                                   const float* __restrict__ init_bias = nullptr) {
     B16 b[2], bn[2];
+    f32x4 init0 = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (kInit) init0 = reinterpret_cast<const f32x4*>(init_bias)[perm_f4(0, g)];     // lands during the cut below
     first_operand_s16(in, b);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -395,7 +420,8 @@ __device__ __forceinline__ void dense128_s16_plain(Ring16& ring, int lane, int g
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int q = 0; q < 8; ++q) nv[cb][q] = t < 3 ? in[2 * (t + 1) + (q >> 2)][cb][q & 3] : 0.0f;
-        if (t < 3) kstep16<true, 1, false>(ring, lane, g, b, nv, bn, acc, in, nullptr);
+        if (t == 0 && kInit) kstep16<true, 1, false, true>(ring, lane, g, b, nv, bn, acc, in, nullptr, init_bias, init0);
+        else if (t < 3) kstep16<true, 1, false>(ring, lane, g, b, nv, bn, acc, in, nullptr);
         else kstep16<true, 4, kTailAdd>(ring, lane, g, b, nv, bn, acc, in, tail_bias);
         b[0] = bn[0];
         b[1] = bn[1];
@@ -405,10 +431,14 @@ __device__ __forceinline__ void dense128_s16_plain(Ring16& ring, int lane, int g
 
 template <bool kAdd>
 __device__ __forceinline__ void bias16(const float* __restrict__ bperm, int g, f32x4 (&acc)[8][2]) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(bperm);
+    // the lane's part of perm_f4 behind an empty asm, the row block as an immediate offset (as kstep16: otherwise the row addresses of
+    // every layer's bias vector are hoisted out of the tile loop into registers of their own)
+    int glane = (g & 1) * 16 + (g >> 1);
+    asm volatile("" : "+v"(glane));
+    const f32x4* p = reinterpret_cast<const f32x4*>(bperm) + glane;
 #pragma unroll
     for (int rb = 0; rb < 8; ++rb) {
-        const f32x4 v = p[perm_f4(rb, g)];
+        const f32x4 v = p[(rb >> 1) * 4 + 2 * (rb & 1)];                    // = [perm_f4(rb, g)]
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -476,29 +506,33 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 
     Ring16 ring;
     ring.w = wsplit;
-    ring.base = reinterpret_cast<f32x4*>(smem_s16);
-    ring.c = 0;
-    ring.p = 0;
+    ring.lds = smem_s16;
+    ring.cur = 0;
+    ring.nxt = kR16SlotF4 * 16;
+    ring.fill = 2 * kR16SlotF4 * 16;
     const int l0_units = kProj ? kS16L0Pe : kS16L0Pe + kS16L0Feat;
-    ring.P = (l0_units + kS16PerView) * p.V + kS16PerView;
-    for (int i = tid; i < ring.P; i += 64 * kW) table[i] = ring16_start_chunk(i, p.V, l0_units);
+    const int n_pos = (l0_units + kS16PerView) * p.V + kS16PerView;
+    for (int i = tid; i < n_pos; i += 64 * kW) table[i] = ring16_start_chunk(i, p.V, l0_units) * 1024;
     ring.table = table;
+    ring.P4 = 4 * n_pos;
+    ring.pf4 = 4 * 3;
     __syncthreads();                                                        // the position table is written
-    ring.tid = tid;
-    ring.wave = wave;
-    ring16_dma(ring, table[0], 0);                                          // prologue: positions 0 and 1 into slots 0 and 1
-    ring16_dma(ring, table[1], 1);
+    ring.lane_off = 16 * tid;
+    ring.wave_off = 1024 * wave;
+    ring16_dma(ring, __builtin_amdgcn_readfirstlane(table[0]), ring.cur);   // prologue: positions 0 and 1
+    ring16_dma(ring, __builtin_amdgcn_readfirstlane(table[1]), ring.nxt);
     ring.start_pf = table[2];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 3; ++q) ring.a0[q] = __builtin_bit_cast(u32x4, ring16_cur(ring)[q * 64 + lane]);
 
-    const long n_groups = (p.n_tiles + kW - 1) / kW;
-    for (long grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
-        long tile = grp * kW + wave;
-        const bool tile_ok = tile < p.n_tiles;
-        if (!tile_ok) tile = p.n_tiles - 1;                               // idle waves shadow the last tile, no stores
+    // (32-bit tile counts - B*R*S < 2^31 - so that the loop's compares are scalar: a 64-bit one runs on the vector ALU against a register pair)
+    const int n_tiles = (int)p.n_tiles, n_groups = (n_tiles + kW - 1) / kW;
+    for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+        const int own = grp * kW + wave;
+        const bool tile_ok = own < n_tiles;
+        const long tile = tile_ok ? own : n_tiles - 1;                    // idle waves shadow the last tile, no stores
         // Loop-invariant scalars are re-read here through an empty asm: otherwise the compiler hoists everything derived from them
         // (float copies of H - 2 and W - 2, the reciprocals of the divisions by S and R, per-lane constants of the positional
         // encoding, ...) into registers that stay live across the whole tile - next to 2 x 64 accumulators that is ~60 spilled dwords
@@ -509,22 +543,48 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
         asm volatile("" : "+s"(pS), "+s"(pR), "+s"(pH), "+s"(pW));
         asm volatile("" : "+v"(gl), "+v"(nl));
         SampleGeo sg[2];
+        // S % 32 == 0 (every shape the renderer uses): the tile lies inside one ray, so ray, scene and view are wave-uniform - scalar
+        // index arithmetic and scalar loads of the ray and of the view's matrices below.  Any other S takes the per-lane path.
+        const bool one_ray = (pS & 31) == 0;
+        if (one_ray) {
+            const unsigned first = (unsigned)tile * 32u;                     // B*R*S < 2^31 (checked by the C entry points)
+            const int ray = __builtin_amdgcn_readfirstlane((int)(first / (unsigned)pS));
+            const int b = __builtin_amdgcn_readfirstlane((int)((unsigned)ray / (unsigned)pR));
+            const int s0 = (int)first - ray * pS;
+            const cfloat* ro = (const cfloat*)(p.rays_o + 3 * ray);
+            const cfloat* rd = (const cfloat*)(p.rays_d + 3 * ray);
+            const float ox = ro[0], oy = ro[1], oz = ro[2], dx = rd[0], dy = rd[1], dz = rd[2];
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-            long gi = tile * 32 + 16 * cb + nl;
-            sg[cb].valid = tile_ok && gi < p.total;
-            if (gi >= p.total) gi = p.total - 1;
-            sg[cb].g = gi;
-            const int ray = (int)((unsigned)gi / (unsigned)pS);              // B*R*S < 2^31 (checked by the C entry points)
-            sg[cb].ray = ray;
-            sg[cb].sidx = (int)gi - ray * pS;
-            sg[cb].b = (int)((unsigned)ray / (unsigned)pR);
-            const float ox = p.rays_o[3 * ray + 0], oy = p.rays_o[3 * ray + 1], oz = p.rays_o[3 * ray + 2];
-            const float dx = p.rays_d[3 * ray + 0], dy = p.rays_d[3 * ray + 1], dz = p.rays_d[3 * ray + 2];
-            const float zz = p.z[gi];
-            sg[cb].wx = ox + zz * dx;
-            sg[cb].wy = oy + zz * dy;
-            sg[cb].wz = oz + zz * dz;
+            for (int cb = 0; cb < 2; ++cb) {
+                const long gi = (long)first + 16 * cb + nl;                  // a whole tile: gi < total
+                sg[cb].valid = tile_ok;
+                sg[cb].g = gi;
+                sg[cb].ray = ray;
+                sg[cb].sidx = s0 + 16 * cb + nl;
+                sg[cb].b = b;
+                const float zz = p.z[gi];
+                sg[cb].wx = ox + zz * dx;
+                sg[cb].wy = oy + zz * dy;
+                sg[cb].wz = oz + zz * dz;
+            }
+        } else {
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                long gi = tile * 32 + 16 * cb + nl;
+                sg[cb].valid = tile_ok && gi < p.total;
+                if (gi >= p.total) gi = p.total - 1;
+                sg[cb].g = gi;
+                const int ray = (int)((unsigned)gi / (unsigned)pS);          // B*R*S < 2^31 (checked by the C entry points)
+                sg[cb].ray = ray;
+                sg[cb].sidx = (int)gi - ray * pS;
+                sg[cb].b = (int)((unsigned)ray / (unsigned)pR);
+                const float ox = p.rays_o[3 * ray + 0], oy = p.rays_o[3 * ray + 1], oz = p.rays_o[3 * ray + 2];
+                const float dx = p.rays_d[3 * ray + 0], dy = p.rays_d[3 * ray + 1], dz = p.rays_d[3 * ray + 2];
+                const float zz = p.z[gi];
+                sg[cb].wx = ox + zz * dx;
+                sg[cb].wy = oy + zz * dy;
+                sg[cb].wz = oz + zz * dz;
+            }
         }
 
         f32x4 x[8][2], hid[8][2];
@@ -536,19 +596,46 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
         // which therefore keeps the runtime bound
         const int n_views = (kMultiView || !(kAux || kStash)) ? p.V : 1;
         for (int v = 0; v < n_views; ++v) {
+            // (fresh copies per view: whatever the front end derives from them - scene and ray offsets, float copies of H - 2 and W - 2 - is
+            // otherwise computed in front of the view loop and kept across the trunk)
+            asm volatile("" : "+s"(pS), "+s"(pR), "+s"(pH), "+s"(pW));
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) asm volatile("" : "+v"(sg[cb].b), "+v"(sg[cb].ray), "+v"(sg[cb].sidx));
             int tl[2];
             float ax[2], ay[2];
             long vrow[2];
             float pe[2][16];
+            // camera coordinates, pixel and the layer-0 accumulator seed = b0 + W0_dir^T PE(cam dir) of the sample's (view, ray)
+            // (dir_bias_kernel, 32x32 accumulator order).  One ray per tile: the view's two matrices through scalar loads, one seed row
+            // for both column blocks; the arithmetic per sample is the same in both paths.
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
                 const int bv = sg[cb].b * p.V + v;
-                const float* E = p.einv + 16 * bv;
-                float cam[4];
+                float cam[4], pxl, pyl;
+                const f32x4* seed;
+                if (one_ray) {
+                    const int bu = __builtin_amdgcn_readfirstlane(sg[0].b), bvu = bu * p.V + v;
+                    const int rayu = __builtin_amdgcn_readfirstlane(sg[0].ray);
+                    const cfloat* Ec = (const cfloat*)(p.einv + 16 * bvu);
+                    const cfloat* Kc = (const cfloat*)(p.k4 + 16 * bvu);
+                    float E[16], K[12];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) cam[r] = row_dot4(E, r, sg[cb].wx, sg[cb].wy, sg[cb].wz, 1.0f);
-                float pxl, pyl;
-                pixel_from_cam(p.k4 + 16 * bv, cam, &pxl, &pyl);
+                    for (int i = 0; i < 16; ++i) E[i] = Ec[i];
+#pragma unroll
+                    for (int i = 0; i < 12; ++i) K[i] = Kc[i];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) cam[r] = row_dot4(E, r, sg[cb].wx, sg[cb].wy, sg[cb].wz, 1.0f);
+                    pixel_from_cam(K, cam, &pxl, &pyl);
+                    seed = reinterpret_cast<const f32x4*>(p.dir_bias + 128 * ((long)bvu * pR + (rayu - bu * pR)));
+                } else {
+                    const float* E = p.einv + 16 * bv;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) cam[r] = row_dot4(E, r, sg[cb].wx, sg[cb].wy, sg[cb].wz, 1.0f);
+                    pixel_from_cam(p.k4 + 16 * bv, cam, &pxl, &pyl);
+                    seed = reinterpret_cast<const f32x4*>(p.dir_bias + 128 * ((long)bv * pR + (sg[cb].ray - sg[cb].b * pR)));
+                }
+#pragma unroll
+                for (int rb = 0; rb < 8; ++rb) x[rb][cb] = seed[perm_f4(rb, gl)];
                 const Taps tp = bilinear_taps(pxl, pyl, pH, pW);
                 tl[cb] = (bv * pH + tp.y0) * pW + tp.x0;
                 ax[cb] = tp.ax;
@@ -563,12 +650,6 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
                         p.pix[2 * vrow[cb] + 0] = pxl;
                         p.pix[2 * vrow[cb] + 1] = pyl;
                     }
-                }
-                // accumulator seed = b0 + W0_dir^T PE(cam dir) of this (view, ray) (dir_bias_kernel, 32x32 accumulator order)
-                {
-                    const f32x4* seed = reinterpret_cast<const f32x4*>(p.dir_bias + 128 * ((long)bv * pR + (sg[cb].ray - sg[cb].b * pR)));
-#pragma unroll
-                    for (int rb = 0; rb < 8; ++rb) x[rb][cb] = seed[perm_f4(rb, gl)];
                 }
                 // this lane group's 16 of the 64 layer-0 inputs PE(cam xyz) | rgb of the sample (slot order: s16_pe_row).
                 // g < 3: dimension g, octaves 0..7 - accurate sin/cos at octaves 0 and 5, double-angle steps in between
@@ -733,15 +814,13 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
             };
             if (kAux && p.acts_view) store_acc16(p.acts_view, vrow);
             // ---- 24 k-steps: the three per-view ResNet blocks: hid = b1 + W1^T relu(x), x += b2 + W2^T relu(hid) ----
-            bias16<false>(net + kPackBHidden, g, hid);
 #pragma unroll 1
             for (int bi = 0; bi < 3; ++bi) {
                 const float* bias1 = net + kPackBHidden + 256 * bi;
-                if (bi > 0) bias16<false>(bias1, g, hid);
-                dense128_s16_plain<true>(ring, lane, g, x, hid, nullptr);
+                dense128_s16_plain<true, true>(ring, lane, g, x, hid, nullptr, bias1);
                 if (kStash && tile_ok) store_tl16(p.stash + (1 + 2 * bi) * p.stash_stride, vtile, n, g, hid);
                 bias16<true>(bias1 + 128, g, x);
-                dense128_s16_plain<false>(ring, lane, g, hid, x, nullptr);
+                dense128_s16_plain<false, false>(ring, lane, g, hid, x, nullptr);
                 // (per-view slot 6 = x3 is not written: nothing reads it, as in field_eval_split_kernel)
                 if (kStash && tile_ok && bi < 2) store_tl16(p.stash + (2 + 2 * bi) * p.stash_stride, vtile, n, g, x);
                 if (kAux && p.acts_view) store_acc16(p.acts_view + (bi + 1) * vslot, vrow);
@@ -789,11 +868,10 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 #pragma unroll 1
         for (int bi = 3; bi < 6; ++bi) {
             const float* bias1 = net + kPackBHidden + 256 * bi;
-            bias16<false>(bias1, g, hid);
-            dense128_s16_plain<true>(ring, lane, g, x, hid, nullptr);
+            dense128_s16_plain<true, true>(ring, lane, g, x, hid, nullptr, bias1);
             if (kStash && tile_ok) store_tl16(p.stash_fused + (1 + 2 * (bi - 3)) * p.stash_fused_stride, tile, n, g, hid);
             bias16<true>(bias1 + 128, g, x);
-            dense128_s16_plain<false>(ring, lane, g, hid, x, nullptr);
+            dense128_s16_plain<false, false>(ring, lane, g, hid, x, nullptr);
             if (kStash && tile_ok) store_tl16(p.stash_fused + (2 + 2 * (bi - 3)) * p.stash_fused_stride, tile, n, g, x);
             if (kAux && p.acts_fused) store_fused16(p.acts_fused + (long)(bi - 2) * p.total * 128);
         }
