@@ -877,7 +877,10 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
         const float dn = __shfl_down(incl_s, off);
         if (lane + off < 64) incl_s = incl_s + dn;
     }
-    float suffix = incl_s - lane_sum;                 // sum over later lanes
+    // sum over later lanes = the next lane's inclusive sum.  Not incl_s - lane_sum: behind a nearly opaque sample the later terms are
+    // t_i times smaller than this lane's own, the difference keeps none of their digits, and suffix / t_i is divided by that t_i.
+    float suffix = __shfl_down(incl_s, 1);
+    if (lane == 63) suffix = 0.0f;
     float dd[P];                                      // dL/d delta_i
 #pragma unroll
     for (int q = P - 1; q >= 0; --q) {
