@@ -436,6 +436,38 @@ int mvnerf_grasp_tail_fwd(const float* x, const float* packed, long M, int n5, f
 int mvnerf_grasp_tail_vjp(const float* x, const float* g_s, const float* stash, const float* packed, long M, int n5, float* g_x,
                           mvnerf_stream_t stream);
 
+/* The same part with TRAINABLE weights: what LanguageNeRF.train_step differentiates (lmvnerf/model_v4.py:277-322: the first backward, and the
+ * derivative of the first backward that the nested GradientTape takes).  E = elu, E'(v) = v > 0 ? 1 : e^v, E''(v) = v > 0 ? 0 : e^v,
+ * H = [x2 > 0]; x, stash, packed as for mvnerf_grasp_tail_vjp; every (M, .) buffer row-major and 16-byte aligned (g_s, out_gs: 4); rows
+ * past M are neither read into results nor written; no sums across workgroups, so the same bits from run to run.  Any M >= 1, n5 >= 1.
+ *
+ * mvnerf_grasp_tail_vjp_train: g_s (M) or NULL (ones) ->
+ *     g_x (M, K)    the same bits mvnerf_grasp_tail_vjp writes for the same inputs,
+ *     cot (M, 320)  = [g_h0 (128) | g_x1 (64) | g_h1 (64) | g_x2 (64)], the cotangents of the stashed pre-activations,
+ *     act (M, 320)  = [E(h0) | E(x1) | E(h1) | g_s relu(x2)],
+ *     ex  (M, K)    = E(x).
+ * The weight gradients are skinny TN products of these buffers, formed by the caller (mvnerf_gemm_tn_batched takes the column blocks in place):
+ *     dW0 = g_h0^T ex, db0 = sum g_h0;  dW1 = g_x1^T E(h0), db1 = sum g_x1;  dWs = g_x1^T x;  dW0' = g_h1^T E(x1), db0' = sum g_h1;
+ *     dW1' = g_x2^T E(h1), db1' = sum g_x2;  dw_out = sum_m g_s relu(x2);  db_out = sum g_s. */
+int mvnerf_grasp_tail_vjp_train(const float* x, const float* g_s, const float* stash, const float* packed, long M, int n5, float* g_x, float* cot,
+                                float* act, float* ex, mvnerf_stream_t stream);
+/* The derivative of mvnerf_grasp_tail_vjp_train: t_x (M, K) = dL/d(g_x) -> the gradient of phi = <t_x, g_x>; cot as written by
+ * mvnerf_grasp_tail_vjp_train for the same x, g_s, stash, packed.  Tangents  da0 = E'(x) . t;  dh0 = da0 W0^T;  de0 = E'(h0) . dh0;
+ * dx1 = t Ws^T + de0 W1^T;  da1 = E'(x1) . dx1;  dh1 = da1 W0'^T;  de1 = E'(h1) . dh1;  dx2 = dx1 + de1 W1'^T,  and second-order cotangents
+ *     pi_h1 = E''(h1) . dh1 . (g_x2 W1');  pi_x1 = E'(x1) . (pi_h1 W0') + E''(x1) . dx1 . (g_h1 W0');
+ *     pi_h0 = E'(h0) . (pi_x1 W1) + E''(h0) . dh0 . (g_x1 W1).
+ * Outputs:
+ *     out_gs (M)      = dphi/dg_s = (H . dx2) . w_out,
+ *     out_x  (M, K)   = dphi/dx = E'(x) . (pi_h0 W0) + E''(x) . t . (g_h0 W0) + pi_x1 Ws;  NULL: not formed (one launch instead of two),
+ *     cot2   (M, 256) = [pi_h0 (128) | pi_x1 (64) | pi_h1 (64)],
+ *     tan    (M, 320) = [de0 (128) | da1 (64) | de1 (64) | g_s H . dx2 (64)],
+ *     dex    (M, K)   = da0.
+ * Weight gradients of phi, each the sum of two TN products (the g2 / a2 form of mvnerf_gemm_tn_batched):
+ *     ddW0 = g_h0^T da0 + pi_h0^T E(x), ddb0 = sum pi_h0;  ddW1 = g_x1^T de0 + pi_x1^T E(h0), ddb1 = sum pi_x1;  ddWs = g_x1^T t + pi_x1^T x;
+ *     ddW0' = g_h1^T da1 + pi_h1^T E(x1), ddb0' = sum pi_h1;  ddW1' = g_x2^T de1;  ddw_out = sum_m g_s H . dx2;  ddb1' = ddb_out = 0. */
+int mvnerf_grasp_tail_vjp_bwd(const float* x, const float* t_x, const float* g_s, const float* stash, const float* cot, const float* packed, long M,
+                              int n5, float* out_gs, float* out_x, float* cot2, float* tan, float* dex, mvnerf_stream_t stream);
+
 /* ---- the grasp-pose optimiser (DNGFOptimizer, lmvnerf/grasp_optimizer.py:28-184; its loop, utils/optimization.py:40-152): the pose side
  * of one optimisation step.  P poses: t (P, 3), rot (P, 4) quaternion (x, y, z, w; rep 0) or (P, 6) 6d ([r1 | r2]; rep 1); offsets (n5, 4, 4)
  * = LanguageNeRF.transforms_to_check (model_v4.py:67-101).  The query tensors hold B scenes of `ld` rows (ld >= P * n5, padding rows are

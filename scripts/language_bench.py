@@ -6,9 +6,12 @@ B scenes x (n_points x 42 offsets) query points, V source views of HxW, fp32.  R
   forward+stash    what TrunkField.forward runs
   vjp              mvnerf_query_vjp (12 dX launches + layer-0 input gradient)
   jvp              mvnerf_query_jvp (fused primal + tangent pass)
-  train_step       LanguageNeRF.train_step: 2 forwards, VJP, JVP, GraspReadout fwd/bwd/double-bwd in torch, Adam
+  train_step       LanguageNeRF.train_step: 2 forwards, VJP, JVP, GraspReadout fwd/bwd/double-bwd (per-point layers fused in HIP; per-pose
+                   layers through torch + gemm_ops, or fused in HIP with fused_tail), pose algebra and losses in torch, Adam
   train_step (HIP graph)  the same step after compile(graph=True): one graph replay
-Usage: python scripts/language_bench.py [--batch 8] [--points 192] [--size 480 640] [--views 1] [--steps 10]"""
+--fused-tail times the train step with GraspReadout.fused_tail off (today's path) and on, the legs alternating --repeats times, and prints
+the median and the range of each leg.
+Usage: python scripts/language_bench.py [--batch 8] [--points 192] [--size 480 640] [--views 1] [--steps 10] [--fused-tail [both|on|off] [--repeats 3]]"""
 import argparse
 import os
 import sys
@@ -30,6 +33,9 @@ ap.add_argument('--views', type=int, default=1)
 ap.add_argument('--steps', type=int, default=10)
 ap.add_argument('--only-train', action='store_true', help='time the train step only (for kernel traces)')
 ap.add_argument('--train-mode', choices=['both', 'eager', 'graph'], default='both', help='which train_step legs to run')
+ap.add_argument('--fused-tail', nargs='?', const='both', choices=['both', 'on', 'off'], default=None,
+                help='time the train step only, with GraspReadout.fused_tail off and on (alternating), or one of the two (for kernel traces)')
+ap.add_argument('--repeats', type=int, default=3, help='with --fused-tail: how often each leg is timed (for the spread)')
 args = ap.parse_args()
 dev = 'cuda:0'
 h, w = args.size
@@ -81,26 +87,53 @@ def timed(fn, steps=args.steps):
 
 z0 = torch.zeros(b, points.shape[1], 1, device=dev)
 packed16 = ops.pack_net_bf16(model.trunk_net)
-res = ({'train_step': timed(lambda: model.train_step((inputs, labels), feats), max(2, args.steps // 2))} if args.train_mode != 'graph' else {}) if args.only_train else {
+eager_steps, graph_steps = max(2, args.steps // 2), max(4, args.steps)
+
+
+def graph_model(fused_tail=None):
+    """The same step captured as one HIP graph (compile(graph=True)): device-resident inputs bound as the graph's buffers; the two eager steps
+    and the capture itself stay outside the timed region."""
+    gm = LanguageNeRF(sc['fine'], n_points_train=npts, n_views=args.views, batch_size=b, rotation_representation='6d',
+                      softmax_before_loss=True, device=dev)
+    gm.compile(graph=True, fused_tail=fused_tail)
+    dv = lambda a: torch.from_numpy(a).to(dev)
+    data = ((dv(t1), dv(r1), dv(t2), dv(r2), images, k4, einv), tuple(dv(l) for l in labels))
+    gm.bind_graph_inputs(data, feats)
+    for _ in range(3):
+        gm.train_step(data, feats)
+    return gm, data
+
+
+if args.fused_tail:
+    legs, graphs = {}, {}
+    for _ in range(args.repeats):
+        for fused in {'both': (False, True), 'on': (True,), 'off': (False,)}[args.fused_tail]:
+            if args.train_mode != 'graph':
+                model.compile(fused_tail=fused)
+                legs.setdefault(f'train_step, fused_tail={fused}', []).append(timed(lambda: model.train_step((inputs, labels), feats), eager_steps))
+            if args.train_mode != 'eager':
+                if fused not in graphs:
+                    graphs[fused] = graph_model(fused)
+                gm, data = graphs[fused]
+                legs.setdefault(f'train_step (HIP graph), fused_tail={fused}', []).append(timed(lambda: gm.train_step(data, feats), graph_steps))
+    print(f'B={b} scenes x {points.shape[1]} query points ({npts} poses x 42 offsets), V={args.views}, {h}x{w}; per leg {args.repeats} timings of '
+          f'{eager_steps} (eager) / {graph_steps} (graph) steps, alternating')
+    for k, ts in sorted(legs.items()):
+        ts = sorted(ts)
+        print(f'  {k:44s} median {ts[len(ts) // 2] * 1e3:8.3f} ms   min {ts[0] * 1e3:8.3f}   max {ts[-1] * 1e3:8.3f}')
+    sys.exit(0)
+
+res = ({'train_step': timed(lambda: model.train_step((inputs, labels), feats), eager_steps)} if args.train_mode != 'graph' else {}) if args.only_train else {
     'forward bf16': timed(lambda: ops.field_eval_bf16(points, dirs, z0, *geo, state.packed, packed16, return_fused_acts=True)),
     'forward': timed(lambda: ops.query_field(points, dirs, *geo, state.packed, complete_output=True)),
     'forward+stash': timed(lambda: ops.query_stash(points, dirs, *geo, state.packed, stash)),
     'vjp': timed(lambda: ops.query_vjp(points, dirs, *geo, state.bwd_streams, stash, g_acts)),
     'jvp': timed(lambda: ops.query_jvp(points, dirs, tp, td, *geo, state.packed)),
-    'train_step': timed(lambda: model.train_step((inputs, labels), feats), max(2, args.steps // 2)),
+    'train_step': timed(lambda: model.train_step((inputs, labels), feats), eager_steps),
 }
-# the same step captured as one HIP graph (compile(graph=True)): device-resident inputs bound as the graph's buffers
 if args.train_mode != 'eager':
-    gmodel = LanguageNeRF(sc['fine'], n_points_train=npts, n_views=args.views, batch_size=b, rotation_representation='6d',
-                          softmax_before_loss=True, device=dev)
-    gmodel.compile(graph=True)
-    dv = lambda a: torch.from_numpy(a).to(dev)
-    g_inputs = (dv(t1), dv(r1), dv(t2), dv(r2), images, k4, einv)
-    g_labels = tuple(dv(l) for l in labels)
-    gmodel.bind_graph_inputs((g_inputs, g_labels), feats)
-    for _ in range(3):                                   # two eager steps and the capture itself stay outside the timed region
-        gmodel.train_step((g_inputs, g_labels), feats)
-    res['train_step (HIP graph)'] = timed(lambda: gmodel.train_step((g_inputs, g_labels), feats), max(4, args.steps))
+    gmodel, (g_inputs, g_labels) = graph_model()
+    res['train_step (HIP graph)'] = timed(lambda: gmodel.train_step((g_inputs, g_labels), feats), graph_steps)
 print(f'cfg3 shape: B={b} scenes x {points.shape[1]} query points ({npts} poses x 42 offsets), V={args.views}, {h}x{w}x256 fp32 features '
       f'({feats.numel() * 4 / 1e9:.2f} GB), {n_q} points per pass')
 for k, dt in res.items():

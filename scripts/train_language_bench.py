@@ -2,7 +2,9 @@
 4096 guesses on 3 images, 16 + 16 optimisation steps): ms per training step (eager and one graph replay, batches assembled on the
 device beforehand), ms per device batch, seconds per validation sample.  One JSON line.
 
-    python scripts/train_language_bench.py [--size 480x640] [--steps 10]
+    python scripts/train_language_bench.py [--size 480x640] [--steps 10] [--fused-tail]
+
+--fused-tail adds the training legs with GraspReadout.fused_tail on (train_step_ms_*_fused_tail, loss_*_fused_tail) after today's legs.
 """
 import argparse
 import json
@@ -26,6 +28,7 @@ def main():
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--guesses', type=int, default=4096)
+    ap.add_argument('--fused-tail', action='store_true', help='also time the training step with compile(fused_tail=True)')
     args = ap.parse_args()
     h, w = T._size(args.size)
     dev = 'cuda:0'
@@ -43,11 +46,11 @@ def main():
     torch.cuda.synchronize()
     batch_ms = (time.time() - t0) / len(batches) * 1e3
     out = {'size': [h, w], 'batch': args.batch, 'poses_per_scene': 192, 'setup_s': round(setup_s, 1), 'device_batch_ms': round(batch_ms, 2)}
-    for graph in (False, True):
+    for graph, fused in [(False, False), (True, False)] + ([(False, True), (True, True)] if args.fused_tail else []):
         torch.manual_seed(0)
         model = LanguageNeRF(glorot_net(np.random.default_rng(0), bias_scale=0.05), n_points_train=192, n_views=1, batch_size=args.batch,
                              rotation_representation='6d', softmax_before_loss=True, device=dev)
-        model.compile(loss=kl_divergence, graph=graph)
+        model.compile(loss=kl_divergence, graph=graph, fused_tail=fused)
         for (inputs, feats), labels in batches[:3]:
             model.train_step((inputs, labels), feats)
         torch.cuda.synchronize()
@@ -55,9 +58,11 @@ def main():
         for (inputs, feats), labels in batches[3:]:
             res = model.train_step((inputs, labels), feats)
         torch.cuda.synchronize()
-        out[f'train_step_ms_{"graph" if graph else "eager"}'] = round((time.time() - t0) / args.steps * 1e3, 2)
-        out[f'loss_{"graph" if graph else "eager"}'] = float(res['landscape_loss'] + res['grad_loss_t'] + res['grad_loss_r'])
+        leg = ('graph' if graph else 'eager') + ('_fused_tail' if fused else '')
+        out[f'train_step_ms_{leg}'] = round((time.time() - t0) / args.steps * 1e3, 2)
+        out[f'loss_{leg}'] = float(res['landscape_loss'] + res['grad_loss_t'] + res['grad_loss_r'])
     del batches
+    model.set_fused_tail(False)                                                               # validation as today
     data = T.get_inputs(valid, 0, 3, device=dev)
     config = dict(n_optimization_steps=16, init_lr_t=0.05, init_lr_r=0.05, decay_t=0.9, decay_r=0.09)
     for graph in (False, True):

@@ -131,6 +131,8 @@ SIGNATURES = {
     'mvnerf_grasp_tail_pack': (c_int, [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
     'mvnerf_grasp_tail_fwd': (c_int, [c_void_p] * 2 + [c_long, c_int] + [c_void_p] * 3),
     'mvnerf_grasp_tail_vjp': (c_int, [c_void_p] * 4 + [c_long, c_int] + [c_void_p] * 2),
+    'mvnerf_grasp_tail_vjp_train': (c_int, [c_void_p] * 4 + [c_long, c_int] + [c_void_p] * 5),
+    'mvnerf_grasp_tail_vjp_bwd': (c_int, [c_void_p] * 6 + [c_long, c_int] + [c_void_p] * 6),
     'mvnerf_pose_query_points': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
     'mvnerf_pose_query_vjp': (c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_long, c_float, c_void_p, c_void_p, c_void_p]),
     'mvnerf_pose_adam_step': (c_int, [ctypes.POINTER(PoseAdamConfig), c_int, c_int] + [c_void_p] * 11),

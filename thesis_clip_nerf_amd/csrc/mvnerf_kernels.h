@@ -92,6 +92,11 @@ size_t grasp_tail_stash_floats();
 hipError_t launch_grasp_tail_pack(const float* const* w, int n5, float* packed, hipStream_t st);
 hipError_t launch_grasp_tail_fwd(const float* x, const float* packed, long M, int n5, float* success, float* stash, hipStream_t st);
 hipError_t launch_grasp_tail_vjp(const float* x, const float* g_s, const float* stash, const float* packed, long M, int n5, float* g_x, hipStream_t st);
+// grasp_tail_train.hip: the same part with trainable weights (the VJP with the buffers its weight gradients are made of, and its derivative)
+hipError_t launch_grasp_tail_vjp_train(const float* x, const float* g_s, const float* stash, const float* packed, long M, int n5, float* g_x,
+                                       float* cot, float* act, float* ex, hipStream_t st);
+hipError_t launch_grasp_tail_vjp_bwd(const float* x, const float* t_x, const float* g_s, const float* stash, const float* cot, const float* packed,
+                                     long M, int n5, float* out_gs, float* out_x, float* cot2, float* tan, float* dex, hipStream_t st);
 
 hipError_t launch_get_rays(const double* m9, const double* origin3, const float* u, const float* v, int n_rays,
                            int width, int normalize, float* rays_o, float* rays_d, double* rays_d64,

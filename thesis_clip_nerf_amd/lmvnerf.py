@@ -7,8 +7,10 @@ with a loss on the prediction and a loss on d prediction / d pose (nested Gradie
 * the trunk is `TrunkField`: forward = `mvnerf_field_eval_stash` on the query points (activations read back from the
   stash), backward = `mvnerf_query_vjp`, and the backward of THAT backward w.r.t. its cotangent = `mvnerf_query_jvp`
   (the trunk is linear in nothing but the cotangent, so the double-backward the second tape needs is a JVP);
-* `GraspReadout`, the pose algebra and the losses are ordinary torch (small, and torch's autograd supplies their
-  double-backward); the CLIP / ViT / conv encoders are outside the hot path: `combined_features` is an input.
+* `GraspReadout`'s per-point layers are fused HIP passes (`_HeadFn`, csrc/grasp_head.hip) and so, with `fused_tail`, are its
+  per-pose blocks (`_TailFn`, csrc/grasp_tail.hip + grasp_tail_train.hip; off by default: torch + gemm_ops); the pose algebra
+  and the losses are ordinary torch (small, and torch's autograd supplies their double-backward); the CLIP / ViT / conv
+  encoders are outside the hot path: `combined_features` is an input.
 
 Names and argument meaning follow the reference (`_call`, `compute_matrices`, `set_pose`, `train_step`, `infer`).
 """
@@ -257,6 +259,94 @@ class _HeadFn(torch.autograd.Function):
         return _HeadVJP.apply(g_y, acts, c, y, w4, b4, wc, bc, packed)
 
 
+# ---- the per-pose part of the read-out as fused HIP passes (csrc/grasp_tail.hip, csrc/grasp_tail_train.hip) ---------------------------
+def _tn1(g, a, g2=None, a2=None, colsum_of=0):
+    """One weight gradient g^T a (+ g2^T a2) [and the column sums of g / g2] on mvnerf_gemm_tn_batched: the operands may be column blocks
+    of the kernels' (M, 320) / (M, 256) buffers, read where they lie."""
+    r = ops.gemm_tn_batched(g[None], a[None], g2=None if g2 is None else g2[None], a2=None if a2 is None else a2[None], colsum_of=colsum_of)
+    return (r[0][0], r[1][0]) if colsum_of else r[0]
+
+
+def _pair(x, lo):
+    """Columns lo .. lo + 128 of x (M, F) as a (2, M, 64) view: the two 64 x 64 layers of block_1 as one batch of two."""
+    return x[:, lo:lo + 128].unflatten(1, (2, 64)).permute(1, 0, 2)
+
+
+class _TailVJP(torch.autograd.Function):
+    """The vector-Jacobian product of the fused tail as a differentiable function of its cotangent, of x and of the weights: forward =
+    mvnerf_grasp_tail_vjp_train (+ the weight gradients as skinny TN products of its buffers), backward = mvnerf_grasp_tail_vjp_bwd - what
+    the nested tape of LanguageNeRF.train_step needs (model_v4.py:290-322).  Unlike the head's, the input's cotangent is returned: x is
+    the head's output and the head is trained.  Cotangents on the weight-gradient outputs are refused."""
+
+    @staticmethod
+    def forward(ctx, g_s, x, stash, packed, w0, b0, w1, b1, ws, w0b, b0b, w1b, b1b, w_out, b_out):
+        g_s = g_s.contiguous()
+        g_x, cot, act, ex = ops.grasp_tail_vjp_train(x, stash, packed, g_s=g_s)
+        if _batched_ok(cot):
+            d_w0, d_b0 = _tn1(cot[:, :128], ex, colsum_of=1)
+            d_ws, d_b1 = _tn1(cot[:, 128:192], x, colsum_of=1)
+            d_w1 = _tn1(cot[:, 128:192], act[:, :128])
+            (d_w0b, d_w1b), (d_b0b, d_b1b) = ops.gemm_tn_batched(_pair(cot, 192), _pair(act, 128), colsum_of=1)
+        else:
+            g_h0, g_x1, g_h1, g_x2 = cot[:, :128], cot[:, 128:192], cot[:, 192:256], cot[:, 256:]
+            d_w0, d_ws, d_w1 = _gtn(g_h0, ex), _gtn(g_x1, x), _gtn(g_x1, act[:, :128])
+            d_w0b, d_w1b = _gtn(g_h1, act[:, 128:192]), _gtn(g_x2, act[:, 192:256])
+            d_b0, d_b1, d_b0b, d_b1b = cot.sum(0).split([128, 64, 64, 64])
+        d_wout = act[:, 256:].sum(0).reshape(w_out.shape)
+        d_bout = g_s.sum().reshape(1) if b_out is not None else None
+        ctx.save_for_backward(g_s, x, stash, packed, cot, act, ex)
+        ctx.wout_shape = w_out.shape
+        ctx.set_materialize_grads(False)
+        return g_x, d_w0, d_b0, d_w1, d_b1, d_ws, d_w0b, d_b0b, d_w1b, d_b1b, d_wout, d_bout
+
+    @staticmethod
+    def backward(ctx, t_x, *weight_cotangents):
+        if any(t is not None for t in weight_cotangents):
+            raise NotImplementedError('_TailVJP: derivatives of the weight gradients are not built (LanguageNeRF.train_step does not take them)')
+        if t_x is None:
+            return (None,) * 15
+        g_s, x, stash, packed, cot, act, ex = ctx.saved_tensors
+        t_x = t_x.contiguous()
+        out_gs, out_x, cot2, tan, dex = ops.grasp_tail_vjp_bwd(x, t_x, stash, cot, packed, g_s=g_s, want_x=ctx.needs_input_grad[1])
+        g_h0, g_x1, g_h1, g_x2 = cot[:, :128], cot[:, 128:192], cot[:, 192:256], cot[:, 256:]
+        p_h0, p_x1, p_h1 = cot2[:, :128], cot2[:, 128:192], cot2[:, 192:]
+        if _batched_ok(cot):
+            d_w0, d_b0 = _tn1(g_h0, dex, p_h0, ex, colsum_of=2)
+            d_ws, d_b1 = _tn1(g_x1, t_x, p_x1, x, colsum_of=2)
+            d_w1 = _tn1(g_x1, tan[:, :128], p_x1, act[:, :128])
+            d_w0b, d_b0b = _tn1(g_h1, tan[:, 128:192], p_h1, act[:, 128:192], colsum_of=2)
+            d_w1b = _tn1(g_x2, tan[:, 192:256])
+        else:
+            d_w0 = _gtn(g_h0, dex) + _gtn(p_h0, ex)
+            d_ws = _gtn(g_x1, t_x) + _gtn(p_x1, x)
+            d_w1 = _gtn(g_x1, tan[:, :128]) + _gtn(p_x1, act[:, :128])
+            d_w0b = _gtn(g_h1, tan[:, 128:192]) + _gtn(p_h1, act[:, 128:192])
+            d_w1b = _gtn(g_x2, tan[:, 192:256])
+            d_b0, d_b1, d_b0b = cot2.sum(0).split([128, 64, 64])
+        d_wout = tan[:, 256:].sum(0).reshape(ctx.wout_shape)
+        # b1' and b_out enter the first backward through the relu's mask only: their second-order gradients are identically zero (None)
+        return out_gs, out_x, None, None, d_w0, d_b0, d_w1, d_b1, d_ws, d_w0b, d_b0b, d_w1b, None, d_wout, None
+
+
+class _TailFn(torch.autograd.Function):
+    """x (M, 64 n5) -> success (M,): Dense(64 n5 -> 128) + elu, the two elu ResNet blocks and relu-Dense(64 -> 1) in ONE launch
+    (mvnerf_grasp_tail_fwd on the weights packed by mvnerf_grasp_tail_pack); its backward is _TailVJP, itself differentiable."""
+
+    @staticmethod
+    def forward(ctx, x2d, w0, b0, w1, b1, ws, w0b, b0b, w1b, b1b, w_out, b_out):
+        x2d, w0, b0, w1, b1, ws, w0b, b0b, w1b, b1b, w_out = (t.contiguous() for t in (x2d, w0, b0, w1, b1, ws, w0b, b0b, w1b, b1b, w_out))
+        packed = ops.grasp_tail_pack((w0, b0, w1, b1, ws), (w0b, b0b, w1b, b1b), (w_out, b_out))
+        if not any(ctx.needs_input_grad):                  # no gradient can be asked for: the value only, no stash
+            return ops.grasp_tail_fwd(x2d, packed, stash=False)
+        s, stash = ops.grasp_tail_fwd(x2d, packed)
+        ctx.save_for_backward(x2d, stash, packed, w0, b0, w1, b1, ws, w0b, b0b, w1b, b1b, w_out, b_out)
+        return s
+
+    @staticmethod
+    def backward(ctx, g_s):
+        return _TailVJP.apply(g_s, *ctx.saved_tensors)
+
+
 def _he_normal_(w):
     fan_in = w.shape[1]
     nn.init.trunc_normal_(w, std=math.sqrt(2.0 / fan_in) / 0.87962566103423978, a=-2 * math.sqrt(2.0 / fan_in) / 0.87962566103423978,
@@ -299,6 +389,7 @@ class GraspReadout(nn.Module):
             nn.init.zeros_(self.output_layer.bias)
 
     fused_head = True      # the per-point layers as fused HIP passes (csrc/grasp_head.hip); False: Linear by Linear (torch + gemm_ops)
+    fused_tail = False     # the per-pose layers as fused HIP passes (csrc/grasp_tail.hip, grasp_tail_train.hip); False: torch + gemm_ops
 
     def forward(self, acts):
         """acts: 4 x (B, np, n5, 128), or the same stacked as one (4, B, np, n5, 128) tensor -> (B, np)."""
@@ -316,6 +407,16 @@ class GraspReadout(nn.Module):
             ds = [nn.functional.elu(_wide_linear(lin, a)) for lin, a in zip(self.activation_downscale, acts)]
             x = nn.functional.elu(_wide_linear(self.combined_activation_downscale, torch.cat(ds, -1)))
             x = x.reshape(x.shape[0], x.shape[1], -1)                            # 'b np n5 d -> b np (n5 d)'
+        if self.fused_tail and x.is_cuda and x.dtype == torch.float32:
+            b0, b1, out = self.block_0, self.block_1, self.output_layer
+            weights = (b0.layer_0.weight, b0.layer_0.bias, b0.layer_1.weight, b0.layer_1.bias, b0.shortcut.weight, b1.layer_0.weight,
+                       b1.layer_0.bias, b1.layer_1.weight, b1.layer_1.bias, out.weight, out.bias)
+            x2d = x.reshape(-1, x.shape[-1])
+            if torch.is_grad_enabled():
+                return _TailFn.apply(x2d, *weights).reshape(x.shape[:-1])
+            packed = ops.grasp_tail_pack(*(tuple(t.detach().contiguous() for t in w) for w in (weights[:5], weights[5:9])),
+                                         (out.weight.detach().contiguous(), None if out.bias is None else out.bias.detach()))
+            return ops.grasp_tail_fwd(x2d.contiguous(), packed, stash=False).reshape(x.shape[:-1])
         x = self.block_1(self.block_0(x))
         return self.output_layer(torch.relu(x))[..., 0]
 
@@ -453,19 +554,32 @@ class LanguageNeRF(nn.Module):
         self.to(self.device_)
 
     # -- reference API --
-    def compile(self, optimizer=None, loss=None, learning_rate=1e-4, graph=False):
+    def compile(self, optimizer=None, loss=None, learning_rate=1e-4, graph=False, fused_tail=None):
         """graph=True: `train_step` is captured ONCE as a HIP graph (torch.cuda.CUDAGraph) and replayed: the step is ~740 launches of
         3-500 us that the host cannot issue as fast as the GPU runs them - 6.6 ms per replay against 8-10.7 ms eager at the cfg3 shape
         (profiles/r02_language_step_graph.md).  The graph fixes shapes and addresses:
         inputs are staged into the buffers `graph_inputs()` returns (a producer that writes `combined_features` there in place skips the
         copy), the optimizer is this method's own Adam (capturable).  The first two steps run eagerly (they load every kernel and size
-        the allocator pools), the third is captured."""
+        the allocator pools), the third is captured.
+        fused_tail: True / False runs the read-out's per-pose layers as fused HIP passes (GraspReadout.fused_tail) or layer by layer through
+        torch; None keeps the current setting.  A captured graph is dropped either way (compile() always starts a new one)."""
+        if fused_tail is not None:
+            self.set_fused_tail(fused_tail)
         if graph and optimizer is not None:
             raise ValueError('graph=True builds its own capturable Adam; pass learning_rate instead of an optimizer')
         self.optimizer = optimizer or torch.optim.Adam(self.grasp_readout.parameters(), lr=learning_rate, eps=1e-7, capturable=bool(graph))
         if loss is not None:
             self.loss = loss
         self._graph_mode, self._graph, self._g_static, self._g_out, self._g_calls = bool(graph), None, None, None, 0
+
+    def set_fused_tail(self, fused_tail):
+        """GraspReadout.fused_tail on this model's read-out without touching the optimizer; a change drops a captured step (the next
+        train_step runs its two eager steps and captures again)."""
+        if not isinstance(fused_tail, bool):
+            raise ValueError(f'fused_tail must be True or False (compile: or None to keep the setting), got {fused_tail!r}')
+        if fused_tail != self.grasp_readout.fused_tail:
+            self.grasp_readout.fused_tail = fused_tail
+            self._graph, self._g_out, self._g_calls = None, None, 0
 
     # -- checkpoints (model_v4.py:132-174): torch.save'd tensors, one file per sub-model, load() -> False when a file is missing --
     # The reference also writes and reads `{path}_visual_features` / `{path}_combine_clip_visual`; here the feature map is an input

@@ -715,6 +715,60 @@ def grasp_tail_vjp(x, stash, packed, g_s=None, out=None):
     return g_x
 
 
+TAIL_COT, TAIL_ACT, TAIL_COT2, TAIL_TAN = 320, 320, 256, 320          # floats per row of the training passes' buffers (include/mvnerf_hip.h)
+
+
+def grasp_tail_vjp_train(x, stash, packed, g_s=None, out=None):
+    """mvnerf_grasp_tail_vjp_train: the tail's first backward with trainable weights.  g_s (M,) or None (ones) -> g_x (M, 64 n5) (the bits
+    of grasp_tail_vjp), cot (M, 320) = [g_h0 | g_x1 | g_h1 | g_x2], act (M, 320) = [E(h0) | E(x1) | E(h1) | g_s relu(x2)], ex (M, 64 n5) = E(x).
+    out: the four tensors to write into."""
+    m, n5 = _tail_shapes(x, packed)
+    _chk(stash, 'stash', shape=(m, TAIL_STASH))
+    if g_s is not None:
+        _chk(g_s, 'g_s', shape=(m,))
+    dev = x.device
+    if out is None:
+        g_x, ex = torch.empty_like(x), torch.empty_like(x)
+        cot = torch.empty((m, TAIL_COT), dtype=torch.float32, device=dev)
+        act = torch.empty((m, TAIL_ACT), dtype=torch.float32, device=dev)
+    else:                                                    # (g_x, cot, act, ex) to write into
+        g_x, cot, act, ex = out
+        for t, name, cols in ((g_x, 'out g_x', 64 * n5), (cot, 'out cot', TAIL_COT), (act, 'out act', TAIL_ACT), (ex, 'out ex', 64 * n5)):
+            _chk(t, name, shape=(m, cols))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mvnerf_grasp_tail_vjp_train(_p(x), _p(g_s), _p(stash), _p(packed), m, n5, _p(g_x), _p(cot), _p(act), _p(ex), _stream(x)),
+                   'grasp_tail_vjp_train')
+    return g_x, cot, act, ex
+
+
+def grasp_tail_vjp_bwd(x, t_x, stash, cot, packed, g_s=None, want_x=True, out=None):
+    """mvnerf_grasp_tail_vjp_bwd: t_x (M, 64 n5) = dL/d(g_x) -> out_gs (M,) = dL/d(g_s), out_x (M, 64 n5) = dL/dx (None with want_x=False),
+    cot2 (M, 256) = [pi_h0 | pi_x1 | pi_h1], tan (M, 320) = [de0 | da1 | de1 | g_s H dx2], dex (M, 64 n5) = E'(x) t (see include/mvnerf_hip.h)."""
+    m, n5 = _tail_shapes(x, packed)
+    _chk(t_x, 't_x', shape=(m, 64 * n5))
+    _chk(stash, 'stash', shape=(m, TAIL_STASH))
+    _chk(cot, 'cot', shape=(m, TAIL_COT))
+    if g_s is not None:
+        _chk(g_s, 'g_s', shape=(m,))
+    dev = x.device
+    if out is None:
+        out_gs = torch.empty(m, dtype=torch.float32, device=dev)
+        out_x = torch.empty_like(x) if want_x else None
+        cot2 = torch.empty((m, TAIL_COT2), dtype=torch.float32, device=dev)
+        tan = torch.empty((m, TAIL_TAN), dtype=torch.float32, device=dev)
+        dex = torch.empty_like(x)
+    else:                                                    # (out_gs, out_x or None, cot2, tan, dex) to write into
+        out_gs, out_x, cot2, tan, dex = out
+        _chk(out_gs, 'out out_gs', shape=(m,))
+        for t, name, cols in ((out_x, 'out out_x', 64 * n5), (cot2, 'out cot2', TAIL_COT2), (tan, 'out tan', TAIL_TAN), (dex, 'out dex', 64 * n5)):
+            if t is not None or name != 'out out_x':
+                _chk(t, name, shape=(m, cols))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mvnerf_grasp_tail_vjp_bwd(_p(x), _p(t_x), _p(g_s), _p(stash), _p(cot), _p(packed), m, n5, _p(out_gs), _p(out_x),
+                                                        _p(cot2), _p(tan), _p(dex), _stream(x)), 'grasp_tail_vjp_bwd')
+    return out_gs, out_x, cot2, tan, dex
+
+
 # ---- one grasp-pose optimisation step behind the C ABI (csrc/grasp_api.hip; lmvnerf/grasp_optimizer.py:158-184) ------------------------------
 def grasp_workspace_bytes(b, v, p, n5):
     return int(_lib.lib().mvnerf_grasp_workspace_bytes(int(b), int(v), int(p), int(n5)))
