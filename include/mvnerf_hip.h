@@ -483,6 +483,14 @@ int mvnerf_pose_query_points(const float* t, const float* rot, int rep, const fl
 int mvnerf_pose_query_vjp(const float* rot, int rep, const float* offsets, const float* d_points, const float* d_dirs, int P, int n5, int B,
                           long ld, float scale, float* d_t, float* d_rot, mvnerf_stream_t stream);
 
+/* The forward-mode product of mvnerf_pose_query_points along (c_t (P, 3), c_rot (P, 4|6)): t_points[b, p n5 + o] = dR_p t_o + c_t_p,
+ * t_dirs[b, p n5 + o] = dR_p z_o, (B, ld, 3) each, rows past P * n5 of a scene left alone.  dR is the derivative of the tfg quaternion form
+ * with q as given (not normalised), or of the 6d form through x / |x| of both halves and their cross product.  It is also the derivative
+ * of mvnerf_pose_query_vjp w.r.t. its cotangents, which is what LanguageNeRF.train_step's nested tape takes of the pose map
+ * (lmvnerf/model_v4.py:290-322; compute_matrices :192-206, the query points :222-226). */
+int mvnerf_pose_query_jvp(const float* rot, int rep, const float* offsets, const float* c_t, const float* c_rot, int P, int n5, int B, long ld,
+                          float* t_points, float* t_dirs, mvnerf_stream_t stream);
+
 /* optimize(opt, var, g, 1.0) for each trained variable (grasp_optimizer.py:179-182; nerf_utils.py:8-12: clip-by-value, then
  * tf.keras.optimizers.Adam with ExponentialDecay(lr0, decay_steps=1, decay, staircase=False), optimization.py:47-61), then post_process
  * (grasp_optimizer.py:126-139) of every pose.  Step k of variable v uses lr = lr0[v] decay[v]^(k-1), alpha = lr sqrt(1 - beta2^k) /
@@ -544,6 +552,74 @@ int mvnerf_grasp_success_and_gradients(const mvnerf_grasp_call* call, mvnerf_str
 /* Stages 1-8: the above followed by mvnerf_pose_adam_step on t, rot (arguments as there; cfg is [host]). */
 int mvnerf_grasp_opt_step(const mvnerf_grasp_call* call, const mvnerf_pose_adam_config* cfg, const int* train_flags, int* counters, float* m_t,
                           float* v_t, float* m_r, float* v_r, mvnerf_stream_t stream);
+
+/* ---- the losses of LanguageNeRF.train_step (lmvnerf/model_v4.py:277-318) with their cotangents.  One workgroup each, fixed-order sums, no
+ * atomics: the same bits from run to run. ---- */
+#define MVNERF_LOSS_KL_DIVERGENCE 0   /* softmax over the last axis, then tf.keras.losses.KLDivergence(reduction=NONE): one loss per batch element */
+#define MVNERF_LOSS_CROSS_ENTROPY 1   /* tf.keras.losses.CategoricalCrossentropy(from_logits=True): mean over the batch */
+/* The landscape loss (model_v4.py:280-285 with the loss train_language.py:40-63 selects) of the predicted success y (B, np) against label
+ * (B, np): loss[0] = its mean over the batch, g_y (B, np) = weight * d(total)/dy where total = the sum over the batch (kl_divergence: both
+ * inputs clipped to [1e-7, 1], no derivative outside) or the mean (cross_entropy). */
+int mvnerf_landscape_loss(const float* y, const float* label, int B, int np, int kind, float weight, float* g_y, float* loss,
+                          mvnerf_stream_t stream);
+/* tf.keras.losses.CosineSimilarity(axis=-1) as model_v4.py:300-314 uses it on d prediction / d pose: x, label (rows, dim), dim = 3, 4, or
+ * 6 = the two 3-halves taken separately and added; loss[0] = -mean_rows sum_halves u(label) . u(x), u(x) = x rsqrt(max(sum x^2, 1e-12));
+ * g_x (rows, dim) = scale * d loss / d x. */
+int mvnerf_cosine_loss(const float* x, const float* label, long rows, int dim, float scale, float* g_x, float* loss, mvnerf_stream_t stream);
+
+/* ---- the LanguageNeRF training step up to the optimiser behind one call (LanguageNeRF.train_step, lmvnerf/model_v4.py:277-318 through _call
+ * :208-265): the landscape loss on one pose set, the cosine losses on d prediction / d pose of a second set (the nested GradientTape,
+ * :290-314), and the gradient of their sum w.r.t. the GraspReadout variables (:316-318; delta_ngf/layers.py:8-42).  The trunk is frozen.
+ * Nothing is allocated, nothing synchronises with the host, every launch goes to `stream`: a step can be captured in a HIP graph.  Any
+ * B, V, np, n5 >= 1: the weight-gradient products pad their row count to a multiple of 8 inside the workspace, and for V > 1 every scene's
+ * np * n5 rows are padded to whole 32-point tiles (the last point repeated, its cotangents zero).
+ * grads: mvnerf_language_grad_floats(n5) floats, the variables in torch [out, in] orientation, K = 64 n5, in this order:
+ *     head   w4 (4, 64, 128), b4 (4, 64), wc (64, 256), bc (64)                             [activation_downscale 0..3, combined_activation_downscale]
+ *     tail   w0 (128, K), b0 (128), w1 (64, 128), b1 (64), ws (64, K)                       [block_0: layer_0, layer_1, shortcut]
+ *            w0b (64, 64), w1b (64, 64), b0b (64), b1b (64)                                  [block_1: both weights, then both biases]
+ *            w_out (64), b_out (1)                                                            [output_layer]
+ * scalars (4): landscape_loss (mean over the batch), grad_loss_t, grad_loss_r, pred (mean prediction) - the dict train_step returns (:318).
+ * With MVNERF_LOSS_KL_DIVERGENCE the total is one loss per batch element, summed (:316): the two scalar cosine losses enter B times. */
+typedef struct mvnerf_language_call {
+    /* the scene: device pointers, layouts as in mvnerf_query_vjp */
+    const float* images;          /* (B,V,H,W,3) */
+    const float* features;        /* (B,V,H,W,256) */
+    const float* intrinsics;      /* (B,V,4,4) */
+    const float* extrinsics_inv;  /* (B,V,4,4) */
+    int B, V, H, W;
+    /* the frozen trunk */
+    const float* packed_net;      /* mvnerf_pack_net */
+    const void* split;            /* mvnerf_pack_net_split */
+    const float* bwd_streams;     /* mvnerf_pack_bwd_streams */
+    /* the read-out being trained, plain weights (packed by the step: they change every step) */
+    const float* head_w4;         /* (4, 64, 128) */
+    const float* head_b4;         /* (4, 64) */
+    const float* head_wc;         /* (64, 256) */
+    const float* head_bc;         /* (64) */
+    const float* tail_w[11];      /* w0, b0, w1, b1, ws, w0b, b0b, w1b, b1b, w_out, b_out: the order of mvnerf_grasp_tail_pack */
+    const float* offsets;         /* (n5, 4, 4) transforms_to_check */
+    int rep, np, n5;              /* rep: 0 quaternion (x, y, z, w), 1 6d; np poses per scene */
+    /* the two pose sets (model_v4.py:279, :287) and the labels */
+    const float* t_landscape;     /* (B, np, 3) */
+    const float* rot_landscape;   /* (B, np, 4 | 6) */
+    const float* t_grad;          /* (B, np, 3) */
+    const float* rot_grad;        /* (B, np, 4 | 6) */
+    const float* label_landscape; /* (B, np) */
+    const float* label_grad_t;    /* (B, np, 3) */
+    const float* label_grad_r;    /* (B, np, 4 | 6) */
+    int loss_kind;                /* MVNERF_LOSS_* */
+    float w_land, w_t, w_r;       /* weights of the three losses' cotangents (the reference: 1, 1, 1) */
+    /* outputs */
+    float* grads;                 /* mvnerf_language_grad_floats(n5), 16-byte aligned */
+    float* prediction;            /* (B, np): the read-out on the gradient poses */
+    float* scalars;               /* (4) */
+    void* workspace;              /* 256-byte aligned, >= mvnerf_language_workspace_bytes(B, V, H, W, np, n5) */
+    size_t workspace_bytes;
+} mvnerf_language_call;
+size_t mvnerf_language_grad_floats(int n5);
+/* Bytes of workspace (every intermediate of both passes, the packed read-out, the three gradient contributions).  0 for non-positive sizes. */
+size_t mvnerf_language_workspace_bytes(int B, int V, int H, int W, int np, int n5);
+int mvnerf_language_loss_and_grads(const mvnerf_language_call* call, mvnerf_stream_t stream);
 
 /* ---- the whole training step behind one call (MVVNeRFRenderer.train_step, model_v0.py:186-197: GradientTape over call(),
  * loss = MSE(y, rgb) + MSE(y, fine_rgb) :193, gradients :194, optimize() :195 = nerf_utils.py:8-12) ----

@@ -10,8 +10,10 @@ B scenes x (n_points x 42 offsets) query points, V source views of HxW, fp32.  R
                    layers through torch + gemm_ops, or fused in HIP with fused_tail), pose algebra and losses in torch, Adam
   train_step (HIP graph)  the same step after compile(graph=True): one graph replay
 --fused-tail times the train step with GraspReadout.fused_tail off (today's path) and on, the legs alternating --repeats times, and prints
-the median and the range of each leg.
-Usage: python scripts/language_bench.py [--batch 8] [--points 192] [--size 480 640] [--views 1] [--steps 10] [--fused-tail [both|on|off] [--repeats 3]]"""
+the median and the range of each leg.  --fused-step adds the leg with compile(fused_step=True) (the step up to the optimiser as one C call,
+csrc/language_api.hip) to that alternation; alone it alternates today's path, fused_tail and fused_step.
+Usage: python scripts/language_bench.py [--batch 8] [--points 192] [--size 480 640] [--views 1] [--steps 10] [--fused-tail [both|on|off]]
+                                        [--fused-step [with|only]] [--repeats 3]"""
 import argparse
 import os
 import sys
@@ -35,7 +37,9 @@ ap.add_argument('--only-train', action='store_true', help='time the train step o
 ap.add_argument('--train-mode', choices=['both', 'eager', 'graph'], default='both', help='which train_step legs to run')
 ap.add_argument('--fused-tail', nargs='?', const='both', choices=['both', 'on', 'off'], default=None,
                 help='time the train step only, with GraspReadout.fused_tail off and on (alternating), or one of the two (for kernel traces)')
-ap.add_argument('--repeats', type=int, default=3, help='with --fused-tail: how often each leg is timed (for the spread)')
+ap.add_argument('--fused-step', nargs='?', const='with', choices=['with', 'only'], default=None,
+                help='time the train step only: the fused_step leg next to the --fused-tail legs (default: both of them), or alone (for kernel traces)')
+ap.add_argument('--repeats', type=int, default=3, help='with --fused-tail / --fused-step: how often each leg is timed (for the spread)')
 args = ap.parse_args()
 dev = 'cuda:0'
 h, w = args.size
@@ -90,12 +94,12 @@ packed16 = ops.pack_net_bf16(model.trunk_net)
 eager_steps, graph_steps = max(2, args.steps // 2), max(4, args.steps)
 
 
-def graph_model(fused_tail=None):
+def graph_model(fused_tail=None, fused_step=None):
     """The same step captured as one HIP graph (compile(graph=True)): device-resident inputs bound as the graph's buffers; the two eager steps
     and the capture itself stay outside the timed region."""
     gm = LanguageNeRF(sc['fine'], n_points_train=npts, n_views=args.views, batch_size=b, rotation_representation='6d',
                       softmax_before_loss=True, device=dev)
-    gm.compile(graph=True, fused_tail=fused_tail)
+    gm.compile(graph=True, fused_tail=fused_tail, fused_step=fused_step)
     dv = lambda a: torch.from_numpy(a).to(dev)
     data = ((dv(t1), dv(r1), dv(t2), dv(r2), images, k4, einv), tuple(dv(l) for l in labels))
     gm.bind_graph_inputs(data, feats)
@@ -104,18 +108,22 @@ def graph_model(fused_tail=None):
     return gm, data
 
 
-if args.fused_tail:
+if args.fused_tail or args.fused_step:
     legs, graphs = {}, {}
+    tails = () if args.fused_step == 'only' else {'both': (False, True), 'on': (True,), 'off': (False,)}[args.fused_tail or 'both']
+    flags = [(f'fused_tail={fused}', dict(fused_tail=fused, fused_step=False)) for fused in tails]
+    if args.fused_step:
+        flags.append(('fused_step=True', dict(fused_tail=False, fused_step=True)))
     for _ in range(args.repeats):
-        for fused in {'both': (False, True), 'on': (True,), 'off': (False,)}[args.fused_tail]:
+        for name, kw in flags:
             if args.train_mode != 'graph':
-                model.compile(fused_tail=fused)
-                legs.setdefault(f'train_step, fused_tail={fused}', []).append(timed(lambda: model.train_step((inputs, labels), feats), eager_steps))
+                model.compile(**kw)
+                legs.setdefault(f'train_step, {name}', []).append(timed(lambda: model.train_step((inputs, labels), feats), eager_steps))
             if args.train_mode != 'eager':
-                if fused not in graphs:
-                    graphs[fused] = graph_model(fused)
-                gm, data = graphs[fused]
-                legs.setdefault(f'train_step (HIP graph), fused_tail={fused}', []).append(timed(lambda: gm.train_step(data, feats), graph_steps))
+                if name not in graphs:
+                    graphs[name] = graph_model(**kw)
+                gm, data = graphs[name]
+                legs.setdefault(f'train_step (HIP graph), {name}', []).append(timed(lambda: gm.train_step(data, feats), graph_steps))
     print(f'B={b} scenes x {points.shape[1]} query points ({npts} poses x 42 offsets), V={args.views}, {h}x{w}; per leg {args.repeats} timings of '
           f'{eager_steps} (eager) / {graph_steps} (graph) steps, alternating')
     for k, ts in sorted(legs.items()):

@@ -2,9 +2,11 @@
 4096 guesses on 3 images, 16 + 16 optimisation steps): ms per training step (eager and one graph replay, batches assembled on the
 device beforehand), ms per device batch, seconds per validation sample.  One JSON line.
 
-    python scripts/train_language_bench.py [--size 480x640] [--steps 10] [--fused-tail]
+    python scripts/train_language_bench.py [--size 480x640] [--steps 10] [--fused-tail] [--fused-step] [--rounds 1]
 
---fused-tail adds the training legs with GraspReadout.fused_tail on (train_step_ms_*_fused_tail, loss_*_fused_tail) after today's legs.
+--fused-tail adds the training legs with GraspReadout.fused_tail on (train_step_ms_*_fused_tail, loss_*_fused_tail) after today's legs,
+--fused-step those with compile(fused_step=True) (the step up to the optimiser as one C call: train_step_ms_*_fused_step).  With
+--rounds N the legs alternate N times in this process and the median is reported (the list of timings as *_all).
 """
 import argparse
 import json
@@ -29,6 +31,8 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--guesses', type=int, default=4096)
     ap.add_argument('--fused-tail', action='store_true', help='also time the training step with compile(fused_tail=True)')
+    ap.add_argument('--fused-step', action='store_true', help='also time the training step with compile(fused_step=True)')
+    ap.add_argument('--rounds', type=int, default=1, help='how often the training legs alternate (the median is reported)')
     args = ap.parse_args()
     h, w = T._size(args.size)
     dev = 'cuda:0'
@@ -46,23 +50,33 @@ def main():
     torch.cuda.synchronize()
     batch_ms = (time.time() - t0) / len(batches) * 1e3
     out = {'size': [h, w], 'batch': args.batch, 'poses_per_scene': 192, 'setup_s': round(setup_s, 1), 'device_batch_ms': round(batch_ms, 2)}
-    for graph, fused in [(False, False), (True, False)] + ([(False, True), (True, True)] if args.fused_tail else []):
-        torch.manual_seed(0)
-        model = LanguageNeRF(glorot_net(np.random.default_rng(0), bias_scale=0.05), n_points_train=192, n_views=1, batch_size=args.batch,
-                             rotation_representation='6d', softmax_before_loss=True, device=dev)
-        model.compile(loss=kl_divergence, graph=graph, fused_tail=fused)
-        for (inputs, feats), labels in batches[:3]:
-            model.train_step((inputs, labels), feats)
-        torch.cuda.synchronize()
-        t0 = time.time()
-        for (inputs, feats), labels in batches[3:]:
-            res = model.train_step((inputs, labels), feats)
-        torch.cuda.synchronize()
-        leg = ('graph' if graph else 'eager') + ('_fused_tail' if fused else '')
-        out[f'train_step_ms_{leg}'] = round((time.time() - t0) / args.steps * 1e3, 2)
-        out[f'loss_{leg}'] = float(res['landscape_loss'] + res['grad_loss_t'] + res['grad_loss_r'])
+    modes = [('', {})] + ([('_fused_tail', dict(fused_tail=True))] if args.fused_tail else []) + \
+        ([('_fused_step', dict(fused_step=True))] if args.fused_step else [])
+    timings = {}
+    for _ in range(args.rounds):
+        for suffix, flags in modes:
+            for graph in (False, True):
+                torch.manual_seed(0)
+                model = LanguageNeRF(glorot_net(np.random.default_rng(0), bias_scale=0.05), n_points_train=192, n_views=1,
+                                     batch_size=args.batch, rotation_representation='6d', softmax_before_loss=True, device=dev)
+                model.compile(loss=kl_divergence, graph=graph, **flags)
+                for (inputs, feats), labels in batches[:3]:
+                    model.train_step((inputs, labels), feats)
+                torch.cuda.synchronize()
+                t0 = time.time()
+                for (inputs, feats), labels in batches[3:]:
+                    res = model.train_step((inputs, labels), feats)
+                torch.cuda.synchronize()
+                leg = ('graph' if graph else 'eager') + suffix
+                timings.setdefault(leg, []).append((time.time() - t0) / args.steps * 1e3)
+                out[f'loss_{leg}'] = float(res['landscape_loss'] + res['grad_loss_t'] + res['grad_loss_r'])
+    for leg, ts in timings.items():
+        out[f'train_step_ms_{leg}'] = round(sorted(ts)[len(ts) // 2], 2)
+        if args.rounds > 1:
+            out[f'train_step_ms_{leg}_all'] = [round(t, 2) for t in ts]
     del batches
     model.set_fused_tail(False)                                                               # validation as today
+    model.set_fused_step(False)
     data = T.get_inputs(valid, 0, 3, device=dev)
     config = dict(n_optimization_steps=16, init_lr_t=0.05, init_lr_r=0.05, decay_t=0.9, decay_r=0.09)
     for graph in (False, True):

@@ -51,6 +51,19 @@ class GraspCall(ctypes.Structure):
                 [('workspace_bytes', c_size_t)])
 
 
+class LanguageCall(ctypes.Structure):
+    """mvnerf_language_call (include/mvnerf_hip.h): one LanguageNeRF training problem, field for field."""
+    _fields_ = ([(n, c_void_p) for n in ('images', 'features', 'intrinsics', 'extrinsics_inv')] +
+                [(n, c_int) for n in ('B', 'V', 'H', 'W')] +
+                [(n, c_void_p) for n in ('packed_net', 'split', 'bwd_streams', 'head_w4', 'head_b4', 'head_wc', 'head_bc')] +
+                [('tail_w', c_void_p * 11), ('offsets', c_void_p)] +
+                [(n, c_int) for n in ('rep', 'np', 'n5')] +
+                [(n, c_void_p) for n in ('t_landscape', 'rot_landscape', 't_grad', 'rot_grad', 'label_landscape', 'label_grad_t', 'label_grad_r')] +
+                [('loss_kind', c_int), ('w_land', c_float), ('w_t', c_float), ('w_r', c_float)] +
+                [(n, c_void_p) for n in ('grads', 'prediction', 'scalars', 'workspace')] +
+                [('workspace_bytes', c_size_t)])
+
+
 class GemmTnBatch(ctypes.Structure):
     """mvnerf_gemm_tn_batch (include/mvnerf_hip.h)."""
     _fields_ = ([(n, c_void_p) for n in ('g', 'a', 'g2', 'a2')] +
@@ -135,6 +148,12 @@ SIGNATURES = {
     'mvnerf_grasp_tail_vjp_bwd': (c_int, [c_void_p] * 6 + [c_long, c_int] + [c_void_p] * 6),
     'mvnerf_pose_query_points': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
     'mvnerf_pose_query_vjp': (c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_long, c_float, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_pose_query_jvp': (c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_long, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_landscape_loss': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_cosine_loss': (c_int, [c_void_p, c_void_p, c_long, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_language_grad_floats': (c_size_t, [c_int]),
+    'mvnerf_language_workspace_bytes': (c_size_t, [c_int] * 6),
+    'mvnerf_language_loss_and_grads': (c_int, [ctypes.POINTER(LanguageCall), c_void_p]),
     'mvnerf_pose_adam_step': (c_int, [ctypes.POINTER(PoseAdamConfig), c_int, c_int] + [c_void_p] * 11),
     'mvnerf_grasp_workspace_bytes': (c_size_t, [c_int] * 4),
     'mvnerf_grasp_success': (c_int, [ctypes.POINTER(GraspCall), c_void_p]),

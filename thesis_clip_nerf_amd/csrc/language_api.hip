@@ -1,0 +1,434 @@
+// extern "C" LanguageNeRF training step up to the optimiser (LanguageNeRF.train_step, src/lib/lmvnerf/model_v4.py:277-318: the landscape
+// loss on one pose set, the cosine losses on d prediction / d pose of a second one under a nested GradientTape, and the gradient of their
+// sum w.r.t. the GraspReadout variables) behind ONE call: mvnerf_language_loss_and_grads.  The second-order step is written out the way
+// grasp_api.hip writes out the optimiser's step - the sequence thesis_clip_nerf_amd/lmvnerf.py builds from autograd functions:
+//
+//   pass A (landscape poses)  points -> trunk -> head -> tail -> landscape loss, g_s -> tail VJP (+ weight gradients) -> head VJP (+ weight
+//                             gradients).  No trunk VJP: only the read-out trains.
+//   pass B (gradient poses)   points -> trunk with stash -> head -> tail = prediction -> tail VJP of sum(prediction) -> head VJP -> trunk VJP
+//                             -> pose VJP = d prediction / d pose -> cosine losses, their cotangents -> pose JVP -> trunk JVP -> derivative of
+//                             the head VJP (second-order head gradients, out_gy) -> derivative of the tail VJP with t_x = out_gy (second-order
+//                             tail gradients, out_x) -> head VJP of out_x (the third contribution to the head gradients).
+//   gradient = (pass A + second order) + third, in that order for every variable.
+//
+// Every weight gradient is a mvnerf_gemm_tn_batched product over the M = B np (tail) or M n5 (head) rows; the buffers carry up to 7 extra
+// rows (7 n5 for the head) so that the row count is a multiple of 8, zero in every `g` operand, finite in every `a` operand: the products
+// are the unpadded ones.  For V > 1 the trunk sees every scene's np n5 rows padded to whole 32-point tiles (the last point repeated, its
+// cotangents and tangents zero); the read-out runs on the compact rows.
+// No allocation: every intermediate lives in the caller's workspace (mvnerf_language_workspace_bytes).  Stream-ordered, no host
+// synchronisation, no global state, no atomics of its own (mvnerf_query_vjp's view sum for V > 1 is the one unordered sum of the step).
+#include <hip/hip_runtime.h>
+
+#include "../../include/mvnerf_hip.h"
+#include "mvnerf_kernels.h"
+
+namespace {
+
+constexpr size_t kAlign = 256;
+size_t up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+
+constexpr long kHeadGrad = 4 * 64 * 128 + 4 * 64 + 64 * 256 + 64;          // floats of d_w4, d_b4, d_wc, d_bc
+
+// offsets (floats) of the variables inside the flat gradient, the order include/mvnerf_hip.h documents
+struct GradLayout {
+    long w4, b4, wc, bc, w0, b0, w1, b1, ws, w0b, w1b, b0b, b1b, w_out, b_out, total;
+};
+
+GradLayout grad_layout(int n5) {
+    const long K = 64L * n5;
+    GradLayout g;
+    long at = 0;
+    auto take = [&](long n) { const long o = at; at += n; return o; };
+    g.w4 = take(4 * 64 * 128); g.b4 = take(4 * 64); g.wc = take(64 * 256); g.bc = take(64);
+    g.w0 = take(128 * K); g.b0 = take(128); g.w1 = take(64 * 128); g.b1 = take(64); g.ws = take(64 * K);
+    g.w0b = take(64 * 64); g.w1b = take(64 * 64); g.b0b = take(64); g.b1b = take(64); g.w_out = take(64); g.b_out = take(1);
+    g.total = at;
+    return g;
+}
+
+struct LangWs {
+    // trunk side: B scenes of ld rows
+    float *points, *dirs, *z, *rgbs, *d_points, *d_dirs, *t_points, *t_dirs, *acts_p, *g_acts_p, *t_acts_p, *stash;
+    void *field_ws, *vjp_scratch, *jvp_ws;
+    // read-out side: N = B n rows (NR with the GEMM pad), M = B np rows (M8)
+    float *acts, *t_acts, *g_acts, *c, *y, *g_v, *q, *g_u, *r, *m, *p, *out_gy, *g_x, *ex, *out_x, *dex;
+    float *tail_stash, *g_s, *out_gs, *cot, *act, *cot2, *tan;
+    float *grads_t, *grads_r, *c_t, *c_r;
+    float *head_packed, *tail_packed, *g1, *g2, *g3;
+    void* gemm_scratch;
+    long n, ld, N, NR, M, M8;
+    size_t bytes;
+};
+
+size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
+
+LangWs carve(void* base, int B, int V, int np, int n5) {
+    LangWs w;
+    char* ptr = static_cast<char*>(base);
+    auto take = [&](size_t floats) {
+        char* q = ptr;
+        ptr += up(floats * 4);
+        return reinterpret_cast<float*>(q);
+    };
+    auto take_bytes = [&](size_t bytes) {
+        char* q = ptr;
+        ptr += up(bytes);
+        return static_cast<void*>(q);
+    };
+    w.n = (long)np * n5;
+    w.ld = V > 1 ? (w.n + 31) / 32 * 32 : w.n;
+    w.N = (long)B * w.n;
+    w.M = (long)B * np;
+    w.M8 = (w.M + 7) / 8 * 8;
+    w.NR = w.M8 * n5;
+    const bool padded = w.ld > w.n;
+    const size_t rows = (size_t)B * w.ld, N = (size_t)w.N, NR = (size_t)w.NR, M8 = (size_t)w.M8, slack = (NR - N) * 128;
+    const int K = 64 * n5, ld = (int)w.ld;
+    w.points = take(rows * 3); w.dirs = take(rows * 3); w.z = take(rows); w.rgbs = take(rows * 4);
+    w.d_points = take(rows * 3); w.d_dirs = take(rows * 3); w.t_points = take(rows * 3); w.t_dirs = take(rows * 3);
+    w.field_ws = take_bytes(mvnerf_field_workspace_bytes(B, V, ld));
+    w.stash = static_cast<float*>(take_bytes(mvnerf_stash_bytes(B, V, ld, 1)));
+    w.vjp_scratch = take_bytes(mvnerf_query_vjp_scratch_bytes(B, V, ld));
+    w.jvp_ws = take_bytes(mvnerf_query_workspace_bytes(B, V, ld));
+    w.acts = take(4 * N * 128 + slack); w.t_acts = take(4 * N * 128 + slack); w.g_acts = take(4 * N * 128);
+    if (padded) {
+        w.acts_p = take(4 * rows * 128); w.g_acts_p = take(4 * rows * 128); w.t_acts_p = take(4 * rows * 128);
+    } else {
+        w.acts_p = w.acts; w.g_acts_p = w.g_acts; w.t_acts_p = w.t_acts;
+    }
+    w.c = take(NR * 256); w.y = take(NR * 64); w.g_v = take(NR * 64); w.q = take(NR * 256); w.g_u = take(NR * 256);
+    w.r = take(NR * 256); w.m = take(NR * 64); w.p = take(NR * 256); w.out_gy = take(NR * 64);
+    w.g_x = take(NR * 64); w.ex = take(NR * 64); w.out_x = take(NR * 64); w.dex = take(NR * 64);
+    w.tail_stash = take(M8 * mvnerf::grasp_tail_stash_floats()); w.g_s = take(M8); w.out_gs = take(M8);
+    w.cot = take(M8 * 320); w.act = take(M8 * 320); w.cot2 = take(M8 * 256); w.tan = take(M8 * 320);
+    w.grads_t = take(M8 * 3); w.grads_r = take(M8 * 6); w.c_t = take(M8 * 3); w.c_r = take(M8 * 6);
+    w.head_packed = take(mvnerf_grasp_head_packed_floats());
+    w.tail_packed = take(mvnerf_grasp_tail_packed_floats(n5));
+    const size_t G = (size_t)grad_layout(n5).total;
+    w.g1 = take(G); w.g2 = take(G); w.g3 = take((size_t)kHeadGrad);
+    size_t sc = 0;
+    sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)NR, 64, 128, 4, 1));
+    sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)NR, 64, 256, 1, 1));
+    sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)M8, 128, K, 1, 1));
+    sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)M8, 64, K, 1, 1));
+    sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)M8, 64, 128, 1, 1));
+    sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)M8, 64, 64, 2, 1));
+    w.gemm_scratch = take_bytes(sc + 16);
+    w.bytes = (size_t)(ptr - static_cast<char*>(base));
+    return w;
+}
+
+bool sizes_ok(int B, int V, int H, int W, int np, int n5) {
+    return B > 0 && V > 0 && H >= 2 && W >= 2 && np > 0 && n5 > 0 && n5 <= 4096 && ((long)np + 7) * n5 + 31 < (1L << 31) / B / 4;
+}
+
+// ---- the small kernels of the step ----------------------------------------------------------------------------------------------------------
+constexpr int kZeroMax = 24;
+struct ZeroList {
+    float* ptr[kZeroMax];
+    long count[kZeroMax];
+    int n;
+};
+// entry blockIdx.y: count floats at ptr <- 0
+__global__ void zero_list_kernel(ZeroList z) {
+    float* p = z.ptr[blockIdx.y];
+    const long n = z.count[blockIdx.y];
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = 0.0f;
+}
+
+// rows n .. ld of every scene repeat row n - 1 (whole tiles for the multi-view kernels; as mvnerf_grasp_opt_step)
+__global__ void pad_rows_kernel(float* __restrict__ points, float* __restrict__ dirs, int B, long n, long ld) {
+    const long pad = ld - n, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)B * pad * 3) return;
+    const long b = idx / (pad * 3), r = (idx / 3) % pad;
+    const int k = (int)(idx % 3);
+    points[(b * ld + n + r) * 3 + k] = points[(b * ld + n - 1) * 3 + k];
+    dirs[(b * ld + n + r) * 3 + k] = dirs[(b * ld + n - 1) * 3 + k];
+}
+
+// (groups, src_ld, 128) -> (groups, dst_ld, 128): rows below `n` copied, rows n .. dst_ld zero.  Compacts the trunk's padded rows
+// (src_ld = ld, dst_ld = n) and expands the read-out's (src_ld = n, dst_ld = ld); one float4 per thread.
+__global__ void copy_rows_kernel(const float4* __restrict__ src, float4* __restrict__ dst, long groups, long n, long src_ld, long dst_ld) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= groups * dst_ld * 32) return;
+    const long g = idx / (dst_ld * 32), r = (idx / 32) % dst_ld, k = idx % 32;
+    dst[idx] = r < n ? src[(g * src_ld + r) * 32 + k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// out[j] = sum_m src[m * ld + j] for 64 columns (+ out_sum[0] = sum_m v[m] when v is given): the output layer's gradients.  One workgroup
+// of 64 columns x 16 row lanes: a lane adds its rows m = lane, lane + 16, ... in order, then the 16 partials are added in order.
+constexpr int kColsumLanes = 16;
+__global__ __launch_bounds__(64 * kColsumLanes) void colsum64_kernel(const float* __restrict__ src, int ld, long M, float* __restrict__ out,
+                                                                     const float* __restrict__ v, float* __restrict__ out_sum) {
+    __shared__ float part[kColsumLanes][64], part_v[kColsumLanes];
+    const int j = threadIdx.x & 63, lane = threadIdx.x >> 6;
+    float acc = 0.0f, acc_v = 0.0f;
+    for (long m = lane; m < M; m += kColsumLanes) {
+        acc += src[m * ld + j];
+        if (j == 0 && v) acc_v += v[m];
+    }
+    part[lane][j] = acc;
+    if (j == 0) part_v[lane] = acc_v;
+    __syncthreads();
+    if (lane != 0) return;
+    float total = 0.0f, total_v = 0.0f;
+    for (int l = 0; l < kColsumLanes; ++l) { total += part[l][j]; total_v += part_v[l]; }
+    out[j] = total;
+    if (j == 0 && out_sum) out_sum[0] = total_v;
+}
+
+constexpr int kMeanThreads = 256;
+__global__ __launch_bounds__(kMeanThreads) void mean_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
+    __shared__ float lds[kMeanThreads];
+    float acc = 0.0f;
+    for (long i = threadIdx.x; i < n; i += kMeanThreads) acc += x[i];
+    lds[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = kMeanThreads / 2; s >= 1; s >>= 1) {
+        if ((int)threadIdx.x < s) lds[threadIdx.x] += lds[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = lds[0] / (float)n;
+}
+
+// grads = (g1 + g2) + g3, g3 covering the first n_head floats only
+__global__ void sum_grads_kernel(const float* __restrict__ g1, const float* __restrict__ g2, const float* __restrict__ g3, long n, long n_head,
+                                 float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float s = g1[i] + g2[i];
+    out[i] = i < n_head ? s + g3[i] : s;
+}
+
+bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+#define MV_RC(x)                  \
+    do {                          \
+        int rc_ = (x);            \
+        if (rc_ != 0) return rc_; \
+    } while (0)
+#define MV_HIP(x, who)                                                                                    \
+    do {                                                                                                  \
+        hipError_t e_ = (x);                                                                              \
+        if (e_ != hipSuccess) return mvnerf::api_fail((int)e_, "%s: %s", who, hipGetErrorString(e_));     \
+    } while (0)
+
+const char* const kWho = "mvnerf_language_loss_and_grads";
+
+int validate(const mvnerf_language_call* c, LangWs* out) {
+    using mvnerf::api_fail;
+    const char* who = kWho;
+    if (!c) return api_fail(MVNERF_E_ARG, "%s: null call", who);
+    if (!c->images || !c->features || !c->intrinsics || !c->extrinsics_inv || !c->packed_net || !c->split || !c->bwd_streams || !c->head_w4 ||
+        !c->head_b4 || !c->head_wc || !c->head_bc || !c->offsets || !c->t_landscape || !c->rot_landscape || !c->t_grad || !c->rot_grad ||
+        !c->label_landscape || !c->label_grad_t || !c->label_grad_r || !c->grads || !c->prediction || !c->scalars || !c->workspace)
+        return api_fail(MVNERF_E_ARG, "%s: null pointer", who);
+    for (int i = 0; i < 11; ++i)
+        if (!c->tail_w[i]) return api_fail(MVNERF_E_ARG, "%s: null pointer (tail_w[%d])", who, i);
+    if (!sizes_ok(c->B, c->V, c->H, c->W, c->np, c->n5))
+        return api_fail(MVNERF_E_ARG, "%s: B=%d V=%d H=%d W=%d np=%d n5=%d", who, c->B, c->V, c->H, c->W, c->np, c->n5);
+    if (c->rep != 0 && c->rep != 1) return api_fail(MVNERF_E_SHAPE, "%s: rep=%d (0 quaternion, 1 6d)", who, c->rep);
+    if (c->loss_kind != MVNERF_LOSS_KL_DIVERGENCE && c->loss_kind != MVNERF_LOSS_CROSS_ENTROPY)
+        return api_fail(MVNERF_E_SHAPE, "%s: loss_kind=%d (0 kl_divergence, 1 cross_entropy)", who, c->loss_kind);
+    if (!al16(c->features) || !al16(c->packed_net) || !al16(c->split) || !al16(c->bwd_streams) || !al16(c->grads))
+        return api_fail(MVNERF_E_ALIGN, "%s: features, packed_net, split, bwd_streams, grads must be 16-byte aligned", who);
+    for (int i = 0; i < 11; ++i)
+        if (!al4(c->tail_w[i])) return api_fail(MVNERF_E_ALIGN, "%s: tail_w[%d] must be 4-byte aligned", who, i);
+    if (!al4(c->images) || !al4(c->intrinsics) || !al4(c->extrinsics_inv) || !al4(c->head_w4) || !al4(c->head_wc) || !al4(c->head_b4) || !al4(c->head_bc) || !al4(c->offsets) ||
+        !al4(c->t_landscape) || !al4(c->rot_landscape) || !al4(c->t_grad) || !al4(c->rot_grad) || !al4(c->label_landscape) ||
+        !al4(c->label_grad_t) || !al4(c->label_grad_r) || !al4(c->prediction) || !al4(c->scalars))
+        return api_fail(MVNERF_E_ALIGN, "%s: float buffers must be 4-byte aligned", who);
+    if ((reinterpret_cast<uintptr_t>(c->workspace) & 255u) != 0) return api_fail(MVNERF_E_ALIGN, "%s: workspace must be 256-byte aligned", who);
+    *out = carve(c->workspace, c->B, c->V, c->np, c->n5);
+    if (c->workspace_bytes < out->bytes)
+        return api_fail(MVNERF_E_ARG, "%s: workspace %zu bytes, need %zu (mvnerf_language_workspace_bytes)", who, c->workspace_bytes, out->bytes);
+    return 0;
+}
+
+// one mvnerf_gemm_tn_batched call: c[b] = G[b]^T A[b] (+ G2[b]^T A2[b]), operands as (pointer, batch stride, row stride)
+struct Op {
+    const float* p;
+    long bs;
+    int ld;
+};
+int tn(Op g, Op a, Op g2, Op a2, int colsum_of, float* c, float* colsum, long M, int N, int K, int batch, void* scratch, mvnerf_stream_t stream) {
+    mvnerf_gemm_tn_batch q = {};
+    q.g = g.p; q.g_batch_stride = g.bs; q.ldg = g.ld;
+    q.a = a.p; q.a_batch_stride = a.bs; q.lda = a.ld;
+    q.g2 = g2.p; q.g2_batch_stride = g2.bs; q.ldg2 = g2.ld;
+    q.a2 = a2.p; q.a2_batch_stride = a2.bs; q.lda2 = a2.ld;
+    q.colsum_of = colsum_of;
+    return mvnerf_gemm_tn_batched(&q, c, colsum, (int)M, N, K, batch, scratch, stream);
+}
+const Op kNone = {nullptr, 0, 0};
+
+struct Step {
+    const mvnerf_language_call* c;
+    LangWs w;
+    mvnerf_stream_t stream;
+    hipStream_t st;
+    GradLayout gl;
+    int K;
+    bool padded;
+
+    // poses -> the trunk's query rows (every (scene, pose) pair is its own pose: one call over B np poses, or one per scene when padded)
+    int points(const float* t, const float* rot) {
+        const int rd = c->rep == 0 ? 4 : 6;
+        if (!padded) return mvnerf_pose_query_points(t, rot, c->rep, c->offsets, c->B * c->np, c->n5, 1, w.N, w.points, w.dirs, stream);
+        for (int b = 0; b < c->B; ++b)
+            MV_RC(mvnerf_pose_query_points(t + (size_t)b * c->np * 3, rot + (size_t)b * c->np * rd, c->rep, c->offsets, c->np, c->n5, 1, w.ld,
+                                           w.points + (size_t)b * w.ld * 3, w.dirs + (size_t)b * w.ld * 3, stream));
+        const long n_pad = (long)c->B * (w.ld - w.n) * 3;
+        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, w.points, w.dirs, c->B, w.n, w.ld);
+        MV_HIP(hipGetLastError(), kWho);
+        return 0;
+    }
+
+    int copy_rows(const float* src, float* dst, long src_ld, long dst_ld) {
+        const long groups = 4L * c->B, total = groups * dst_ld * 32;
+        hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(src),
+                           reinterpret_cast<float4*>(dst), groups, w.n, src_ld, dst_ld);
+        MV_HIP(hipGetLastError(), kWho);
+        return 0;
+    }
+
+    // points -> trunk (pre-activations kept) -> fused activations -> head -> tail
+    int forward(const float* t, const float* rot, float* success) {
+        MV_RC(points(t, rot));
+        MV_RC(mvnerf_field_eval_stash_split(w.points, w.dirs, w.z, c->images, c->features, nullptr, c->intrinsics, c->extrinsics_inv, c->packed_net,
+                                            c->split, c->B, c->V, (int)w.ld, 1, c->H, c->W, w.rgbs, w.stash, w.field_ws, stream));
+        MV_RC(mvnerf_stash_fused_acts(w.stash, c->B, c->V, (int)w.ld, w.acts_p, stream));
+        if (padded) MV_RC(copy_rows(w.acts_p, w.acts, w.ld, w.n));
+        MV_RC(mvnerf_grasp_head_fwd(w.acts, w.head_packed, c->head_b4, c->head_bc, w.N, w.c, w.y, stream));
+        return mvnerf_grasp_tail_fwd(w.y, w.tail_packed, w.M, c->n5, success, w.tail_stash, stream);
+    }
+
+    // head VJP of g_y and the weight gradients it gives (dW_k = g_u_k^T a_k, db_k = sum g_u_k, dW_c = g_v^T c, db_c = sum g_v) -> g
+    int head_first(const float* g_y, float* g) {
+        MV_RC(mvnerf_grasp_head_vjp(g_y, w.c, w.y, w.head_packed, w.N, w.g_v, w.q, w.g_u, w.g_acts, stream));
+        MV_RC(tn({w.g_u, 64, 256}, {w.acts, w.N * 128, 128}, kNone, kNone, 1, g + gl.w4, g + gl.b4, w.NR, 64, 128, 4, w.gemm_scratch, stream));
+        return tn({w.g_v, 0, 64}, {w.c, 0, 256}, kNone, kNone, 1, g + gl.wc, g + gl.bc, w.NR, 64, 256, 1, w.gemm_scratch, stream);
+    }
+
+    int run() {
+        const int B = c->B, V = c->V, np = c->np, n5 = c->n5, rd = c->rep == 0 ? 4 : 6;
+        const long N = w.N, NR = w.NR, M = w.M, M8 = w.M8;
+        void* sc = w.gemm_scratch;
+        // 0. the GEMM pad rows, the zero depths, the identically zero second-order gradients, and the padded tangents' pad rows
+        {
+            ZeroList z = {};
+            auto add = [&](float* p, long count) {
+                if (count > 0) { z.ptr[z.n] = p; z.count[z.n] = count; ++z.n; }
+            };
+            const long hp = NR - N, tp = M8 - M;
+            for (float* p : {w.c, w.g_u, w.r, w.p}) add(p + N * 256, hp * 256);
+            for (float* p : {w.y, w.g_v, w.m, w.out_gy, w.g_x, w.ex, w.dex}) add(p + N * 64, hp * 64);
+            add(w.acts + 4 * N * 128, hp * 128);
+            add(w.t_acts + 4 * N * 128, hp * 128);
+            for (float* p : {w.cot, w.act, w.tan}) add(p + M * 320, tp * 320);
+            add(w.cot2 + M * 256, tp * 256);
+            add(w.z, (long)B * w.ld);
+            add(w.g2 + gl.b1b, 64);
+            add(w.g2 + gl.b_out, 1);
+            if (padded) { add(w.t_points, (long)B * w.ld * 3); add(w.t_dirs, (long)B * w.ld * 3); }
+            hipLaunchKernelGGL(zero_list_kernel, dim3(64, (unsigned)z.n), dim3(256), 0, st, z);
+            MV_HIP(hipGetLastError(), kWho);
+        }
+        // the read-out's operand images (the weights change every step)
+        MV_RC(mvnerf_grasp_head_pack(c->head_w4, c->head_wc, w.head_packed, stream));
+        const float* const* tw = c->tail_w;
+        MV_RC(mvnerf_grasp_tail_pack(tw[0], tw[1], tw[2], tw[3], tw[4], tw[5], tw[6], tw[7], tw[8], tw[9], tw[10], n5, w.tail_packed, stream));
+
+        // ---- pass A: the landscape poses ----
+        MV_RC(forward(c->t_landscape, c->rot_landscape, w.out_gs));                        // A1-A4 (success of pass A lives in out_gs)
+        MV_RC(mvnerf_landscape_loss(w.out_gs, c->label_landscape, B, np, c->loss_kind, c->w_land, w.g_s, c->scalars + 0, stream));   // A5
+        MV_RC(mvnerf_grasp_tail_vjp_train(w.y, w.g_s, w.tail_stash, w.tail_packed, M, n5, w.g_x, w.cot, w.act, w.ex, stream));      // A6
+        MV_RC(tn({w.cot, 0, 320}, {w.ex, 0, K}, kNone, kNone, 1, w.g1 + gl.w0, w.g1 + gl.b0, M8, 128, K, 1, sc, stream));
+        MV_RC(tn({w.cot + 128, 0, 320}, {w.y, 0, K}, kNone, kNone, 1, w.g1 + gl.ws, w.g1 + gl.b1, M8, 64, K, 1, sc, stream));
+        MV_RC(tn({w.cot + 128, 0, 320}, {w.act, 0, 320}, kNone, kNone, 0, w.g1 + gl.w1, nullptr, M8, 64, 128, 1, sc, stream));
+        MV_RC(tn({w.cot + 192, 64, 320}, {w.act + 128, 64, 320}, kNone, kNone, 1, w.g1 + gl.w0b, w.g1 + gl.b0b, M8, 64, 64, 2, sc, stream));
+        hipLaunchKernelGGL(colsum64_kernel, dim3(1), dim3(64 * kColsumLanes), 0, st, w.act + 256, 320, M, w.g1 + gl.w_out, w.g_s, w.g1 + gl.b_out);
+        MV_HIP(hipGetLastError(), kWho);
+        MV_RC(head_first(w.g_x, w.g1));                                                    // A7
+
+        // ---- pass B: the gradient poses ----
+        MV_RC(forward(c->t_grad, c->rot_grad, c->prediction));                             // B1-B4
+        MV_RC(mvnerf_grasp_tail_vjp_train(w.y, nullptr, w.tail_stash, w.tail_packed, M, n5, w.g_x, w.cot, w.act, w.ex, stream));    // B5
+        MV_RC(mvnerf_grasp_head_vjp(w.g_x, w.c, w.y, w.head_packed, N, w.g_v, w.q, w.g_u, w.g_acts, stream));                        // B6
+        if (padded) MV_RC(copy_rows(w.g_acts, w.g_acts_p, w.n, w.ld));
+        MV_RC(mvnerf_query_vjp(w.points, w.dirs, c->images, c->features, c->intrinsics, c->extrinsics_inv, c->bwd_streams, w.stash, w.g_acts_p, B, V,
+                               (int)w.ld, c->H, c->W, w.vjp_scratch, w.d_points, w.d_dirs, stream));                                  // B7
+        if (!padded) {                                                                                                              // B8
+            MV_RC(mvnerf_pose_query_vjp(c->rot_grad, c->rep, c->offsets, w.d_points, w.d_dirs, B * np, n5, 1, N, 1.0f, w.grads_t, w.grads_r, stream));
+        } else {
+            for (int b = 0; b < B; ++b)
+                MV_RC(mvnerf_pose_query_vjp(c->rot_grad + (size_t)b * np * rd, c->rep, c->offsets, w.d_points + (size_t)b * w.ld * 3,
+                                            w.d_dirs + (size_t)b * w.ld * 3, np, n5, 1, w.ld, 1.0f, w.grads_t + (size_t)b * np * 3,
+                                            w.grads_r + (size_t)b * np * rd, stream));
+        }
+        // B9: with the per-element kl_divergence the total is a (B,) tensor that is summed: the two scalar cosine losses enter B times
+        const float times = c->loss_kind == MVNERF_LOSS_KL_DIVERGENCE ? (float)B : 1.0f;
+        MV_RC(mvnerf_cosine_loss(w.grads_t, c->label_grad_t, M, 3, c->w_t * times, w.c_t, c->scalars + 1, stream));
+        MV_RC(mvnerf_cosine_loss(w.grads_r, c->label_grad_r, M, rd, c->w_r * times, w.c_r, c->scalars + 2, stream));
+        hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(kMeanThreads), 0, st, c->prediction, M, c->scalars + 3);
+        MV_HIP(hipGetLastError(), kWho);
+        if (!padded) {                                                                                                              // B10
+            MV_RC(mvnerf_pose_query_jvp(c->rot_grad, c->rep, c->offsets, w.c_t, w.c_r, B * np, n5, 1, N, w.t_points, w.t_dirs, stream));
+        } else {
+            for (int b = 0; b < B; ++b)
+                MV_RC(mvnerf_pose_query_jvp(c->rot_grad + (size_t)b * np * rd, c->rep, c->offsets, w.c_t + (size_t)b * np * 3,
+                                            w.c_r + (size_t)b * np * rd, np, n5, 1, w.ld, w.t_points + (size_t)b * w.ld * 3,
+                                            w.t_dirs + (size_t)b * w.ld * 3, stream));
+        }
+        MV_RC(mvnerf_query_jvp(w.points, w.dirs, w.t_points, w.t_dirs, c->images, c->features, c->intrinsics, c->extrinsics_inv, c->packed_net, B, V,
+                               (int)w.ld, c->H, c->W, nullptr, w.t_acts_p, w.jvp_ws, stream));                                        // B11
+        if (padded) MV_RC(copy_rows(w.t_acts_p, w.t_acts, w.ld, w.n));
+        // B12: the derivative of the head VJP; dW_k = g_u_k^T t_k + p_k^T a_k, db_k = sum p_k, dW_c = g_v^T r + m^T c, db_c = sum m
+        MV_RC(mvnerf_grasp_head_vjp_bwd(w.t_acts, w.g_x, w.c, w.y, w.q, w.head_packed, N, w.out_gy, w.r, w.m, w.p, stream));
+        MV_RC(tn({w.g_u, 64, 256}, {w.t_acts, N * 128, 128}, {w.p, 64, 256}, {w.acts, N * 128, 128}, 2, w.g2 + gl.w4, w.g2 + gl.b4, NR, 64, 128, 4, sc,
+                 stream));
+        MV_RC(tn({w.g_v, 0, 64}, {w.r, 0, 256}, {w.m, 0, 64}, {w.c, 0, 256}, 2, w.g2 + gl.wc, w.g2 + gl.bc, NR, 64, 256, 1, sc, stream));
+        // B13: the derivative of the tail VJP with t_x = out_gy (the sums of include/mvnerf_hip.h, mvnerf_grasp_tail_vjp_bwd)
+        MV_RC(mvnerf_grasp_tail_vjp_bwd(w.y, w.out_gy, nullptr, w.tail_stash, w.cot, w.tail_packed, M, n5, w.out_gs, w.out_x, w.cot2, w.tan, w.dex,
+                                        stream));
+        MV_RC(tn({w.cot, 0, 320}, {w.dex, 0, K}, {w.cot2, 0, 256}, {w.ex, 0, K}, 2, w.g2 + gl.w0, w.g2 + gl.b0, M8, 128, K, 1, sc, stream));
+        MV_RC(tn({w.cot + 128, 0, 320}, {w.out_gy, 0, K}, {w.cot2 + 128, 0, 256}, {w.y, 0, K}, 2, w.g2 + gl.ws, w.g2 + gl.b1, M8, 64, K, 1, sc, stream));
+        MV_RC(tn({w.cot + 128, 0, 320}, {w.tan, 0, 320}, {w.cot2 + 128, 0, 256}, {w.act, 0, 320}, 0, w.g2 + gl.w1, nullptr, M8, 64, 128, 1, sc, stream));
+        MV_RC(tn({w.cot + 192, 0, 320}, {w.tan + 128, 0, 320}, {w.cot2 + 192, 0, 256}, {w.act + 128, 0, 320}, 2, w.g2 + gl.w0b, w.g2 + gl.b0b, M8, 64,
+                 64, 1, sc, stream));
+        MV_RC(tn({w.cot + 256, 0, 320}, {w.tan + 192, 0, 320}, kNone, kNone, 0, w.g2 + gl.w1b, nullptr, M8, 64, 64, 1, sc, stream));
+        hipLaunchKernelGGL(colsum64_kernel, dim3(1), dim3(64 * kColsumLanes), 0, st, w.tan + 256, 320, M, w.g2 + gl.w_out, (const float*)nullptr, (float*)nullptr);
+        MV_HIP(hipGetLastError(), kWho);
+        // B14: out_x back through the head: the third contribution to the head gradients
+        MV_RC(head_first(w.out_x, w.g3));
+        hipLaunchKernelGGL(sum_grads_kernel, dim3((unsigned)((gl.total + 255) / 256)), dim3(256), 0, st, w.g1, w.g2, w.g3, gl.total, kHeadGrad, c->grads);
+        MV_HIP(hipGetLastError(), kWho);
+        return 0;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+size_t mvnerf_language_grad_floats(int n5) { return n5 > 0 && n5 <= 4096 ? (size_t)grad_layout(n5).total : 0; }
+
+size_t mvnerf_language_workspace_bytes(int B, int V, int H, int W, int np, int n5) {
+    if (!sizes_ok(B, V, H, W, np, n5)) return 0;
+    return carve(nullptr, B, V, np, n5).bytes;
+}
+
+int mvnerf_language_loss_and_grads(const mvnerf_language_call* call, mvnerf_stream_t stream) {
+    Step s;
+    MV_RC(validate(call, &s.w));
+    s.c = call;
+    s.stream = stream;
+    s.st = static_cast<hipStream_t>(stream);
+    s.gl = grad_layout(call->n5);
+    s.K = 64 * call->n5;
+    s.padded = s.w.ld > s.w.n;
+    return s.run();
+}
+
+}  // extern "C"

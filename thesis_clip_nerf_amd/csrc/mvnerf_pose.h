@@ -109,6 +109,48 @@ MVP_HD void pose_vjp(int rep, const float* rot, const float* acc, float scale, f
     }
 }
 
+// ---- forward mode (LanguageNeRF.train_step, model_v4.py:290-322: the loss on d prediction / d pose is differentiated through the pose
+// map a second time; the pose VJP is linear in its cotangent, so that derivative is this product) ----
+// dR (row-major 3x3) = the derivative of rotation(rep, rot) along c_rot.
+MVP_HD void rotation_jvp(int rep, const float* rot, const float* c_rot, float* dR) {
+    if (rep == kRepQuaternion) {
+        // term for term the derivative of the tfg form above, q as given (not normalised)
+        const float x = rot[0], y = rot[1], z = rot[2], w = rot[3];
+        const float dx = c_rot[0], dy = c_rot[1], dz = c_rot[2], dw = c_rot[3];
+        const float dxx = 4.0f * (x * dx), dyy = 4.0f * (y * dy), dzz = 4.0f * (z * dz);          // d(2 x x) ...
+        const float dxy = 2.0f * (x * dy + y * dx), dxz = 2.0f * (x * dz + z * dx), dyz = 2.0f * (y * dz + z * dy);
+        const float dwx = 2.0f * (w * dx + x * dw), dwy = 2.0f * (w * dy + y * dw), dwz = 2.0f * (w * dz + z * dw);
+        dR[0] = -(dyy + dzz); dR[1] = dxy - dwz;    dR[2] = dxz + dwy;
+        dR[3] = dxy + dwz;    dR[4] = -(dxx + dzz); dR[5] = dyz - dwx;
+        dR[6] = dxz - dwy;    dR[7] = dyz + dwx;    dR[8] = -(dxx + dyy);
+    } else {
+        float c[6], dc[6];
+        for (int h = 0; h < 2; ++h) {                       // r = a / ||a||: dr = (da - r (r . da)) / ||a||
+            const float* a = rot + 3 * h;
+            const float* da = c_rot + 3 * h;
+            const float n = sqrtf(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+            float* r = c + 3 * h;
+            r[0] = a[0] / n; r[1] = a[1] / n; r[2] = a[2] / n;
+            const float rd = (r[0] * da[0] + r[1] * da[1]) + r[2] * da[2];
+            for (int i = 0; i < 3; ++i) dc[3 * h + i] = (da[i] - r[i] * rd) / n;
+        }
+        const float* r1 = c;
+        const float* r2 = c + 3;
+        const float* d1 = dc;
+        const float* d2 = dc + 3;
+        // r3 = r1 x r2: dr3 = dr1 x r2 + r1 x dr2
+        const float d3[3] = {(d1[1] * r2[2] - d1[2] * r2[1]) + (r1[1] * d2[2] - r1[2] * d2[1]),
+                             (d1[2] * r2[0] - d1[0] * r2[2]) + (r1[2] * d2[0] - r1[0] * d2[2]),
+                             (d1[0] * r2[1] - d1[1] * r2[0]) + (r1[0] * d2[1] - r1[1] * d2[0])};
+        for (int i = 0; i < 3; ++i) { dR[3 * i] = d1[i]; dR[3 * i + 1] = d2[i]; dR[3 * i + 2] = d3[i]; }
+    }
+}
+
+// tangents of query_point: t_p = dR t_o + c_t, t_d = dR z_o (the same sums as query_point, R -> dR, t -> c_t)
+MVP_HD void query_point_jvp(const float* dR, const float* c_t, const float* ot, const float* oz, float* tp, float* td) {
+    query_point(dR, c_t, ot, oz, tp, td);
+}
+
 // ---- the optimiser (src/utils/optimization.py:40-69; TF 2.11 keras Adam, ExponentialDecay(init, decay_steps=1, rate, staircase=False)) ----
 struct AdamConfig {
     float lr0[2], decay[2];          // per variable: 0 = translations, 1 = rotations

@@ -6,11 +6,13 @@
 //   pose_query_vjp    : (d_points, d_dirs) -> (d_t, d_rot).  One wavefront per pose: each lane sums its rows of the B * n5 into the 12
 //                       numbers (G = dL/dR, dL/dt), a fixed butterfly combines the lanes (no atomics: the result is the same bits from run
 //                       to run), lane 0 applies the closed-form derivative of R(rot).
+//   pose_query_jvp    : (c_t, c_rot) -> (t_points, t_dirs), the forward-mode product of pose_query_points with its structure (one thread per
+//                       (pose, offset)); what LanguageNeRF.train_step's nested tape takes of the pose map (csrc/language_api.hip).
 //   pose_adam_step    : clip-by-value, Keras Adam with the exponentially decayed rate computed on the device from per-pose step counters,
 //                       post_process.  One thread per pose owns that pose's counters, so they advance without a race; which variables
 //                       train comes from a device-resident flag pair, so one captured step serves both phases.
 //
-// The math per pose is mvnerf_pose.h (also built for the host by tests/cpu_pose).  All three are tiny next to the trunk passes (bytes:
+// The math per pose is mvnerf_pose.h (also built for the host by tests/cpu_pose, tests/cpu_language).  All are tiny next to the trunk passes (bytes:
 // ~2 x B * P * n5 * 24 per step); the point is to replace ~60 torch launches per step and keep the whole step capturable.
 #include <hip/hip_runtime.h>
 
@@ -40,6 +42,30 @@ __global__ void pose_query_points_kernel(const float* __restrict__ t, const floa
         for (int i = 0; i < 3; ++i) {
             points[row * 3 + i] = pt[i];
             dirs[row * 3 + i] = dr[i];
+        }
+    }
+}
+
+// The forward-mode product of pose_query_points_kernel, same structure: one thread per (pose, offset) forms dR of its pose along c_rot and
+// writes t_point = dR t_o + c_t, t_dir = dR z_o once per scene.  Rows past P * n5 of a scene are left alone.
+__global__ void pose_query_jvp_kernel(const float* __restrict__ rot, int rep, const float* __restrict__ offsets, const float* __restrict__ c_t,
+                                      const float* __restrict__ c_rot, int P, int n5, int B, long ld, float* __restrict__ t_points,
+                                      float* __restrict__ t_dirs) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)P * n5) return;
+    const int p = (int)(idx / n5), o = (int)(idx % n5);
+    const int rd = pose::rot_dim(rep);
+    float r[6], cr[6], dR[9], ct[3], ot[3], oz[3], tp[3], td[3];
+    for (int i = 0; i < rd; ++i) { r[i] = rot[(long)p * rd + i]; cr[i] = c_rot[(long)p * rd + i]; }
+    for (int i = 0; i < 3; ++i) ct[i] = c_t[(long)p * 3 + i];
+    pose::rotation_jvp(rep, r, cr, dR);
+    pose::offset_parts(offsets + 16 * o, ot, oz);
+    pose::query_point_jvp(dR, ct, ot, oz, tp, td);
+    for (int b = 0; b < B; ++b) {
+        const long row = (long)b * ld + idx;
+        for (int i = 0; i < 3; ++i) {
+            t_points[row * 3 + i] = tp[i];
+            t_dirs[row * 3 + i] = td[i];
         }
     }
 }
@@ -136,6 +162,20 @@ int mvnerf_pose_query_vjp(const float* rot, int rep, const float* offsets, const
     hipLaunchKernelGGL(mvnerf::pose_query_vjp_kernel, dim3((unsigned)((P + waves - 1) / waves)), dim3(64 * waves), 0,
                        static_cast<hipStream_t>(stream), rot, rep, offsets, d_points, d_dirs, P, n5, B, ld, scale, d_t, d_rot);
     return hs_pose(hipGetLastError(), "mvnerf_pose_query_vjp");
+}
+
+int mvnerf_pose_query_jvp(const float* rot, int rep, const float* offsets, const float* c_t, const float* c_rot, int P, int n5, int B, long ld,
+                          float* t_points, float* t_dirs, mvnerf_stream_t stream) {
+    if (!rot || !offsets || !c_t || !c_rot || !t_points || !t_dirs) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_pose_query_jvp: null pointer");
+    if (P <= 0 || n5 <= 0 || B <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_pose_query_jvp: P=%d n5=%d B=%d", P, n5, B);
+    if (rep != 0 && rep != 1) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_query_jvp: rep=%d (0 quaternion, 1 6d)", rep);
+    if (ld < (long)P * n5) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_query_jvp: ld=%ld < P*n5=%ld", ld, (long)P * n5);
+    if (!al4(rot) || !al4(offsets) || !al4(c_t) || !al4(c_rot) || !al4(t_points) || !al4(t_dirs))
+        return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_pose_query_jvp: buffers must be 4-byte aligned");
+    const long n = (long)P * n5;
+    hipLaunchKernelGGL(mvnerf::pose_query_jvp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), rot, rep,
+                       offsets, c_t, c_rot, P, n5, B, ld, t_points, t_dirs);
+    return hs_pose(hipGetLastError(), "mvnerf_pose_query_jvp");
 }
 
 int mvnerf_pose_adam_step(const mvnerf_pose_adam_config* cfg, int rep, int P, const int* train_flags, int* counters, const float* g_t,

@@ -551,10 +551,11 @@ class LanguageNeRF(nn.Module):
         self.loss = kl_divergence if softmax_before_loss else None
         self.optimizer = None
         self._graph_mode, self._graph, self._g_static, self._g_out, self._g_calls = False, None, None, None, 0
+        self.fused_step, self.loss_weights, self._fs = False, (1.0, 1.0, 1.0), None
         self.to(self.device_)
 
     # -- reference API --
-    def compile(self, optimizer=None, loss=None, learning_rate=1e-4, graph=False, fused_tail=None):
+    def compile(self, optimizer=None, loss=None, learning_rate=1e-4, graph=False, fused_tail=None, fused_step=None, loss_weights=None):
         """graph=True: `train_step` is captured ONCE as a HIP graph (torch.cuda.CUDAGraph) and replayed: the step is ~740 launches of
         3-500 us that the host cannot issue as fast as the GPU runs them - 6.6 ms per replay against 8-10.7 ms eager at the cfg3 shape
         (profiles/r02_language_step_graph.md).  The graph fixes shapes and addresses:
@@ -562,9 +563,20 @@ class LanguageNeRF(nn.Module):
         copy), the optimizer is this method's own Adam (capturable).  The first two steps run eagerly (they load every kernel and size
         the allocator pools), the third is captured.
         fused_tail: True / False runs the read-out's per-pose layers as fused HIP passes (GraspReadout.fused_tail) or layer by layer through
-        torch; None keeps the current setting.  A captured graph is dropped either way (compile() always starts a new one)."""
+        torch; None keeps the current setting.  A captured graph is dropped either way (compile() always starts a new one).
+        fused_step: True makes `loss_and_grads` one call of mvnerf_language_loss_and_grads (csrc/language_api.hip: both passes, the pose
+        algebra, the losses and every weight gradient as HIP launches on the current stream, no autograd graph); the parameters' `.grad` are
+        views into its flat gradient, the optimizer and `graph=True` work as before.  False is the autograd path; None keeps the setting.
+        loss_weights: (landscape, grad_t, grad_r) factors of the three losses in the total that is differentiated (the reference: 1, 1, 1;
+        the returned losses stay unweighted); None keeps the setting."""
         if fused_tail is not None:
             self.set_fused_tail(fused_tail)
+        if fused_step is not None:
+            self.set_fused_step(fused_step)
+        if loss_weights is not None:
+            if len(loss_weights) != 3:
+                raise ValueError(f'loss_weights: (landscape, grad_t, grad_r), got {loss_weights!r}')
+            self.loss_weights = tuple(float(x) for x in loss_weights)
         if graph and optimizer is not None:
             raise ValueError('graph=True builds its own capturable Adam; pass learning_rate instead of an optimizer')
         self.optimizer = optimizer or torch.optim.Adam(self.grasp_readout.parameters(), lr=learning_rate, eps=1e-7, capturable=bool(graph))
@@ -579,6 +591,15 @@ class LanguageNeRF(nn.Module):
             raise ValueError(f'fused_tail must be True or False (compile: or None to keep the setting), got {fused_tail!r}')
         if fused_tail != self.grasp_readout.fused_tail:
             self.grasp_readout.fused_tail = fused_tail
+            self._graph, self._g_out, self._g_calls = None, None, 0
+
+    def set_fused_step(self, fused_step):
+        """The step up to the optimizer as one C call (compile(fused_step=...)) without touching the optimizer; a change drops a captured
+        step, like set_fused_tail."""
+        if not isinstance(fused_step, bool):
+            raise ValueError(f'fused_step must be True or False (compile: or None to keep the setting), got {fused_step!r}')
+        if fused_step != self.fused_step:
+            self.fused_step = fused_step
             self._graph, self._g_out, self._g_calls = None, None, 0
 
     # -- checkpoints (model_v4.py:132-174): torch.save'd tensors, one file per sub-model, load() -> False when a file is missing --
@@ -697,6 +718,8 @@ class LanguageNeRF(nn.Module):
 
     def loss_and_grads(self, data, combined_features):
         """The body of train_step (model_v4.py:277-318) up to the optimizer: returns (dict of losses, prediction)."""
+        if self.fused_step:
+            return self._loss_and_grads_fused(data, combined_features)
         inputs, labels = data
         dev = self.device_
         lab = [torch.as_tensor(l, dtype=torch.float32).to(dev) for l in labels]
@@ -715,12 +738,81 @@ class LanguageNeRF(nn.Module):
             loss_r = cosine_similarity_loss(lab[2], grads[1])
         else:
             loss_r = cosine_similarity_loss(lab[2][..., :3], grads[1][..., :3]) + cosine_similarity_loss(lab[2][..., 3:], grads[1][..., 3:])
-        loss = loss_t + loss_r + landscape_loss
+        if self.loss_weights == (1.0, 1.0, 1.0):
+            loss = loss_t + loss_r + landscape_loss
+        else:
+            w_land, w_t, w_r = self.loss_weights
+            loss = w_t * loss_t + w_r * loss_r + w_land * landscape_loss
         for prm in self.grasp_readout.parameters():
             prm.grad = None
         loss.sum().backward(inputs=list(self.grasp_readout.parameters()))
         return {'landscape_loss': landscape_loss.detach().mean(), 'grad_loss_t': loss_t.detach(), 'grad_loss_r': loss_r.detach(),
                 'pred': prediction.detach().mean()}, prediction.detach()
+
+    # -- the same body as one C call (compile(fused_step=True); csrc/language_api.hip) --
+    def _readout_tensors(self):
+        """The read-out's parameters in the order of mvnerf_language_call: the four per-activation layers, then (wc, bc), then the tail's 11."""
+        ro = self.grasp_readout
+        b0, b1, out = ro.block_0, ro.block_1, ro.output_layer
+        tail = {'w0': b0.layer_0.weight, 'b0': b0.layer_0.bias, 'w1': b0.layer_1.weight, 'b1': b0.layer_1.bias, 'ws': b0.shortcut.weight,
+                'w0b': b1.layer_0.weight, 'b0b': b1.layer_0.bias, 'w1b': b1.layer_1.weight, 'b1b': b1.layer_1.bias, 'w_out': out.weight,
+                'b_out': out.bias}
+        return list(ro.activation_downscale), ro.combined_activation_downscale, tail
+
+    def _fused_buffers(self, key):
+        """Everything the C step writes, allocated once per shape: the flat gradient (the parameters' `.grad` are views into it), the
+        prediction, the four scalars, the landscape poses, the stacked head weights and the workspace."""
+        if self._fs is not None and self._fs['key'] == key:
+            return self._fs
+        b, v, h, w, n_p, n5, rd = key
+        dev = self.device_
+        layout, total = ops.language_grad_layout(n5)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        grads = torch.zeros(total, dtype=torch.float32, device=dev)
+        view = lambda name: grads[layout[name][0]:layout[name][0] + int(np.prod(layout[name][1]))].view(layout[name][1])
+        heads, comb, tail = self._readout_tensors()
+        grad_views = [(comb.weight, view('wc')), (comb.bias, view('bc'))]
+        grad_views += [(lin.weight, view('w4')[k]) for k, lin in enumerate(heads)] + [(lin.bias, view('b4')[k]) for k, lin in enumerate(heads)]
+        grad_views += [(prm, view(name)) for name, prm in tail.items()]
+        self._fs = {'key': key, 'grads': grads, 'grad_views': grad_views, 'prediction': f32(b, n_p), 'scalars': f32(4), 't_l': f32(b, n_p, 3),
+                    'r_l': f32(b, n_p, rd), 'w4': f32(4, 64, 128), 'b4': f32(4, 64),
+                    'workspace': torch.empty(ops.language_workspace_bytes(b, v, h, w, n_p, n5), dtype=torch.uint8, device=dev)}
+        return self._fs
+
+    def _loss_and_grads_fused(self, data, combined_features):
+        if self.loss is kl_divergence and self.softmax_before_loss:
+            kind = 'kl_divergence'
+        elif self.loss is categorical_crossentropy_from_logits and not self.softmax_before_loss:
+            kind = 'cross_entropy'
+        else:
+            raise ValueError('fused_step: the C step knows kl_divergence after a softmax and categorical_crossentropy_from_logits without one '
+                             '(train_language.select_loss); use fused_step=False for another loss')
+        if self.grasp_readout.output_layer.bias is None:
+            raise ValueError('fused_step: the read-out needs its output bias')
+        inputs, labels = data
+        dev = self.device_
+        lab = [torch.as_tensor(l, dtype=torch.float32).to(dev).contiguous() for l in labels]
+        state = self.trunk_state(inputs, combined_features)
+        images, features = state.geo[0], state.geo[1]
+        b, v, h, w = images.shape[:4]
+        n_p, n5, rd = self.n_points_train, self.n_transforms_to_check, self.rotations.shape[-1]
+        fs = self._fused_buffers((b, v, h, w, n_p, n5, rd))
+        heads, comb, tail = self._readout_tensors()
+        with torch.no_grad():
+            fs['t_l'].copy_(torch.as_tensor(inputs[0], dtype=torch.float32), non_blocking=True)
+            fs['r_l'].copy_(torch.as_tensor(inputs[1], dtype=torch.float32), non_blocking=True)
+            torch.stack([lin.weight.detach() for lin in heads], out=fs['w4'])
+            torch.stack([lin.bias.detach() for lin in heads], out=fs['b4'])
+        self.set_pose(inputs[2], inputs[3])
+        call = ops.language_call(*state.geo, state.packed, state.packed_split, state.bwd_streams,
+                                 (fs['w4'], fs['b4'], comb.weight.detach(), comb.bias.detach()), [t.detach() for t in tail.values()],
+                                 self.transforms_to_check, (fs['t_l'], fs['r_l'], self.translations.detach(), self.rotations.detach()), lab, kind,
+                                 self.loss_weights, fs['grads'], fs['prediction'], fs['scalars'], fs['workspace'])
+        ops.language_loss_and_grads(call, features)
+        for prm, g in fs['grad_views']:
+            prm.grad = g
+        s = fs['scalars'].clone()
+        return {'landscape_loss': s[0], 'grad_loss_t': s[1], 'grad_loss_r': s[2], 'pred': s[3]}, fs['prediction'].clone()
 
     def _clip_and_step(self):
         for prm in self.grasp_readout.parameters():                      # optimize(): clip-by-value 1.0, then Adam

@@ -1255,6 +1255,139 @@ def pose_query_vjp(rot, offsets, d_points, d_dirs, scale=1.0, out=None):
     return d_t, d_rot
 
 
+def pose_query_jvp(rot, offsets, c_t, c_rot, n_scenes=1, ld=None, out=None):
+    """mvnerf_pose_query_jvp: tangents (c_t (P, 3), c_rot (P, 4|6)) of the poses -> (t_points, t_dirs), each (n_scenes, ld, 3), rows
+    p * n5 + o (rows past P * n5 are not written).  out: a (t_points, t_dirs) pair to write into."""
+    p, rep, rd = _rot_shape(rot)
+    _chk(offsets, 'offsets', shape=(None, 4, 4))
+    n5 = offsets.shape[0]
+    _chk(c_t, 'c_t', shape=(p, 3))
+    _chk(c_rot, 'c_rot', shape=(p, rd))
+    ld = p * n5 if ld is None else int(ld)
+    if out is None:
+        out = tuple(torch.empty((n_scenes, ld, 3), dtype=torch.float32, device=rot.device) for _ in range(2))
+    t_points, t_dirs = out
+    _chk(t_points, 't_points', shape=(n_scenes, ld, 3))
+    _chk(t_dirs, 't_dirs', shape=(n_scenes, ld, 3))
+    with torch.cuda.device(rot.device):
+        rc = _lib.lib().mvnerf_pose_query_jvp(_p(rot), rep, _p(offsets), _p(c_t), _p(c_rot), p, n5, int(n_scenes), ld, _p(t_points), _p(t_dirs),
+                                              _stream(rot))
+    _lib.check(rc, 'pose_query_jvp')
+    return t_points, t_dirs
+
+
+# ---- the LanguageNeRF training step behind the C ABI (csrc/language_ops.hip, language_api.hip; lmvnerf/model_v4.py:277-318) ----------------
+LANGUAGE_LOSSES = {'kl_divergence': 0, 'cross_entropy': 1}
+
+
+def landscape_loss(y, label, kind, weight=1.0):
+    """mvnerf_landscape_loss: predicted success y (B, np) against label -> (loss (1,) = the mean over the batch, g_y (B, np))."""
+    _chk(y, 'y', shape=(None, None))
+    b, n_p = y.shape
+    _chk(label, 'label', shape=(b, n_p))
+    g_y = torch.empty_like(y)
+    loss = torch.empty(1, dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        rc = _lib.lib().mvnerf_landscape_loss(_p(y), _p(label), b, n_p, LANGUAGE_LOSSES[kind], float(weight), _p(g_y), _p(loss), _stream(y))
+    _lib.check(rc, 'landscape_loss')
+    return loss, g_y
+
+
+def cosine_loss(x, label, scale=1.0):
+    """mvnerf_cosine_loss: x, label (..., 3|4|6) (6: the two 3-halves separately, added) -> (loss (1,), g_x = scale * d loss / d x)."""
+    _chk(x, 'x')
+    dim = x.shape[-1]
+    _chk(label, 'label', shape=tuple(x.shape))
+    g_x = torch.empty_like(x)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().mvnerf_cosine_loss(_p(x), _p(label), x.numel() // max(dim, 1), dim, float(scale), _p(g_x), _p(loss), _stream(x))
+    _lib.check(rc, 'cosine_loss')
+    return loss, g_x
+
+
+def language_grad_layout(n5):
+    """name -> (offset, shape) of every read-out variable inside the flat gradient of mvnerf_language_loss_and_grads (include/mvnerf_hip.h)."""
+    k = 64 * n5
+    shapes = (('w4', (4, 64, 128)), ('b4', (4, 64)), ('wc', (64, 256)), ('bc', (64,)), ('w0', (128, k)), ('b0', (128,)), ('w1', (64, 128)),
+              ('b1', (64,)), ('ws', (64, k)), ('w0b', (64, 64)), ('w1b', (64, 64)), ('b0b', (64,)), ('b1b', (64,)), ('w_out', (1, 64)),
+              ('b_out', (1,)))
+    layout, at = {}, 0
+    for name, shape in shapes:
+        layout[name] = (at, shape)
+        at += int(np.prod(shape))
+    if at != int(_lib.lib().mvnerf_language_grad_floats(int(n5))):
+        raise RuntimeError('language_grad_layout disagrees with mvnerf_language_grad_floats')
+    return layout, at
+
+
+def language_workspace_bytes(b, v, h, w, n_p, n5):
+    return int(_lib.lib().mvnerf_language_workspace_bytes(int(b), int(v), int(h), int(w), int(n_p), int(n5)))
+
+
+_TAIL_ORDER = ('w0', 'b0', 'w1', 'b1', 'ws', 'w0b', 'b0b', 'w1b', 'b1b', 'w_out', 'b_out')
+
+
+def language_call(images, features, intrinsics, extrinsics_inv, packed_net, split, bwd_streams, head, tail, offsets, poses, labels, loss_kind,
+                  loss_weights, grads, prediction, scalars, workspace):
+    """Fill a mvnerf_language_call (include/mvnerf_hip.h) from device tensors after checking shapes; the caller keeps the tensors alive.
+    head = (w4 (4,64,128), b4 (4,64), wc (64,256), bc (64,)); tail = the 11 tensors of grasp_tail_pack in its order; poses = (t_landscape,
+    rot_landscape, t_grad, rot_grad), each (B, np, .); labels = (landscape (B, np), grad_t (B, np, 3), grad_r (B, np, 4|6))."""
+    b, v, h, w = _scene(images, features, intrinsics, extrinsics_inv)
+    _chk(packed_net, 'packed_net', shape=(packed_net_floats(),))
+    _chk(split, 'split', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_packed_net_split_bytes()),))
+    _chk(bwd_streams, 'bwd_streams', shape=(15 * 16384,))
+    _chk(offsets, 'offsets', shape=(None, 4, 4))
+    n5 = offsets.shape[0]
+    k = 64 * n5
+    for t, name, shape in zip(head, ('w4', 'b4', 'wc', 'bc'), ((4, 64, 128), (4, 64), (64, 256), (64,))):
+        _chk(t, 'head ' + name, shape=shape)
+    tail_shapes = ((128, k), (128,), (64, 128), (64,), (64, k), (64, 64), (64,), (64, 64), (64,), None, (1,))
+    if len(tail) != 11:
+        raise ValueError('tail: the 11 tensors of grasp_tail_pack')
+    for t, name, shape in zip(tail, _TAIL_ORDER, tail_shapes):
+        _chk(t, 'tail ' + name, shape=shape)
+    if tail[9].numel() != 64:
+        raise ValueError(f'tail w_out: shape {tuple(tail[9].shape)}, expected (1, 64)')
+    t_l, r_l, t_g, r_g = poses
+    _chk(t_l, 't_landscape', shape=(b, None, 3))
+    n_p = t_l.shape[1]
+    rd = r_l.shape[-1]
+    if rd not in POSE_REPS:
+        raise ValueError(f'rot_landscape: shape {tuple(r_l.shape)}, expected (B, np, 4|6)')
+    _chk(r_l, 'rot_landscape', shape=(b, n_p, rd))
+    _chk(t_g, 't_grad', shape=(b, n_p, 3))
+    _chk(r_g, 'rot_grad', shape=(b, n_p, rd))
+    _chk(labels[0], 'label_landscape', shape=(b, n_p))
+    _chk(labels[1], 'label_grad_t', shape=(b, n_p, 3))
+    _chk(labels[2], 'label_grad_r', shape=(b, n_p, rd))
+    _chk(grads, 'grads', shape=(int(_lib.lib().mvnerf_language_grad_floats(n5)),))
+    _chk(prediction, 'prediction', shape=(b, n_p))
+    _chk(scalars, 'scalars', shape=(4,))
+    _chk(workspace, 'workspace', dtype=torch.uint8)
+    c = _lib.LanguageCall()
+    for name, x in (('images', images), ('features', features), ('intrinsics', intrinsics), ('extrinsics_inv', extrinsics_inv),
+                    ('packed_net', packed_net), ('split', split), ('bwd_streams', bwd_streams), ('head_w4', head[0]), ('head_b4', head[1]),
+                    ('head_wc', head[2]), ('head_bc', head[3]), ('offsets', offsets), ('t_landscape', t_l), ('rot_landscape', r_l),
+                    ('t_grad', t_g), ('rot_grad', r_g), ('label_landscape', labels[0]), ('label_grad_t', labels[1]),
+                    ('label_grad_r', labels[2]), ('grads', grads), ('prediction', prediction), ('scalars', scalars), ('workspace', workspace)):
+        setattr(c, name, x.data_ptr())
+    for i, t in enumerate(tail):
+        c.tail_w[i] = t.data_ptr()
+    c.B, c.V, c.H, c.W = b, v, h, w
+    c.rep, c.np, c.n5 = POSE_REPS[rd], n_p, n5
+    c.loss_kind = LANGUAGE_LOSSES[loss_kind] if isinstance(loss_kind, str) else int(loss_kind)
+    c.w_land, c.w_t, c.w_r = (float(x) for x in loss_weights)
+    c.workspace_bytes = workspace.numel()
+    return c
+
+
+def language_loss_and_grads(call, stream_of):
+    """mvnerf_language_loss_and_grads on a filled language_call -> its grads, prediction, scalars."""
+    with torch.cuda.device(stream_of.device):
+        _lib.check(_lib.lib().mvnerf_language_loss_and_grads(ctypes.byref(call), _stream(stream_of)), 'language_loss_and_grads')
+
+
 def pose_adam_config(lr0=(0.09, 0.09), decay=(1.0, 1.0), beta1=0.9, beta2=0.999, eps=1e-7, clip=1.0, clip_translation=False, bounds=None):
     """mvnerf_pose_adam_config: lr0 / decay per variable (translations, rotations); bounds (3, 2) = workspace_bounds."""
     bounds = np.zeros((3, 2)) if bounds is None else np.asarray(bounds, dtype=np.float64).reshape(3, 2)
