@@ -158,7 +158,7 @@ int mvnerf_field_eval_bf16maps(const float* rays_o, const float* rays_d, const f
  *   MVNERF_SPLIT_F16X3 (default)  two fp16 pieces per operand (round-to-nearest twice, the remainder scaled by 64: 22-24 significant
  *                                 bits), three v_mfma_f32_16x16x32_f16 per block; per ResNet block as close to a float64 evaluation as
  *                                 the fp32 MFMA (tests/test_gpu_split.py); range |w| < 1023, |activation| < 4.19e6
- *                                 (csrc/field_eval_split16_impl.h, field_eval_split16h.hip)
+ *                                 (MVNERF_F16X3_MAX_WEIGHT / _MAX_ACT below; csrc/field_eval_split16_impl.h, field_eval_split16h.hip)
  *   MVNERF_SPLIT_BF16X6           three bf16 pieces per operand, an EXACT cut, the six products of order >= 2^-16 as
  *                                 v_mfma_f32_16x16x32_bf16; dropped terms <= 2^-24 relative; full fp32 range (field_eval_split16.hip)
  *   MVNERF_SPLIT_BF16X6_32        the same products as v_mfma_f32_32x32x16_bf16 (round 2's kernel, field_eval_split.hip)
@@ -167,6 +167,16 @@ int mvnerf_field_eval_bf16maps(const float* rays_o, const float* rays_d, const f
 #define MVNERF_SPLIT_F16X3 0
 #define MVNERF_SPLIT_BF16X6 1
 #define MVNERF_SPLIT_BF16X6_32 2
+/* Range of MVNERF_SPLIT_F16X3.  Its weight pieces are rn16(64 w), its activation pieces rn16(v / 64), and fp16 rounds to infinity from
+ * 65520 upward: the kernel is correct for |w| < 1023.75 and |v| < 4193280 and silently wrong beyond (inf - inf inside the products; a
+ * relu can turn the NaN into 0, so the output need not show it).  The two constants are those thresholds, slightly conservative.
+ * Weights: mvnerf_net_range.  Activations: the range status of the _ex entry points.  Out of range, run MVNERF_SPLIT_BF16X6 (same
+ * packed_split image, full fp32 range).
+ * The training BACKWARD is tighter: its weight-gradient GEMM cuts relu(stashed pre-activation) as rn16(64 a), so every stashed
+ * pre-activation has to stay below MVNERF_F16X3_MAX_WEIGHT as well - 4096 times less than the forward allows.  That limit is detected
+ * (range status of mvnerf_field_eval_stash_split_ex against MVNERF_F16X3_MAX_WEIGHT), not lifted. */
+#define MVNERF_F16X3_MAX_WEIGHT 1023.0f
+#define MVNERF_F16X3_MAX_ACT 4.19e6f
 /* Process-wide choice of the kernel behind mvnerf_field_eval_split / mvnerf_render_fwd_split; returns the previous value (< 0 and
  * no change for an unknown value).  The environment variable MVNERF_SPLIT_MFMA ("f16x3" | "bf16x6" | "32x32x16"), read at every
  * launch, overrides it (A/B runs, tests). */
@@ -182,6 +192,25 @@ int mvnerf_field_eval_split(const float* rays_o, const float* rays_d, const floa
                             const float* packed_net, const void* packed_split, int B, int V, int R, int S, int H, int W,
                             float* rgbs, int32_t* tap_idx, float* pix, float* embedding, float* acts_per_view, float* acts_fused,
                             void* workspace, mvnerf_stream_t stream);
+/* mvnerf_field_eval_split with the kernel chosen for THIS call and an optional range status.
+ * which: -1 = the process-wide value (mvnerf_set_split_kernel), or MVNERF_SPLIT_F16X3 / _BF16X6 / _BF16X6_32 for this call only; any
+ *   other value is MVNERF_E_ARG.  MVNERF_SPLIT_MFMA in the environment still overrides both.
+ * range_status (optional, may be NULL): ONE device float, 4-byte aligned (else MVNERF_E_ALIGN).  When the f16x3 kernel runs the pass, its
+ *   range-guarded copy runs instead (csrc/field_eval_split16h_guard.hip; bit-identical results) and max-accumulates into it the largest
+ *   |v| of every value it cuts into fp16 activation pieces: the PE / rgb operands, the gathered features (direct form), and relu(x),
+ *   relu(h) in front of every hidden Dense layer, per view and fused (after the relu).  Compare with MVNERF_F16X3_MAX_ACT.  The caller
+ *   zeroes it; calls accumulate (the chunks of a frame).  It is the bit pattern of a non-negative float under an unsigned max: a NaN operand
+ *   leaves a NaN, infinity leaves infinity.  The other two kernels have the full fp32 range and leave it untouched.  Nothing is read back:
+ *   reading the status is the caller's synchronisation. */
+int mvnerf_field_eval_split_ex(const float* rays_o, const float* rays_d, const float* z, const float* images,
+                               const float* features, const float* texel_table, const float* intrinsics, const float* extrinsics_inv,
+                               const float* packed_net, const void* packed_split, int B, int V, int R, int S, int H, int W,
+                               float* rgbs, int32_t* tap_idx, float* pix, float* embedding, float* acts_per_view, float* acts_fused,
+                               void* workspace, int which, float* range_status, mvnerf_stream_t stream);
+/* Weight range of a Keras-order net (247300 floats, see mvnerf_pack_net), two device floats, same bit-pattern convention (NaN stays NaN):
+ * out2[0] = max |w| over what mvnerf_pack_net_split cuts into 16-bit pieces (the 379 rows of W0 and the 12 hidden kernels; no bias, no
+ * read-out) - compare with MVNERF_F16X3_MAX_WEIGHT;  out2[1] = max |.| over all variables.  out2: 4-byte aligned; overwritten. */
+int mvnerf_net_range(const float* net_keras, float* out2, mvnerf_stream_t stream);
 
 /* MVVNeRFRenderer.volumetric_render (model_v0.py:89-100) with sigma_to_alpha (nerf_utils.py:129-140).
  * z (n_rays,S); rgbs (n_rays,S,4); S in {64,128,192,256}.
@@ -276,6 +305,14 @@ int mvnerf_field_eval_stash_split(const float* rays_o, const float* rays_d, cons
                                   const float* features, const float* texel_table, const float* intrinsics,
                                   const float* extrinsics_inv, const float* packed_net, const void* packed_split, int B, int V, int R,
                                   int S, int H, int W, float* rgbs, float* stash, void* workspace, mvnerf_stream_t stream);
+/* ... with `which` and `range_status` as in mvnerf_field_eval_split_ex.  The stash holds the very fp32 values that are cut, so the status is
+ * max(relu(stash)) joined with the layer-0 operands.  For training compare it with MVNERF_F16X3_MAX_WEIGHT: the backward cuts
+ * relu(pre-activation) as a weight-side operand (see the constants). */
+int mvnerf_field_eval_stash_split_ex(const float* rays_o, const float* rays_d, const float* z, const float* images,
+                                     const float* features, const float* texel_table, const float* intrinsics,
+                                     const float* extrinsics_inv, const float* packed_net, const void* packed_split, int B, int V, int R,
+                                     int S, int H, int W, float* rgbs, float* stash, void* workspace, int which, float* range_status,
+                                     mvnerf_stream_t stream);
 
 /* The 12 hidden Dense kernels of one MLP and the three 128-row slabs of the layer-0 kernel, transposed, in
  * weight-stream order (15 x 16384 floats), for the dX GEMMs of the backward pass.
@@ -713,6 +750,13 @@ int mvnerf_render_fwd_split(const float* rays_o, const float* rays_d, const floa
                             const float* u_fine, int B, int V, int R, int S, int H, int W, double near_, double far_, int q7_mode,
                             float* rgb, float* depth, float* fine_rgb, float* fine_depth, void* workspace, float* texel_tables,
                             int tables_ready, mvnerf_stream_t stream);
+/* ... with `which` and `range_status` as in mvnerf_field_eval_split_ex; range_status here is TWO floats: [0] the coarse pass, [1] the fine pass. */
+int mvnerf_render_fwd_split_ex(const float* rays_o, const float* rays_d, const float* images, const float* features,
+                               const float* intrinsics, const float* extrinsics_inv, const float* packed_coarse,
+                               const float* packed_fine, const void* split_coarse, const void* split_fine, const float* u_coarse,
+                               const float* u_fine, int B, int V, int R, int S, int H, int W, double near_, double far_, int q7_mode,
+                               float* rgb, float* depth, float* fine_rgb, float* fine_depth, void* workspace, float* texel_tables,
+                               int tables_ready, int which, float* range_status, mvnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get('MVNERF_LIB', os.path.join(_HERE, 'lib', 'libmvnerf_hi
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'mvnerf_hip.h')
 
 NET_PARAMS = 247300
+F16X3_MAX_WEIGHT = 1023.0          # MVNERF_F16X3_MAX_WEIGHT (also the training backward's limit on stashed pre-activations)
+F16X3_MAX_ACT = 4.19e6             # MVNERF_F16X3_MAX_ACT
 Q7_ZERO, Q7_CLAMP = 0, 1
 
 
@@ -100,6 +102,8 @@ SIGNATURES = {
     'mvnerf_packed_net_split_bytes': (c_size_t, []),
     'mvnerf_pack_net_split': (c_int, [c_void_p, c_void_p, c_void_p]),
     'mvnerf_field_eval_split': (c_int, [c_void_p] * 10 + [c_int] * 6 + [c_void_p] * 8),
+    'mvnerf_field_eval_split_ex': (c_int, [c_void_p] * 10 + [c_int] * 6 + [c_void_p] * 7 + [c_int, c_void_p, c_void_p]),
+    'mvnerf_net_range': (c_int, [c_void_p, c_void_p, c_void_p]),
     'mvnerf_field_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'mvnerf_composite': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mvnerf_resample': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -120,6 +124,7 @@ SIGNATURES = {
     'mvnerf_field_backward_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'mvnerf_field_eval_stash': (c_int, [c_void_p] * 9 + [c_int] * 6 + [c_void_p] * 4),
     'mvnerf_field_eval_stash_split': (c_int, [c_void_p] * 10 + [c_int] * 6 + [c_void_p] * 4),
+    'mvnerf_field_eval_stash_split_ex': (c_int, [c_void_p] * 10 + [c_int] * 6 + [c_void_p] * 3 + [c_int, c_void_p, c_void_p]),
     'mvnerf_pack_bwd_streams': (c_int, [c_void_p, c_void_p, c_void_p]),
     'mvnerf_mse_grad': (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     'mvnerf_composite_bwd': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -168,6 +173,8 @@ SIGNATURES = {
                           [c_int, c_void_p]),
     'mvnerf_render_fwd_split': (c_int, [c_void_p] * 12 + [c_int] * 6 + [c_double, c_double, c_int] + [c_void_p] * 6 +
                                 [c_int, c_void_p]),
+    'mvnerf_render_fwd_split_ex': (c_int, [c_void_p] * 12 + [c_int] * 6 + [c_double, c_double, c_int] + [c_void_p] * 6 +
+                                   [c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

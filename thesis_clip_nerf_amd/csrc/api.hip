@@ -1,6 +1,7 @@
 // extern "C" surface of libmvnerf_hip.so (include/mvnerf_hip.h): argument validation, launch
-// orchestration, error reporting.  No allocation, no host synchronisation, no global state besides
-// the thread-local error string; safe to call from one process per GPU on any stream.
+// orchestration, error reporting.  No allocation, no host synchronisation; global state: the thread-local
+// error string and the two process-wide switches mvnerf_set_split_kernel / mvnerf_set_deterministic (the
+// _ex entry points choose the split kernel per call instead); safe to call from one process per GPU on any stream.
 // Of several faults in one call the first in this order is reported: null pointers, sizes, int32 index
 // ranges, alignment.
 #include <hip/hip_runtime.h>
@@ -38,6 +39,19 @@ int hip_status(hipError_t e, const char* what) {
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// The two arguments the _ex entry points add: `which` (-1 or a MVNERF_SPLIT_* value) is checked before everything else, the
+// alignment of `range_status` with the other alignments (after them).
+int split_choice_check(const char* who, int which) {
+    if (which < -1 || which > MVNERF_SPLIT_BF16X6_32)
+        return fail(MVNERF_E_ARG, "%s: which=%d (-1 process-wide, 0 f16x3, 1 bf16x6, 2 bf16x6 as 32x32x16)", who, which);
+    return 0;
+}
+int range_status_check(const char* who, const float* range_status) {
+    if (!aligned4(range_status)) return fail(MVNERF_E_ALIGN, "%s: range_status must be 4-byte aligned", who);
+    return 0;
+}
 
 struct Workspace {          // carve-up of the caller's scratch for mvnerf_render_fwd (floats)
     float *z, *rgbs_c, *weights, *z_all, *rgbs_f, *dir_bias;
@@ -114,12 +128,15 @@ int field_params(const char* who, const FieldArgs& a, FieldKind kind, mvnerf::Fi
     return 0;
 }
 
-int field_pass(const char* who, const FieldArgs& a, FieldKind kind, mvnerf_stream_t stream) {
+// which / range_status: the split kernel of this call and its optional range status (the _ex entry points); the others pass -1, NULL
+int field_pass(const char* who, const FieldArgs& a, FieldKind kind, mvnerf_stream_t stream, int which = -1, float* range_status = nullptr) {
+    if (const int rc = split_choice_check(who, which)) return rc;
     mvnerf::FieldParams p;
     if (const int rc = field_params(who, a, kind, &p)) return rc;
+    if (const int rc = range_status_check(who, range_status)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (kind.kernel == kFieldFp32) return hip_status(mvnerf::launch_field_eval(p, st), who);
-    if (kind.kernel == kFieldSplit) return hip_status(mvnerf::launch_field_eval_split(p, a.second, st), who);
+    if (kind.kernel == kFieldSplit) return hip_status(mvnerf::launch_field_eval_split(p, a.second, st, which, range_status), who);
     return hip_status(mvnerf::launch_field_eval_bf16(p, a.second, st, kind.kernel == kFieldBf16Maps), who);
 }
 
@@ -271,6 +288,22 @@ int mvnerf_field_eval_split(const float* rays_o, const float* rays_d, const floa
     const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, packed_split, B, V, R, S, H, W,
                          rgbs, tap_idx, pix, embedding, acts_per_view, acts_fused, nullptr, workspace};
     return field_pass("mvnerf_field_eval_split", a, {kFieldSplit, false, MVNERF_E_SHAPE}, stream);
+}
+
+int mvnerf_field_eval_split_ex(const float* rays_o, const float* rays_d, const float* z, const float* images,
+                               const float* features, const float* texel_table, const float* intrinsics, const float* extrinsics_inv,
+                               const float* packed_net, const void* packed_split, int B, int V, int R, int S, int H, int W,
+                               float* rgbs, int32_t* tap_idx, float* pix, float* embedding, float* acts_per_view, float* acts_fused,
+                               void* workspace, int which, float* range_status, mvnerf_stream_t stream) {
+    const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, packed_split, B, V, R, S, H, W,
+                         rgbs, tap_idx, pix, embedding, acts_per_view, acts_fused, nullptr, workspace};
+    return field_pass("mvnerf_field_eval_split_ex", a, {kFieldSplit, false, MVNERF_E_SHAPE}, stream, which, range_status);
+}
+
+int mvnerf_net_range(const float* net_keras, float* out2, mvnerf_stream_t stream) {
+    if (!net_keras || !out2) return fail(MVNERF_E_ARG, "mvnerf_net_range: null pointer");
+    if (!aligned4(out2)) return fail(MVNERF_E_ALIGN, "mvnerf_net_range: out2 must be 4-byte aligned");
+    return hip_status(mvnerf::launch_net_range(net_keras, out2, static_cast<hipStream_t>(stream)), "mvnerf_net_range");
 }
 
 int mvnerf_composite(const float* z, const float* rgbs, int n_rays, int S, float* rgb, float* depth, float* weights,
@@ -428,6 +461,16 @@ int mvnerf_field_eval_stash_split(const float* rays_o, const float* rays_d, cons
     const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, packed_split, B, V, R, S, H, W,
                          rgbs, nullptr, nullptr, nullptr, nullptr, nullptr, stash, workspace};
     return field_pass("mvnerf_field_eval_stash_split", a, {kFieldSplit, true, MVNERF_E_ARG}, stream);
+}
+
+int mvnerf_field_eval_stash_split_ex(const float* rays_o, const float* rays_d, const float* z, const float* images,
+                                     const float* features, const float* texel_table, const float* intrinsics,
+                                     const float* extrinsics_inv, const float* packed_net, const void* packed_split, int B, int V, int R,
+                                     int S, int H, int W, float* rgbs, float* stash, void* workspace, int which, float* range_status,
+                                     mvnerf_stream_t stream) {
+    const FieldArgs a = {rays_o, rays_d, z, images, features, texel_table, intrinsics, extrinsics_inv, packed_net, packed_split, B, V, R, S, H, W,
+                         rgbs, nullptr, nullptr, nullptr, nullptr, nullptr, stash, workspace};
+    return field_pass("mvnerf_field_eval_stash_split_ex", a, {kFieldSplit, true, MVNERF_E_ARG}, stream, which, range_status);
 }
 
 int mvnerf_pack_bwd_streams(const float* net_keras, float* bwd_streams, mvnerf_stream_t stream) {
@@ -754,13 +797,16 @@ static int render_fwd(const char* who, bool split, const float* rays_o, const fl
                       const float* intrinsics, const float* extrinsics_inv, const float* packed_coarse, const float* packed_fine,
                       const void* split_coarse, const void* split_fine, const float* u_coarse, const float* u_fine, int B, int V, int R,
                       int S, int H, int W, double near_, double far_, int q7_mode, float* rgb, float* depth, float* fine_rgb,
-                      float* fine_depth, void* workspace, float* texel_tables, int tables_ready, mvnerf_stream_t stream) {
+                      float* fine_depth, void* workspace, float* texel_tables, int tables_ready, mvnerf_stream_t stream, int which = -1,
+                      float* range_status = nullptr) {
+    if (const int rc = split_choice_check(who, which)) return rc;
     if (!u_coarse || !u_fine || !rgb || !depth || !fine_rgb || !fine_depth || !workspace || !packed_fine ||
         (split && (!split_coarse || !split_fine)))
         return fail(MVNERF_E_ARG, "%s: null pointer", who);
     if (S != 64) return fail(MVNERF_E_SHAPE, "%s: S=%d, only the reference's n_samples=64 is built", who, S);
     if (B <= 0 || R <= 0) return fail(MVNERF_E_ARG, "%s: B=%d R=%d", who, B, R);
     if (!aligned16(workspace)) return fail(MVNERF_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
+    if (const int rc = range_status_check(who, range_status)) return rc;
     const long n_rays = (long)B * R;
     if (n_rays * 2 * S >= (1L << 31)) return fail(MVNERF_E_SHAPE, "%s: B*R*2S too large", who);
     const Workspace w = carve(workspace, n_rays, V, S);
@@ -781,11 +827,11 @@ static int render_fwd(const char* who, bool split, const float* rays_o, const fl
     const FieldArgs fine = {rays_o, rays_d, w.z_all, images, features, table_f, intrinsics, extrinsics_inv, packed_fine, split_fine, B, V, R,
                             2 * S, H, W, w.rgbs_f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, w.dir_bias};
     if ((rc = mvnerf_stratified_depths(u_coarse, (int)n_rays, S, near_, far_, w.z, stream))) return rc;
-    if ((rc = field_pass(field_who, coarse, kind, stream))) return rc;
+    if ((rc = field_pass(field_who, coarse, kind, stream, which, range_status))) return rc;
     if ((rc = mvnerf_composite(w.z, w.rgbs_c, (int)n_rays, S, rgb, depth, w.weights, stream))) return rc;
     if ((rc = mvnerf_resample(w.z, w.weights, u_fine, (int)n_rays, S, q7_mode, w.z_all, nullptr, nullptr, nullptr, nullptr, stream)))
         return rc;
-    if ((rc = field_pass(field_who, fine, kind, stream))) return rc;
+    if ((rc = field_pass(field_who, fine, kind, stream, which, range_status ? range_status + 1 : nullptr))) return rc;
     return mvnerf_composite(w.z_all, w.rgbs_f, (int)n_rays, 2 * S, fine_rgb, fine_depth, nullptr, stream);
 }
 
@@ -809,6 +855,17 @@ int mvnerf_render_fwd_split(const float* rays_o, const float* rays_d, const floa
     return render_fwd("mvnerf_render_fwd_split", true, rays_o, rays_d, images, features, intrinsics, extrinsics_inv, packed_coarse,
                       packed_fine, split_coarse, split_fine, u_coarse, u_fine, B, V, R, S, H, W, near_, far_, q7_mode, rgb, depth, fine_rgb,
                       fine_depth, workspace, texel_tables, tables_ready, stream);
+}
+
+int mvnerf_render_fwd_split_ex(const float* rays_o, const float* rays_d, const float* images, const float* features,
+                               const float* intrinsics, const float* extrinsics_inv, const float* packed_coarse,
+                               const float* packed_fine, const void* split_coarse, const void* split_fine, const float* u_coarse,
+                               const float* u_fine, int B, int V, int R, int S, int H, int W, double near_, double far_, int q7_mode,
+                               float* rgb, float* depth, float* fine_rgb, float* fine_depth, void* workspace, float* texel_tables,
+                               int tables_ready, int which, float* range_status, mvnerf_stream_t stream) {
+    return render_fwd("mvnerf_render_fwd_split_ex", true, rays_o, rays_d, images, features, intrinsics, extrinsics_inv, packed_coarse,
+                      packed_fine, split_coarse, split_fine, u_coarse, u_fine, B, V, R, S, H, W, near_, far_, q7_mode, rgb, depth, fine_rgb,
+                      fine_depth, workspace, texel_tables, tables_ready, stream, which, range_status);
 }
 
 }  // extern "C"

@@ -637,24 +637,29 @@ size_t packed_net_split_bytes() { return (size_t)kSpChunks * 1024 + packed_net_s
 
 // Which kernel runs a split field pass.  MVNERF_SPLIT_MFMA (read per launch: tests flip it inside one process):
 //   "32x32x16"  this file's kernel (round 2);   "bf16x6"  field_eval_split16.hip (exact three-piece bf16 cut, six products);
-//   "f16x3"     field_eval_split16h.hip (two fp16 pieces, three products);   unset: mvnerf_set_split_kernel's value
-//               (default f16x3).
+//   "f16x3"     field_eval_split16h.hip (two fp16 pieces, three products);   unset: the caller's choice for this launch (the _ex entry
+//               points), otherwise mvnerf_set_split_kernel's value (default f16x3).
 enum SplitKernel { kSplit16F16 = 0, kSplit16Bf16 = 1, kSplit32 = 2 };            // = MVNERF_SPLIT_* of include/mvnerf_hip.h
 static std::atomic<int> g_split_kernel{kSplit16F16};
 int set_split_kernel(int which) {
     if (which < 0 || which > 2) return -1;
     return g_split_kernel.exchange(which);
 }
-static SplitKernel split_kernel_choice() {
+static SplitKernel split_kernel_choice(int which_call) {
     const char* s = getenv("MVNERF_SPLIT_MFMA");
-    if (!s || !s[0]) return static_cast<SplitKernel>(g_split_kernel.load());
+    if (!s || !s[0]) return static_cast<SplitKernel>(which_call >= 0 ? which_call : g_split_kernel.load());
     return s[0] == '3' ? kSplit32 : (s[0] == 'f' ? kSplit16F16 : kSplit16Bf16);
 }
 
-hipError_t launch_field_eval_split(const FieldParams& p, const void* packed_split, hipStream_t stream) {
-    const SplitKernel which = split_kernel_choice();
+// which_call: -1 or the caller's choice for this launch; range_status: optional, honoured by the f16x3 kernel alone (the other two have
+// the full fp32 range and leave it untouched)
+hipError_t launch_field_eval_split(const FieldParams& p, const void* packed_split, hipStream_t stream, int which_call, float* range_status) {
+    const SplitKernel which = split_kernel_choice(which_call);
     const char* base16 = static_cast<const char*>(packed_split) + (size_t)kSpChunks * 1024;
-    if (which == kSplit16F16 && field_eval_split16h_supports(p)) return launch_field_eval_split16h(p, base16 + packed_net_split16_bytes(), stream);
+    if (which == kSplit16F16 && field_eval_split16h_supports(p)) {
+        if (range_status) return launch_field_eval_split16h_guard(p, base16 + packed_net_split16_bytes(), range_status, stream);
+        return launch_field_eval_split16h(p, base16 + packed_net_split16_bytes(), stream);
+    }
     if (which != kSplit32 && field_eval_split16_supports(p)) return launch_field_eval_split16(p, base16, stream);
     static DeviceSetup setup;
     const int n_pos = ((p.texel_table ? 4 : kSpL0Steps) + kHiddenUnits) * p.V + kHiddenUnits + 2;

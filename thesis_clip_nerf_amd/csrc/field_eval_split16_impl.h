@@ -20,7 +20,8 @@
 //
 // Inference and, since the end of round 3, the training forward (kStash: the 13 pre-activation tensors go to the stash in tile layout).
 //
-// This file is the body of TWO translation units (field_eval_split16.hip: MVS16_F16 = 0, field_eval_split16h.hip: MVS16_F16 = 1):
+// This file is the body of THREE translation units (field_eval_split16.hip: MVS16_F16 = 0, field_eval_split16h.hip: MVS16_F16 = 1,
+// field_eval_split16h_guard.hip: MVS16_F16 = 1 and MVS16_GUARD = 1, the range-guarded copy of the second - see RangeMax below):
 //   MVS16_F16 = 0  operands cut EXACTLY into three bf16 pieces, six v_mfma_f32_16x16x32_bf16 per product block (as described above);
 //   MVS16_F16 = 1  operands as TWO fp16 pieces, three v_mfma_f32_16x16x32_f16 per product block.  With tw = 64 w and tv = v / 64 (powers
 //                  of two: exact, tw tv = w v):  A0 = rn16(tw), A1 = rn16(tw - A0), A0s = A0 / 64;  B0 = rn16(tv), B1 = rn16(64 (tv - B0))
@@ -43,7 +44,17 @@
 #ifndef MVS16_F16
 #error "include through field_eval_split16.hip / field_eval_split16h.hip"
 #endif
-#if MVS16_F16
+#ifndef MVS16_GUARD
+#define MVS16_GUARD 0
+#endif
+#if MVS16_GUARD && !MVS16_F16
+#error "the range guard belongs to the fp16 form: the bf16 cut has the full fp32 range"
+#endif
+#if MVS16_GUARD
+// the guarded unit shares the plain fp16 unit's weight stream, pack kernel and supports(): only the kernel and its launcher are its own
+#define MVS16_LAUNCH_FN launch_field_eval_split16h_guard
+#define MVS16_KERNEL field_eval_split16h_guard_kernel
+#elif MVS16_F16
 #define MVS16_BYTES packed_net_split16h_bytes
 #define MVS16_PACK launch_pack_net_split16h
 #define MVS16_SUPPORTS field_eval_split16h_supports
@@ -87,6 +98,7 @@ __host__ __device__ constexpr int s16_pe_row(int g, int e) {
     return g < 3 ? 20 * g + e : (e < 12 ? 20 * (e >> 2) + 2 * (8 + ((e >> 1) & 1)) + (e & 1) : (e < 15 ? 120 + (e - 12) : -1));
 }
 
+#if !MVS16_GUARD
 __global__ void MVS16_PACK_KERNEL(const float* __restrict__ src, unsigned short* __restrict__ dst) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= kS16Chunks * kChunkElems16) return;
@@ -125,6 +137,7 @@ __global__ void MVS16_PACK_KERNEL(const float* __restrict__ src, unsigned short*
     dst[idx] = __builtin_bit_cast(unsigned short, pc);
 #endif
 }
+#endif  // !MVS16_GUARD
 
 __device__ __forceinline__ f32x4 mfma1632(u32x4 a, u32x4 b, f32x4 c) {
 #if MVS16_F16
@@ -138,15 +151,40 @@ struct B16 {
     u32x4 p1, p2, p3;
 };
 
+// Range guard (MVS16_GUARD, field_eval_split16h_guard.hip): the largest |v| of every value a lane cuts into fp16 activation pieces,
+// kept as the BIT PATTERN of the non-negative float under an unsigned max - a NaN operand (pattern above infinity's) stays a NaN, infinity
+// stays infinity.  One running maximum per column block, because the two samples of a lane can differ in validity (rows past `total`); `all`
+// collects the valid ones of the tiles the wave has finished.  Behind a relu the operands already are non-negative patterns (the relu is an
+// integer max): one v_max3_u32 per value pair.  The signed layer-0 operands (PE, rgb, gathered features) lose their sign bit first: three
+// instructions per pair, in 2 (texel table) or 10 (direct gather) of a view's 26 / 34 k-steps.
+// Without the guard the struct is empty and every use below compiles to nothing.
+#if MVS16_GUARD
+struct RangeMax {
+    unsigned cb[2], all;
+};
+#else
+struct RangeMax {};
+#endif
+
 // values 2q, 2q+1 of an 8-value B operand -> dword q of the three pieces (relu first where the layer has one); truncation cut,
 // every remainder exact (field_eval_split.hip)
 template <bool kRelu>
-__device__ __forceinline__ void cut_pair(float v0, float v1, int q, B16& b) {
+__device__ __forceinline__ void cut_pair(float v0, float v1, int q, B16& b, RangeMax& gm, int cb) {
     if (kRelu) {               // relu on the bit pattern: one v_max_i32
         const int i0 = __builtin_bit_cast(int, v0), i1 = __builtin_bit_cast(int, v1);
         v0 = __builtin_bit_cast(float, i0 > 0 ? i0 : 0);
         v1 = __builtin_bit_cast(float, i1 > 0 ? i1 : 0);
     }
+#if MVS16_GUARD
+    {
+        unsigned u0 = __builtin_bit_cast(unsigned, v0), u1 = __builtin_bit_cast(unsigned, v1);
+        if (!kRelu) {
+            u0 &= 0x7fffffffu;
+            u1 &= 0x7fffffffu;
+        }
+        asm("v_max3_u32 %0, %1, %2, %3" : "=v"(gm.cb[cb]) : "v"(gm.cb[cb]), "v"(u0), "v"(u1));
+    }
+#endif
 #if MVS16_F16
     // p1 = B0 = rn16(v / 64), p3 = B1 = rn16(64 (v / 64 - B0)) = rn16(v - 64 B0): the remainder is exact in fp32, formed by one
     // mixed-precision fma per value (v_fma_mix_f32 reads B0's halves as they lie); p2 is not used.  The remainders stay two
@@ -189,9 +227,9 @@ __device__ __forceinline__ void pin_pieces(B16& b, int q) {
 }
 
 template <bool kRelu>
-__device__ __forceinline__ void cut8(const float (&v)[8], B16& b) {
+__device__ __forceinline__ void cut8(const float (&v)[8], B16& b, RangeMax& gm, int cb) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) cut_pair<kRelu>(v[2 * q], v[2 * q + 1], q, b);
+    for (int q = 0; q < 4; ++q) cut_pair<kRelu>(v[2 * q], v[2 * q + 1], q, b, gm, cb);
 }
 
 // ---- the slot ring: one k-step (24 KiB) per slot, 3 slots -------------------------------------------------------------------------
@@ -303,7 +341,7 @@ __device__ __forceinline__ void apply_bias_row(f32x4 (&row)[2], const f32x4& bv)
 // from LDS while group rb runs (as the tail rows below), row 0 (init0) by the caller in front of the layer's first cut.
 template <bool kRelu, int kMode, bool kTailAdd, bool kInit = false>
 __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16 (&b)[2], const float (&nv)[2][8], B16 (&bn)[2], f32x4 (&acc)[8][2],
-                                        f32x4 (&in)[8][2], const float* __restrict__ tail_bias, const float* __restrict__ init_bias = nullptr,
+                                        f32x4 (&in)[8][2], const float* __restrict__ tail_bias, RangeMax& gm, const float* __restrict__ init_bias = nullptr,
                                         f32x4 init0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}) {
     const f32x4* cur = ring16_cur(ring) + lane;
     const f32x4* nxt = ring16_nxt(ring) + lane;
@@ -321,7 +359,7 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
         u32x4 an[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) an[q] = __builtin_bit_cast(u32x4, rb < 7 ? cur[((rb + 1) * 3 + q) * 64] : nxt[q * 64]);
-        if (kMode == 1) cut_pair<kRelu>(nv[rb >> 2][2 * (rb & 3)], nv[rb >> 2][2 * (rb & 3) + 1], rb & 3, bn[rb >> 2]);
+        if (kMode == 1) cut_pair<kRelu>(nv[rb >> 2][2 * (rb & 3)], nv[rb >> 2][2 * (rb & 3) + 1], rb & 3, bn[rb >> 2], gm, rb >> 2);
         f32x4 cin = ci;
         if (kInit && rb < 7) cin = init_rows[((rb + 1) >> 1) * 4 + 2 * ((rb + 1) & 1)];    // = [perm_f4(rb + 1, g)]
         if (kMode == 4 && tail_bias) {
@@ -391,11 +429,11 @@ __device__ __forceinline__ void kstep16(Ring16& ring, int lane, int g, const B16
 }
 
 // the cut of relu(in[0..1]): the first B operands of a hidden layer (k-step 0 reads in[0][cb] (jj < 4) and in[1][cb] (jj >= 4))
-__device__ __forceinline__ void first_operand_s16(const f32x4 (&in)[8][2], B16 (&b)[2]) {
+__device__ __forceinline__ void first_operand_s16(const f32x4 (&in)[8][2], B16 (&b)[2], RangeMax& gm) {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
         const float v8[8] = {in[0][cb][0], in[0][cb][1], in[0][cb][2], in[0][cb][3], in[1][cb][0], in[1][cb][1], in[1][cb][2], in[1][cb][3]};
-        cut8<true>(v8, b[cb]);
+        cut8<true>(v8, b[cb], gm, cb);
     }
 }
 
@@ -408,11 +446,11 @@ __device__ __forceinline__ void first_operand_s16(const f32x4 (&in)[8][2], B16 (
 // kInit: acc = init_bias + W^T relu(in) (acc's contents on entry are ignored; kstep16, kInit), otherwise acc += W^T relu(in).
 template <bool kTailAdd, bool kInit>
 __device__ __forceinline__ void dense128_s16_plain(Ring16& ring, int lane, int g, f32x4 (&in)[8][2], f32x4 (&acc)[8][2], const float* __restrict__ tail_bias,
-                                                   const float* __restrict__ init_bias = nullptr) {
+                                                   RangeMax& gm, const float* __restrict__ init_bias = nullptr) {
     B16 b[2], bn[2];
     f32x4 init0 = {0.0f, 0.0f, 0.0f, 0.0f};
     if (kInit) init0 = reinterpret_cast<const f32x4*>(init_bias)[perm_f4(0, g)];     // lands during the cut below
-    first_operand_s16(in, b);
+    first_operand_s16(in, b, gm);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         float nv[2][8];
@@ -420,9 +458,9 @@ __device__ __forceinline__ void dense128_s16_plain(Ring16& ring, int lane, int g
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int q = 0; q < 8; ++q) nv[cb][q] = t < 3 ? in[2 * (t + 1) + (q >> 2)][cb][q & 3] : 0.0f;
-        if (t == 0 && kInit) kstep16<true, 1, false, true>(ring, lane, g, b, nv, bn, acc, in, nullptr, init_bias, init0);
-        else if (t < 3) kstep16<true, 1, false>(ring, lane, g, b, nv, bn, acc, in, nullptr);
-        else kstep16<true, 4, kTailAdd>(ring, lane, g, b, nv, bn, acc, in, tail_bias);
+        if (t == 0 && kInit) kstep16<true, 1, false, true>(ring, lane, g, b, nv, bn, acc, in, nullptr, gm, init_bias, init0);
+        else if (t < 3) kstep16<true, 1, false>(ring, lane, g, b, nv, bn, acc, in, nullptr, gm);
+        else kstep16<true, 4, kTailAdd>(ring, lane, g, b, nv, bn, acc, in, tail_bias, gm);
         b[0] = bn[0];
         b[1] = bn[1];
         ring16_next(ring);
@@ -489,7 +527,11 @@ struct SampleGeo {
 // kStash (training forward): the trunk's 13 pre-activation tensors also go to HBM (p.stash / p.stash_fused, mvnerf_kernels.h), exactly
 // the slots field_eval_split_kernel<.., kStash> writes.
 template <bool kMultiView, bool kProj, bool kAux, bool kStash>
-__global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x4* __restrict__ wsplit) {
+__global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x4* __restrict__ wsplit
+#if MVS16_GUARD
+                                                       , unsigned* __restrict__ range_status      // max |cut activation| as a bit pattern
+#endif
+) {
     constexpr int kW = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s16[];
     constexpr int kRingBytes = kR16Slots * kR16SlotF4 * 16;                 // 72 KiB
@@ -527,6 +569,10 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 #pragma unroll
     for (int q = 0; q < 3; ++q) ring.a0[q] = __builtin_bit_cast(u32x4, ring16_cur(ring)[q * 64 + lane]);
 
+    RangeMax gm;
+#if MVS16_GUARD
+    gm.all = 0u;
+#endif
     // (32-bit tile counts - B*R*S < 2^31 - so that the loop's compares are scalar: a 64-bit one runs on the vector ALU against a register pair)
     const int n_tiles = (int)p.n_tiles, n_groups = (n_tiles + kW - 1) / kW;
     for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
@@ -589,6 +635,9 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 
         f32x4 x[8][2], hid[8][2];
         f32x4 xsum[kMultiView ? 8 : 1][2];
+#if MVS16_GUARD
+        gm.cb[0] = gm.cb[1] = 0u;
+#endif
 
         // (a sample row of 128 floats: lane (n, g) holds features 16 rb + 4g + {0..3} of samples n (cb 0) and 16 + n (cb 1))
         // the launcher sends V = 1 to the !kMultiView variants.  Telling the compiler so takes the optional-output and stash variants from 92-132
@@ -710,16 +759,16 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 #pragma unroll
                 for (int cb = 0; cb < 2; ++cb) {
                     const float v8[8] = {pe[cb][0], pe[cb][1], pe[cb][2], pe[cb][3], pe[cb][4], pe[cb][5], pe[cb][6], pe[cb][7]};
-                    cut8<false>(v8, bq[cb]);
+                    cut8<false>(v8, bq[cb], gm, cb);
                 }
                 float nv[2][8];
 #pragma unroll
                 for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
                     for (int q = 0; q < 8; ++q) nv[cb][q] = pe[cb][8 + q];
-                kstep16<false, 1, false>(ring, lane, g, bq, nv, bqn, x, x, nullptr);
+                kstep16<false, 1, false>(ring, lane, g, bq, nv, bqn, x, x, nullptr, gm);
                 ring16_next(ring);
-                kstep16<false, 0, false>(ring, lane, g, bqn, nv, bq, x, x, nullptr);
+                kstep16<false, 0, false>(ring, lane, g, bqn, nv, bq, x, x, nullptr, gm);
                 ring16_next(ring);
             }
 
@@ -789,11 +838,11 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
                             const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + row * kS16StageRowBytes + (((8 * s + 2 * gl) ^ (row & 15)) << 4));
                             const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + row * kS16StageRowBytes + (((8 * s + 2 * gl + 1) ^ (row & 15)) << 4));
                             const float b8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                            cut8<false>(b8, bq[cb]);
+                            cut8<false>(b8, bq[cb], gm, cb);
 #pragma unroll
                             for (int q = 0; q < 8; ++q) nv[cb][q] = 0.0f;
                         }
-                        kstep16<false, 0, false>(ring, lane, gl, bq, nv, bqn, x, x, nullptr);
+                        kstep16<false, 0, false>(ring, lane, gl, bq, nv, bqn, x, x, nullptr, gm);
                         ring16_next(ring);
                     }
                 }
@@ -817,10 +866,10 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 #pragma unroll 1
             for (int bi = 0; bi < 3; ++bi) {
                 const float* bias1 = net + kPackBHidden + 256 * bi;
-                dense128_s16_plain<true, true>(ring, lane, g, x, hid, nullptr, bias1);
+                dense128_s16_plain<true, true>(ring, lane, g, x, hid, nullptr, gm, bias1);
                 if (kStash && tile_ok) store_tl16(p.stash + (1 + 2 * bi) * p.stash_stride, vtile, n, g, hid);
                 bias16<true>(bias1 + 128, g, x);
-                dense128_s16_plain<false, false>(ring, lane, g, hid, x, nullptr);
+                dense128_s16_plain<false, false>(ring, lane, g, hid, x, nullptr, gm);
                 // (per-view slot 6 = x3 is not written: nothing reads it, as in field_eval_split_kernel)
                 if (kStash && tile_ok && bi < 2) store_tl16(p.stash + (2 + 2 * bi) * p.stash_stride, vtile, n, g, x);
                 if (kAux && p.acts_view) store_acc16(p.acts_view + (bi + 1) * vslot, vrow);
@@ -868,10 +917,10 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
 #pragma unroll 1
         for (int bi = 3; bi < 6; ++bi) {
             const float* bias1 = net + kPackBHidden + 256 * bi;
-            dense128_s16_plain<true, true>(ring, lane, g, x, hid, nullptr, bias1);
+            dense128_s16_plain<true, true>(ring, lane, g, x, hid, nullptr, gm, bias1);
             if (kStash && tile_ok) store_tl16(p.stash_fused + (1 + 2 * (bi - 3)) * p.stash_fused_stride, tile, n, g, hid);
             bias16<true>(bias1 + 128, g, x);
-            dense128_s16_plain<false, false>(ring, lane, g, hid, x, nullptr);
+            dense128_s16_plain<false, false>(ring, lane, g, hid, x, nullptr, gm);
             if (kStash && tile_ok) store_tl16(p.stash_fused + (2 + 2 * (bi - 3)) * p.stash_fused_stride, tile, n, g, x);
             if (kAux && p.acts_fused) store_fused16(p.acts_fused + (long)(bi - 2) * p.total * 128);
         }
@@ -917,12 +966,44 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
                 *reinterpret_cast<f32x4*>(p.rgbs + 4 * gi) = out;
             }
         }
+#if MVS16_GUARD
+        // the tile's maxima join the wave's: an idle wave (it shadows the last tile) and rows past `total` contribute nothing
+        {
+            const unsigned m0 = gvalid[0] ? gm.cb[0] : 0u, m1 = gvalid[1] ? gm.cb[1] : 0u;
+            gm.all = gm.all > m0 ? gm.all : m0;
+            gm.all = gm.all > m1 ? gm.all : m1;
+        }
+#endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                     // weight requests still in flight must land before the LDS is released
+#if MVS16_GUARD
+    // the workgroup's maximum: across the wave's lanes, then across the waves through the head of each wave's private gather stage (nobody
+    // reads a stage after its wave's last gather; the ring may still be read by a slower wave), then ONE atomic max per workgroup.
+    // Every wave arrives here: the tile loop's trip count is the same for the whole workgroup.
+    {
+        unsigned m = gm.all;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned o = (unsigned)__shfl_xor((int)m, off);
+            m = m > o ? m : o;
+        }
+        if (lane == 0) *reinterpret_cast<unsigned*>(stage) = m;
+        __syncthreads();
+        if (tid == 0) {
+            unsigned wg = 0u;
+            for (int w = 0; w < kW; ++w) {
+                const unsigned o = *reinterpret_cast<const unsigned*>(smem_s16 + kRingBytes + w * (32 * kS16StageRowBytes));
+                wg = wg > o ? wg : o;
+            }
+            atomicMax(range_status, wg);
+        }
+    }
+#endif
 }
 
 }  // namespace
 
+#if !MVS16_GUARD
 size_t MVS16_BYTES() { return (size_t)kS16Chunks * 1024; }
 
 hipError_t MVS16_PACK(const float* net_keras, void* packed_split16, hipStream_t st) {
@@ -936,10 +1017,19 @@ bool MVS16_SUPPORTS(const FieldParams& p) {
     const int n_pos = ((p.texel_table ? kS16L0Pe : kS16L0Pe + kS16L0Feat) + kS16PerView) * p.V + kS16PerView;
     return n_pos <= kS16MaxPositions;
 }
+#endif  // !MVS16_GUARD
 
+#if MVS16_GUARD
+// range_status: one device float, max-accumulated (never reset here: the chunks of a frame accumulate into it)
+hipError_t MVS16_LAUNCH_FN(const FieldParams& p, const void* packed_split16, float* range_status, hipStream_t stream) {
+    static DeviceSetup setup;
+    if (!range_status || !field_eval_split16h_supports(p)) return hipErrorInvalidValue;
+    unsigned* status = reinterpret_cast<unsigned*>(range_status);
+#else
 hipError_t MVS16_LAUNCH_FN(const FieldParams& p, const void* packed_split16, hipStream_t stream) {
     static DeviceSetup setup;
     if (!MVS16_SUPPORTS(p)) return hipErrorInvalidValue;
+#endif
     const int lds_bytes = kR16Slots * kR16SlotF4 * 16 + 8 * 32 * kS16StageRowBytes + (kPackBr + 8 - kPackB0) * 4 + kS16MaxPositions * 4 + 512 * 4;
     int cus = 0;
     hipError_t e = device_setup(setup, {{&MVS16_KERNEL<false, false, false, false>, lds_bytes}, {&MVS16_KERNEL<false, true, false, false>, lds_bytes},
@@ -956,7 +1046,11 @@ hipError_t MVS16_LAUNCH_FN(const FieldParams& p, const void* packed_split16, hip
     const unsigned wgs = (unsigned)(n_groups < resident ? n_groups : resident);
     const f32x4* w = static_cast<const f32x4*>(packed_split16);
     const dim3 grid(wgs), block(512);
+#if MVS16_GUARD
+#define MVS16_LAUNCH(MV, PROJ, AUX, STASH) hipLaunchKernelGGL((MVS16_KERNEL<MV, PROJ, AUX, STASH>), grid, block, lds_bytes, stream, p, w, status)
+#else
 #define MVS16_LAUNCH(MV, PROJ, AUX, STASH) hipLaunchKernelGGL((MVS16_KERNEL<MV, PROJ, AUX, STASH>), grid, block, lds_bytes, stream, p, w)
+#endif
     const bool aux = p.tap_idx || p.pix || p.embedding || p.acts_view || p.acts_fused;
     if (p.stash && p.V > 1 && ((long)p.R * p.S) % 32 != 0) return hipErrorInvalidValue;     // tiles must not straddle scenes
     if (p.stash) {

@@ -62,7 +62,9 @@ hipError_t launch_project_texels_bf16maps(const void* features_bf16, const void*
                                           float* table1, hipStream_t stream);
 size_t packed_net_split_bytes();
 hipError_t launch_pack_net_split(const float* net_keras, void* packed_split, hipStream_t st);
-hipError_t launch_field_eval_split(const FieldParams& p, const void* packed_split, hipStream_t stream);
+// which: -1 = the process-wide choice (set_split_kernel), 0..2 = that kernel for this launch (MVNERF_SPLIT_* of include/mvnerf_hip.h);
+// range_status (optional, one device float): with the f16x3 kernel the pass runs its range-guarded copy (field_eval_split16h_guard.hip)
+hipError_t launch_field_eval_split(const FieldParams& p, const void* packed_split, hipStream_t stream, int which = -1, float* range_status = nullptr);
 // field_eval_split16.hip: the same field pass issued as v_mfma_f32_16x16x32_bf16 (inference; its weight stream follows the
 // 32x32x16 kernel's inside the packed_split buffer)
 size_t packed_net_split16_bytes();
@@ -75,6 +77,10 @@ size_t packed_net_split16h_bytes();
 hipError_t launch_pack_net_split16h(const float* net_keras, void* packed_split16h, hipStream_t st);
 bool field_eval_split16h_supports(const FieldParams& p);
 hipError_t launch_field_eval_split16h(const FieldParams& p, const void* packed_split16h, hipStream_t stream);
+// field_eval_split16h_guard.hip: that kernel with the range guard; *range_status = max(*range_status, max |v| of every cut activation)
+hipError_t launch_field_eval_split16h_guard(const FieldParams& p, const void* packed_split16h, float* range_status, hipStream_t stream);
+// net_range.hip: out2 = {max |w| over the weights the split streams cut, max |.| over all variables} of a Keras-order net
+hipError_t launch_net_range(const float* net_keras, float* out2, hipStream_t stream);
 
 // grasp_head.hip: the per-point part of GraspReadout (value, VJP, derivative of the VJP)
 size_t grasp_head_packed_floats();

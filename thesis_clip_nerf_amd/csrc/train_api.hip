@@ -7,7 +7,10 @@
 //   mvnerf_apply_gradients = clip-by-value + Adam on both MLPs (+ re-packing the weight images the next forward needs)
 //   mvnerf_train_step      = the two in sequence (single device; a data-parallel host all-reduces `grad` in between)
 // No allocation: every intermediate lives in the caller's workspace (mvnerf_train_workspace_bytes).  Stream-ordered, no host
-// synchronisation, no global state.
+// synchronisation.  One piece of global state is read: which split kernel runs the two forward passes is the process-wide value of
+// mvnerf_set_split_kernel (mvnerf_train_call is frozen and has no room for the per-call choice of the _ex entry points).
+// Range: with the default fp16 two-piece kernels every stashed pre-activation must stay below MVNERF_F16X3_MAX_WEIGHT (the
+// weight-gradient GEMM cuts relu(a) as rn16(64 a)); nothing here checks it - mvnerf_field_eval_stash_split_ex with a range status does.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>

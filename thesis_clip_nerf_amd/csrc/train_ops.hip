@@ -270,6 +270,9 @@ __device__ __forceinline__ void cut2h_scaled(const f32x4& xlo, const f32x4& xhi,
 }
 
 // 8 fp32 values -> the three fp16 pieces of an A operand with t = 64 x: a0 = rn16(t), a0s = a0 / 64, a1 = rn16(t - a0) (unscaled remainder)
+// Range: |x| < 1023.75 (rn16(64 x) is infinite beyond).  For the transposed weights that is the forward's weight limit; for the dW waves'
+// relu(stashed pre-activation) it is a limit on ACTIVATIONS 4096 times tighter than the forward's - MVNERF_F16X3_MAX_WEIGHT, watched by the
+// range status of mvnerf_field_eval_stash_split_ex (include/mvnerf_hip.h), not lifted here.
 template <bool kRelu>
 __device__ __forceinline__ void cut3a(const f32x4& xlo, const f32x4& xhi, u32x4_t& a0, u32x4_t& a0s, u32x4_t& a1) {
 #pragma unroll

@@ -18,12 +18,13 @@ from __future__ import annotations
 
 import math
 import os
+import warnings
 
 import numpy as np
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, range_policy
 
 N_FUSED = 4
 
@@ -620,6 +621,12 @@ class LanguageNeRF(nn.Module):
             raise ValueError(f'{path}: {flat.numel()} backbone parameters, expected {self.trunk_net.numel()}')
         with torch.no_grad():
             self.trunk_net.copy_(flat)
+        if self.trunk_net.is_cuda:
+            # the query kernels read the same packed_split image as the render passes: its fp16 two-piece form is only correct for
+            # |w| < 1023 (include/mvnerf_hip.h, MVNERF_F16X3_MAX_WEIGHT); checked once per load, one host read
+            max_w = float(ops.net_range(self.trunk_net.detach())[0])
+            if not range_policy.below(max_w, range_policy.limits()[0]):
+                warnings.warn(f'{path}: backbone ' + range_policy.describe(max_w, None), RuntimeWarning, stacklevel=2)
         return True
 
     def store(self, path):

@@ -20,11 +20,12 @@ signatures; the uniforms that the reference draws inside the graph with ``tf.ran
 from __future__ import annotations
 
 import os
+import warnings
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, range_policy as rp
 from ._lib import NET_PARAMS, Q7_ZERO
 from .synthetic import glorot_net
 
@@ -37,7 +38,8 @@ class MVVNeRFRenderer:
 
     def __init__(self, n_rays_train, n_rays_infer, n_views=2, n_samples=64, n_features=256,
                  embed_direction_vector=True, batch_size=1, near=0.7, far=1.5, original_image_size=(480, 640),
-                 device='cuda', seed=0, feature_encoder=None, q7_mode=Q7_ZERO, compute_dtype='f32', f32_gemm='split_f16'):
+                 device='cuda', seed=0, feature_encoder=None, q7_mode=Q7_ZERO, compute_dtype='f32', f32_gemm='split_f16',
+                 range_policy='fallback', range_check=False):
         if n_features != 256:
             raise ValueError('n_features must be 256 (the HIP kernels are built for the reference feature width)')
         if not embed_direction_vector:
@@ -63,6 +65,16 @@ class MVVNeRFRenderer:
             raise ValueError("f32_gemm must be 'split_f16' (two fp16 pieces per operand, three MFMAs per product block: the default), "
                              "'split_bf16' (exact three-piece bf16 cut, six MFMAs) - both fp32-grade - or 'mfma_f32'")
         self.f32_gemm = f32_gemm                 # how compute_dtype='f32' inference runs its Dense layers (same results to ~1e-6)
+        # 'split_f16' is only correct for |w| < 1023, |activation| < 4.19e6 (range_policy.py).  Weights are checked once per weight
+        # version by the first inference call after a change; out of range the call runs on 'split_bf16' with one RuntimeWarning
+        # ('fallback'), raises FloatingPointError ('raise'), or nobody looks ('off').  Activations are opt-in (range_check=True routes
+        # `_call` through the range-guarded kernel, range_report() reads the result): reading the status is a host synchronisation.
+        if range_policy not in rp.POLICIES:
+            raise ValueError(f'range_policy must be one of {rp.POLICIES}, got {range_policy!r}')
+        self.range_policy = range_policy
+        self.range_check = bool(range_check)
+        self._weight_range = None       # ((max |w|, max |.|) coarse, fine) of the current weight version, once read
+        self._range_status = None       # device (2,): max |cut activation| of the coarse / fine passes since range_reset()
         rng = np.random.default_rng(seed)
         self.coarse_net = torch.from_numpy(glorot_net(rng)).to(self.device)      # Keras glorot_uniform, zero bias
         self.fine_net = torch.from_numpy(glorot_net(rng)).to(self.device)
@@ -88,6 +100,7 @@ class MVVNeRFRenderer:
         self._packed_bwd = None
         self._tables_key = None
         self._last_call = (None, None)
+        self._weight_range = None
 
     def weights_changed(self):
         """Call after updating coarse_net / fine_net in place (e.g. an optimizer step)."""
@@ -95,6 +108,7 @@ class MVVNeRFRenderer:
         self._packed_bwd = None
         self._tables_key = None
         self._last_call = (None, None)
+        self._weight_range = None
 
     def packed(self):
         if self._packed is None:
@@ -115,6 +129,75 @@ class MVVNeRFRenderer:
             self._packed16 = (ops.pack_net_bf16(self.coarse_net), ops.pack_net_bf16(self.fine_net))
         return self._packed16
 
+    # ---- range of the fp16 two-piece kernel (range_policy.py) ---------------------------------
+    def weight_range(self):
+        """((max |w| over the cut weights, max |.| over all variables) of the coarse net, ... of the fine net): one host read per
+        weight version (ops.net_range), cached until the weights change."""
+        if self._weight_range is None:
+            both = torch.stack([ops.net_range(self.coarse_net), ops.net_range(self.fine_net)]).cpu().tolist()
+            self._weight_range = (tuple(both[0]), tuple(both[1]))
+        return self._weight_range
+
+    def _inference_kernel(self):
+        """The split kernel an inference call runs: f32_gemm, or 'split_bf16' when the weights have left split_f16's range."""
+        if self.f32_gemm != 'split_f16' or self.range_policy == 'off':
+            return self.f32_gemm
+        first = self._weight_range is None
+        max_w = rp.worst([net[0] for net in self.weight_range()])
+        action = rp.decide(self.range_policy, self.f32_gemm, max_weight=max_w)
+        if action == rp.RUN:
+            return self.f32_gemm
+        if action == rp.RAISE:
+            raise FloatingPointError(rp.describe(max_w, None))
+        if first:                               # one warning per weight version
+            warnings.warn(rp.describe(max_w, None) + " - running on 'split_bf16'", RuntimeWarning, stacklevel=3)
+        return 'split_bf16'
+
+    def range_reset(self):
+        """Zero the activation status that range-checked calls accumulate into."""
+        if self._range_status is None:
+            self._range_status = torch.zeros(2, dtype=torch.float32, device=self.device)
+        else:
+            self._range_status.zero_()
+        return self._range_status
+
+    def range_report(self):
+        """Synchronises.  -> {'coarse': {'max_weight', 'max_activation'}, 'fine': {...}, 'in_range': bool}: the weights of the current
+        version and the largest |activation| the range-checked calls since range_reset() cut into fp16 pieces (0.0: none ran)."""
+        acts = [0.0, 0.0] if self._range_status is None else self._range_status.cpu().tolist()
+        wr = self.weight_range()
+        out = {name: {'max_weight': wr[k][0], 'max_activation': acts[k]} for k, name in enumerate(('coarse', 'fine'))}
+        out['in_range'] = all(rp.in_range(v['max_weight'], v['max_activation']) for v in list(out.values()))
+        return out
+
+    def check_range(self, inputs, combined_features, training=True, u_coarse=None, u_fine=None, generator=None):
+        """Runs the coarse -> resample -> fine chain of one step on the range-guarded training forward (ops.field_eval_stash with a
+        range status) and reads the result: synchronises.  training=True compares with the backward's limit (every stashed
+        pre-activation below 1023: the weight-gradient GEMM cuts relu(a) as rn16(64 a)), training=False with the forward's.
+        -> {'coarse': {...}, 'fine': {...}, 'limit', 'in_range', 'message'}."""
+        rays_o, rays_d, images, k4, einv = [self._dev(t) for t in inputs]
+        feats = self._dev(combined_features)
+        b, r, _ = rays_o.shape
+        u_coarse, u_fine = self._uniforms(b, r, u_coarse, u_fine, generator)
+        pc, pf = self.packed()
+        sc, sf = self.packed_split()
+        status = torch.zeros(2, dtype=torch.float32, device=self.device)
+        geo = (images, feats, k4, einv)
+        z = ops.stratified_depths(self._dev(u_coarse), self.near, self.far)
+        rgbs_c, stash = ops.field_eval_stash(rays_o, rays_d, z, *geo, pc, packed_split=sc, kernel='split_f16', range_status=status[0:1])
+        _, _, w = ops.composite(z, rgbs_c)
+        z_all = ops.resample(z, w, self._dev(u_fine), self.q7_mode)
+        del stash
+        ops.field_eval_stash(rays_o, rays_d, z_all, *geo, pf, packed_split=sf, kernel='split_f16', range_status=status[1:2])
+        acts = status.cpu().tolist()
+        wr = self.weight_range()
+        out = {name: {'max_weight': wr[k][0], 'max_activation': acts[k]} for k, name in enumerate(('coarse', 'fine'))}
+        max_w, max_a = rp.worst([wr[0][0], wr[1][0]]), rp.worst(acts)
+        out['limit'] = rp.limits(training)[1]
+        out['in_range'] = rp.in_range(max_w, max_a, training)
+        out['message'] = '' if out['in_range'] else rp.describe(max_w, max_a, training)
+        return out
+
     # ---- forward -------------------------------------------------------------------------
     def encode(self, image):
         """model_v0.py:47-49 - image encoder hook; out of the hot-path scope."""
@@ -132,13 +215,15 @@ class MVVNeRFRenderer:
         return u_coarse, u_fine
 
     def _call(self, inputs, n_rays, batch_size, combined_features, u_coarse=None, u_fine=None, generator=None,
-              scene_key=None):
+              scene_key=None, range_check=None, kernel=None):
         """model_v0.py:113-184.  inputs = (ray_origins (B,R,3), ray_directions (B,R,3),
         images (B,V,H,W,3) in [0,1], intrinsics (B,V,4,4), extrinsics_inv (B,V,4,4)).
         Returns (rgb, depth, fine_rgb, fine_depth).
         The feature rows of layer 0 go through per-texel tables (include/mvnerf_hip.h, "Texel table") when that is
         cheaper: always rebuilt for a call with R*S >= 2*H*W; with `scene_key` (any hashable naming the feature maps,
-        e.g. one frame rendered in chunks) they are built by the first call and re-used while key and weights last."""
+        e.g. one frame rendered in chunks) they are built by the first call and re-used while key and weights last.
+        range_check (default: the constructor's): run the split_f16 passes range-guarded, accumulating into range_report().
+        kernel: run this call on that split kernel instead of f32_gemm (render_view's fallback frame)."""
         rays_o, rays_d, images, k4, einv = [self._dev(t) for t in inputs]
         if self.compute_dtype == 'bf16' and isinstance(combined_features, torch.Tensor) and combined_features.dtype == torch.bfloat16:
             # bf16 feature maps stay bf16 (encoders.FeatureProducer(out_dtype=torch.bfloat16)): the bf16 passes read them as stored
@@ -166,11 +251,17 @@ class MVVNeRFRenderer:
             tables = self._tables
             ready = scene_key is not None and self._tables_key == scene_key
             self._tables_key = scene_key
-        if self.f32_gemm != 'mfma_f32':
-            ops.set_split_kernel(self.f32_gemm)          # process-wide: which split kernel the calls below run
+        if self.f32_gemm == 'mfma_f32':
+            return ops.render_fwd(rays_o, rays_d, images, features, k4, einv, pc, pf, self._dev(u_coarse), self._dev(u_fine),
+                                  self.near, self.far, self.q7_mode, workspace=self._workspace, texel_tables=tables, tables_ready=ready)
+        # the split kernel is chosen for this call alone (the process-wide value is neither read nor written)
+        kernel = kernel or self._inference_kernel()
+        status = None
+        if (self.range_check if range_check is None else range_check) and kernel == 'split_f16':
+            status = self._range_status if self._range_status is not None else self.range_reset()
         return ops.render_fwd(rays_o, rays_d, images, features, k4, einv, pc, pf, self._dev(u_coarse), self._dev(u_fine),
                               self.near, self.far, self.q7_mode, workspace=self._workspace, texel_tables=tables,
-                              tables_ready=ready, split=self.packed_split() if self.f32_gemm != 'mfma_f32' else None)
+                              tables_ready=ready, split=self.packed_split(), kernel=kernel, range_status=status)
 
     def infer(self, inputs, batched_features, **kw):
         """model_v0.py:61-63 (any ray count, not only n_rays_infer=512)."""
@@ -231,7 +322,15 @@ class MVVNeRFRenderer:
         if not hasattr(self, '_grad'):
             self.compile()
         call, keep = self._train_call(inputs, labels, combined_features, u_coarse, u_fine, generator, stop_fine_z, return_d_features)
-        ops.loss_and_grads(call, keep['rays_o'])                 # ONE C call: mvnerf_loss_and_grads (csrc/train_api.hip)
+        # ONE C call: mvnerf_loss_and_grads (csrc/train_api.hip).  Its struct has no room for a per-call kernel choice, so the training
+        # forward follows the process-wide value: it is set for the length of the call (the choice is read when the passes are
+        # launched) and put back, so that one model's training does not choose another model's or caller's kernel
+        prev = ops.set_split_kernel(self.f32_gemm) if keep['split'] is not None else None
+        try:
+            ops.loss_and_grads(call, keep['rays_o'])
+        finally:
+            if prev is not None:
+                ops.set_split_kernel(prev)
         self._last_call = (call, keep)
         if return_d_features:
             return keep['loss'], self._grad, keep['outputs'], keep['d_features']
@@ -249,9 +348,9 @@ class MVVNeRFRenderer:
         pc, pf = self.packed()
         if self._packed_bwd is None:
             self._packed_bwd = (ops.pack_bwd_streams(self.coarse_net), ops.pack_bwd_streams(self.fine_net))
+        # the training forward runs on the same split kernel as inference (loss_and_grads selects it); the backward's layer launches
+        # always use fp16 two-piece products, which is why a training step has the tighter range of check_range(training=True)
         split = self.packed_split() if self.f32_gemm != 'mfma_f32' else None
-        if split is not None:
-            ops.set_split_kernel(self.f32_gemm)          # the training forward runs on the same split kernel as inference; the backward keeps the exact cut
         use_tables = ops.texel_table_pays(r, self.n_samples, h, w)      # layer 0's feature rows per texel
         tb = self._train_bufs
         key = (b, v, r, h, w, bool(return_d_features))
@@ -332,6 +431,7 @@ class MVVNeRFRenderer:
         ops.apply_gradients(call, adam, self._grad)
         self._packed16 = None
         self._tables_key = None
+        self._weight_range = None
         if not call.split_coarse:
             self._packed_split = None
 
@@ -387,11 +487,14 @@ def render(rays, model, *, features, images, K4, Einv, near=None, far=None, n_sa
 
 
 def render_view(model, src_colors, src_camera_configs, tgt_camera_config, combined_features=None, generator=None,
-                chunk=None):
+                chunk=None, range_check=False):
     """model_v0.py:243-281.  src_colors: list of (H,W,>=3) uint8 images; camera configs: dicts with
     'pose' (4x4) and 'intrinsics' (9,).  Returns (rgb (H,W,3) uint8, depth (H,W,1) uint8) as NumPy.
     Everything between the upload of the source views and the download of the two uint8 images stays on
-    the device; `chunk` rays per `_call` (default: the whole image in one call)."""
+    the device; `chunk` rays per `_call` (default: the whole image in one call).
+    range_check: render on the range-guarded split_f16 kernel; the status is zeroed before the frame and read ONCE behind its last
+    chunk (one host synchronisation per frame).  Out of range the frame is rendered again on 'split_bf16' with a RuntimeWarning
+    (range_policy='fallback') or FloatingPointError is raised ('raise')."""
     dev = model.device
     tgt_k = np.reshape(tgt_camera_config['intrinsics'], (3, 3)).astype(np.float32)
     h, w = src_colors[0].shape[:2]
@@ -411,10 +514,35 @@ def render_view(model, src_colors, src_camera_configs, tgt_camera_config, combin
     rgbs = torch.empty((n, 3), dtype=torch.float32, device=dev)
     depths = torch.empty((n,), dtype=torch.float32, device=dev)
     frame = object() if model.compute_dtype == 'f32' else None           # texel tables: built by the first chunk, then re-used
-    for i in range(0, n, chunk):
-        sl = slice(i, min(n, i + chunk))
-        kw = {'scene_key': frame} if frame is not None else {}
-        out = model.infer((rays_o[None, sl], rays_d[None, sl], images, k4, einv), combined_features, generator=generator, **kw)
-        rgbs[sl], depths[sl] = out[2][0], out[3][0]
+
+    def render_chunks(**kw):
+        if frame is not None:
+            kw['scene_key'] = frame
+        for i in range(0, n, chunk):
+            sl = slice(i, min(n, i + chunk))
+            out = model.infer((rays_o[None, sl], rays_d[None, sl], images, k4, einv), combined_features, generator=generator, **kw)
+            rgbs[sl], depths[sl] = out[2][0], out[3][0]
+
+    guarded = bool(range_check) and model.compute_dtype == 'f32' and model.f32_gemm == 'split_f16' and model.range_policy != 'off'
+    if guarded:
+        model.range_reset()
+        # (a fallback frame draws the same uniforms as the frame it replaces)
+        rng_state = generator.get_state() if generator is not None else torch.cuda.get_rng_state(dev)
+        render_chunks(range_check=True)
+        rep = model.range_report()                                        # the frame's one host read
+        max_a = rp.worst([rep['coarse']['max_activation'], rep['fine']['max_activation']])
+        # (the weights have been dealt with by the calls themselves: out of range they already ran on 'split_bf16', which leaves the status at 0)
+        action = rp.decide(model.range_policy, model.f32_gemm, max_activation=max_a)
+        if action == rp.RAISE:
+            raise FloatingPointError(rp.describe(None, max_a))
+        if action == rp.FALLBACK:
+            warnings.warn(rp.describe(None, max_a) + " - rendering the frame again on 'split_bf16'", RuntimeWarning, stacklevel=2)
+            if generator is not None:
+                generator.set_state(rng_state)
+            else:
+                torch.cuda.set_rng_state(rng_state, dev)
+            render_chunks(kernel='split_bf16')
+    else:
+        render_chunks()
     rgb8, depth8 = ops.finish_view(rgbs, depths)
     return rgb8.reshape(h, w, 3).cpu().numpy(), depth8.reshape(h, w, 1).cpu().numpy()

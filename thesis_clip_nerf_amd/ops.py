@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import NET_PARAMS, Q7_CLAMP, Q7_ZERO  # noqa: F401
+from ._lib import F16X3_MAX_ACT, F16X3_MAX_WEIGHT, NET_PARAMS, Q7_CLAMP, Q7_ZERO  # noqa: F401
 
 
 def _chk(t, name, dtype=torch.float32, shape=None):
@@ -149,10 +149,11 @@ def project_texels2(features, packed_a, packed_b, out=None):
 
 def _field_pass(what, fn, rays_o, rays_d, z, scene, packed_net, second=None, texel_table=None, table_arg=True, wide=True,
                 features_dtype=torch.float32, return_taps=False, return_pix=False, return_embedding=False, complete_output=False,
-                return_fused_acts=False):
+                return_fused_acts=False, extra=()):
     """The checks, output allocation, C call and result tuple of field_eval / field_eval_split / field_eval_bf16.
     fn: the entry point; second: (tensor, name, bytes) of the weight stream it takes behind packed_net; table_arg: it takes a
-    texel_table; wide: it has the pix and per-view outputs (the bf16 entry points do not)."""
+    texel_table; wide: it has the pix and per-view outputs (the bf16 entry points do not); extra: what an _ex entry point takes
+    in front of the stream."""
     _chk(rays_o, 'rays_o', shape=(None, None, 3))
     b, r, _ = rays_o.shape
     _chk(rays_d, 'rays_d', shape=(b, r, 3))
@@ -175,7 +176,7 @@ def _field_pass(what, fn, rays_o, rays_d, z, scene, packed_net, second=None, tex
     ins = [rays_o, rays_d, z, scene[0], scene[1]] + ([texel_table] if table_arg else []) + [scene[2], scene[3], packed_net]
     outs = [rgbs, taps, pix, emb, acts_v, acts_f] if wide else [rgbs, taps, emb, acts_f]
     with torch.cuda.device(dev):
-        rc = fn(*map(_p, ins + ([] if second is None else [second[0]])), b, v, r, s, h, w, *map(_p, outs + [ws]), _stream(rays_o))
+        rc = fn(*map(_p, ins + ([] if second is None else [second[0]])), b, v, r, s, h, w, *map(_p, outs + [ws]), *extra, _stream(rays_o))
     _lib.check(rc, what)
     out = (rgbs,)
     if return_taps:
@@ -274,9 +275,11 @@ def render_workspace_bytes(b, v, r, s):
 
 
 def render_fwd(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, packed_coarse, packed_fine, u_coarse,
-               u_fine, near, far, q7_mode=Q7_ZERO, workspace=None, out=None, texel_tables=None, tables_ready=False, split=None):
+               u_fine, near, far, q7_mode=Q7_ZERO, workspace=None, out=None, texel_tables=None, tables_ready=False, split=None,
+               kernel=None, range_status=None):
     """mvnerf_render_fwd = MVVNeRFRenderer._call (model_v0.py:113-184) -> (rgb, depth, fine_rgb, fine_depth).
     split: (pack_net_split(coarse), pack_net_split(fine)) -> mvnerf_render_fwd_split (fp32-grade Dense layers on the bf16 MFMA).
+    kernel, range_status (split path only): see field_eval_split; range_status here is TWO floats (coarse pass, fine pass).
     texel_tables: None = gather raw features; 'auto' = allocate and build when texel_table_pays(); or a float32
     tensor (2,B,V,H,W,128) [coarse net | fine net], built by this call unless tables_ready."""
     _chk(rays_o, 'rays_o', shape=(None, None, 3))
@@ -307,6 +310,8 @@ def render_fwd(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, pac
         _chk(texel_tables, 'texel_tables', shape=(2, b, v, h, w, 128))
     with torch.cuda.device(dev):
         if split is None:
+            if kernel is not None or range_status is not None:
+                raise ValueError('kernel / range_status belong to the split path: pass split=')
             rc = _lib.lib().mvnerf_render_fwd(_p(rays_o), _p(rays_d), _p(images), _p(features), _p(intrinsics),
                                               _p(extrinsics_inv), _p(packed_coarse), _p(packed_fine), _p(u_coarse),
                                               _p(u_fine), b, v, r, s, h, w, float(near), float(far), int(q7_mode), _p(rgb),
@@ -316,6 +321,15 @@ def render_fwd(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, pac
             nbytes = int(_lib.lib().mvnerf_packed_net_split_bytes())
             _chk(split[0], 'split_coarse', dtype=torch.uint8, shape=(nbytes,))
             _chk(split[1], 'split_fine', dtype=torch.uint8, shape=(nbytes,))
+            ex = _split_ex_args(kernel, range_status, 2)
+            if ex is not None:
+                rc = _lib.lib().mvnerf_render_fwd_split_ex(_p(rays_o), _p(rays_d), _p(images), _p(features), _p(intrinsics),
+                                                           _p(extrinsics_inv), _p(packed_coarse), _p(packed_fine), _p(split[0]), _p(split[1]),
+                                                           _p(u_coarse), _p(u_fine), b, v, r, s, h, w, float(near), float(far),
+                                                           int(q7_mode), _p(rgb), _p(depth), _p(fine_rgb), _p(fine_depth), _p(workspace),
+                                                           _p(texel_tables), int(bool(tables_ready)), *ex, _stream(rays_o))
+                _lib.check(rc, 'render_fwd')
+                return rgb, depth, fine_rgb, fine_depth
             rc = _lib.lib().mvnerf_render_fwd_split(_p(rays_o), _p(rays_d), _p(images), _p(features), _p(intrinsics),
                                                     _p(extrinsics_inv), _p(packed_coarse), _p(packed_fine), _p(split[0]), _p(split[1]),
                                                     _p(u_coarse), _p(u_fine), b, v, r, s, h, w, float(near), float(far),
@@ -459,9 +473,10 @@ def stash_bytes(b, v, r, s):
 
 
 def field_eval_stash(rays_o, rays_d, z, images, features, intrinsics, extrinsics_inv, packed_net, stash=None, texel_table=None,
-                     packed_split=None):
+                     packed_split=None, kernel=None, range_status=None):
     """Training-mode field pass: -> (rgbs (B,R,S,4), stash uint8 tensor with the trunk pre-activations).
-    packed_split: pack_net_split(net) -> the split-bf16 kernel (mvnerf_field_eval_stash_split), same stash."""
+    packed_split: pack_net_split(net) -> the split-bf16 kernel (mvnerf_field_eval_stash_split), same stash.
+    kernel, range_status (with packed_split): as field_eval_split -> mvnerf_field_eval_stash_split_ex."""
     _chk(rays_o, 'rays_o', shape=(None, None, 3))
     b, r, _ = rays_o.shape
     _chk(rays_d, 'rays_d', shape=(b, r, 3))
@@ -479,11 +494,20 @@ def field_eval_stash(rays_o, rays_d, z, images, features, intrinsics, extrinsics
         if texel_table is not None:
             _chk(texel_table, 'texel_table', shape=(b, v, h, w, 128))
         if packed_split is None:
+            if kernel is not None or range_status is not None:
+                raise ValueError('kernel / range_status belong to the split path: pass packed_split=')
             rc = _lib.lib().mvnerf_field_eval_stash(_p(rays_o), _p(rays_d), _p(z), _p(images), _p(features), _p(texel_table),
                                                     _p(intrinsics), _p(extrinsics_inv), _p(packed_net), b, v, r, s, h, w, _p(rgbs),
                                                     _p(stash), _p(ws), _stream(rays_o))
         else:
             _chk(packed_split, 'packed_split', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_packed_net_split_bytes()),))
+            ex = _split_ex_args(kernel, range_status, 1)
+            if ex is not None:
+                rc = _lib.lib().mvnerf_field_eval_stash_split_ex(_p(rays_o), _p(rays_d), _p(z), _p(images), _p(features), _p(texel_table),
+                                                                 _p(intrinsics), _p(extrinsics_inv), _p(packed_net), _p(packed_split), b, v, r,
+                                                                 s, h, w, _p(rgbs), _p(stash), _p(ws), *ex, _stream(rays_o))
+                _lib.check(rc, 'field_eval_stash')
+                return rgbs, stash
             rc = _lib.lib().mvnerf_field_eval_stash_split(_p(rays_o), _p(rays_d), _p(z), _p(images), _p(features), _p(texel_table),
                                                           _p(intrinsics), _p(extrinsics_inv), _p(packed_net), _p(packed_split), b, v, r, s,
                                                           h, w, _p(rgbs), _p(stash), _p(ws), _stream(rays_o))
@@ -1002,6 +1026,29 @@ def set_split_kernel(name):
     return {v: k for k, v in SPLIT_KERNELS.items()}[prev]
 
 
+def _split_ex_args(kernel, range_status, n_status):
+    """(which, range_status pointer) of an _ex entry point, or None when both keywords are left alone (the plain entry point runs)."""
+    if kernel is None and range_status is None:
+        return None
+    if kernel is not None and kernel not in SPLIT_KERNELS:
+        raise ValueError(f'kernel must be None or one of {sorted(SPLIT_KERNELS)}, got {kernel!r}')
+    if range_status is not None:
+        _chk(range_status, 'range_status', shape=(n_status,))
+    return (-1 if kernel is None else SPLIT_KERNELS[kernel], _p(range_status))
+
+
+def net_range(net_keras, out=None):
+    """mvnerf_net_range: -> device tensor [max |w| over the weights pack_net_split cuts (W0, the 12 hidden kernels), max |.| over all
+    variables]; NaN stays NaN.  Compare [0] with F16X3_MAX_WEIGHT.  No host synchronisation here."""
+    _chk(net_keras, 'net_keras', shape=(NET_PARAMS,))
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=net_keras.device)
+    _chk(out, 'out', shape=(2,))
+    with torch.cuda.device(net_keras.device):
+        _lib.check(_lib.lib().mvnerf_net_range(_p(net_keras), _p(out), _stream(net_keras)), 'net_range')
+    return out
+
+
 def set_deterministic(on=True):
     """mvnerf_set_deterministic.  Weight gradients are ALWAYS summed in a fixed order since round 2 (stored per-workgroup partials +
     a parallel fixed-order reduction turned out faster than fp32 atomics); the call is kept for its callers, records the flag and
@@ -1108,13 +1155,19 @@ def pack_net_split(net_keras):
 
 
 def field_eval_split(rays_o, rays_d, z, images, features, intrinsics, extrinsics_inv, packed_net, packed_split, return_taps=False,
-                     return_pix=False, return_embedding=False, complete_output=False, texel_table=None):
+                     return_pix=False, return_embedding=False, complete_output=False, texel_table=None, kernel=None, range_status=None):
     """mvnerf_field_eval_split: field_eval (same outputs, same fp32 bar) with the Dense layers as split-bf16 MFMA products.
-    texel_table: project_texels(features, packed_net) of the same net (fp32)."""
-    return _field_pass('field_eval_split', _lib.lib().mvnerf_field_eval_split, rays_o, rays_d, z, (images, features, intrinsics, extrinsics_inv),
+    texel_table: project_texels(features, packed_net) of the same net (fp32).
+    kernel: None (the process-wide choice, set_split_kernel) or a SPLIT_KERNELS name for this call only.
+    range_status: None, or one device float the caller has zeroed: the 'split_f16' kernel then runs range-guarded and max-accumulates
+    the largest |activation| it cuts into fp16 pieces (compare with F16X3_MAX_ACT; reading it is the caller's synchronisation).
+    With both left at None the plain entry point runs; otherwise mvnerf_field_eval_split_ex."""
+    ex = _split_ex_args(kernel, range_status, 1)
+    fn = _lib.lib().mvnerf_field_eval_split if ex is None else _lib.lib().mvnerf_field_eval_split_ex
+    return _field_pass('field_eval_split', fn, rays_o, rays_d, z, (images, features, intrinsics, extrinsics_inv),
                        packed_net, second=(packed_split, 'packed_split', int(_lib.lib().mvnerf_packed_net_split_bytes())),
                        texel_table=texel_table, return_taps=return_taps, return_pix=return_pix, return_embedding=return_embedding,
-                       complete_output=complete_output)
+                       complete_output=complete_output, extra=ex or ())
 
 
 def render_fwd_split(rays_o, rays_d, images, features, intrinsics, extrinsics_inv, packed_coarse, packed_fine, split_coarse,

@@ -190,19 +190,34 @@ def init_training_session(model_log_dir):
     return start_epoch, training_progress_file
 
 
-def fit(nerf_renderer, data_generator, epochs, initial_epoch=0, log=print):
-    """Keras `Model.fit(generator, epochs=, initial_epoch=)` over the custom train_step."""
+def fit(nerf_renderer, data_generator, epochs, initial_epoch=0, log=print, keep=None):
+    """Keras `Model.fit(generator, epochs=, initial_epoch=)` over the custom train_step.
+    keep: a dict that receives the last batch as keep['batch'] = (inputs, features) (train_model's range check reads it)."""
     history = []
     for epoch in range(initial_epoch, epochs):
         losses = []
         for step in range(len(data_generator)):
             (inputs, features), targets = data_generator[step]
             losses.append(nerf_renderer.train_step((inputs, targets), combined_features=features)['loss'])
+            if keep is not None:
+                keep['batch'] = (inputs, features)
         data_generator.on_epoch_end()
         mean = float(torch.cat(losses).mean()) if losses else float('nan')
         history.append(mean)
         log(f'Epoch {epoch + 1}/{epochs} - loss: {mean:.6f}')
     return history
+
+
+def check_training_range(nerf_renderer, batch):
+    """A training step on the default fp32 path is only valid while every stashed pre-activation stays below 1023: the backward's
+    weight-gradient GEMM cuts relu(a) as rn16(64 a), and beyond that limit it feeds NaN to Adam.  Runs the guarded
+    forward on `batch` = (inputs, features) and raises FloatingPointError naming the limit; one host synchronisation."""
+    if batch is None or getattr(nerf_renderer, 'f32_gemm', None) == 'mfma_f32' or getattr(nerf_renderer, 'range_policy', 'off') == 'off':
+        return None
+    rep = nerf_renderer.check_range(batch[0], batch[1], training=True)
+    if not rep['in_range']:
+        raise FloatingPointError(f"training has left the range of the fp16 backward (limit {rep['limit']:g}): {rep['message']}")
+    return rep
 
 
 def write_ppm(path, image):
@@ -231,7 +246,9 @@ def train_model(nerf_renderer, data_generator, n_epochs, eval_after_epochs, mode
     history = []
     for k in range(start_n_fit, n_fits):
         e_epoch = (k + 1) * eval_after_epochs
-        history += fit(nerf_renderer, data_generator, epochs=e_epoch, initial_epoch=k * eval_after_epochs, log=log)
+        last = {}
+        history += fit(nerf_renderer, data_generator, epochs=e_epoch, initial_epoch=k * eval_after_epochs, log=log, keep=last)
+        check_training_range(nerf_renderer, last.get('batch'))          # before the next interval's steps can poison Adam
         write_ppm(f'{model_log_dir}/valid/valid-{e_epoch}.ppm', validate(nerf_renderer, tgt_color, valid_data))
         with open(training_progress_file, 'w') as f:
             json.dump({'epoch': e_epoch}, f)
