@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from thesis_clip_nerf_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,3 +138,34 @@ def test_round3_entry_points_validate_their_arguments():
     assert lib.mvnerf_gemm_tn_batched(ctypes.byref(q), one, None, 64, 64, 64, 1, None, None) == -1        # ... without an output
     assert lib.mvnerf_gemm_tn_batched_scratch_bytes(64512, 64, 128, 4, 1) > 0
     assert lib.mvnerf_gemm_tn_batched_scratch_bytes(60, 64, 128, 4, 1) == 0
+
+
+# Return values of the size functions, recorded from the library as it was before the workspace carvers and the stash arithmetic
+# were given one owner each: they pin every carver's order and alignment.
+# (B, V, R or N, S, H, W, P or np, n5, use_texel_tables, want_d_features) -> (stash, field_backward_scratch, query_vjp_scratch,
+# query_workspace, render_workspace, train_workspace, grasp_workspace, language_workspace bytes, language_grad floats)
+PINNED_SIZES = [
+    ((1, 1, 32, 64, 16, 16, 3, 7, 0, 0), (14680064, 15863296, 49152, 32768, 147456, 76042752, 413184, 3560960, 152257)),
+    ((1, 1, 40, 64, 16, 16, 3, 1, 1, 0), (18350080, 19828224, 98304, 40960, 184320, 95314432, 302336, 1868032, 78529)),
+    ((2, 2, 32, 64, 16, 16, 3, 7, 1, 1), (44040192, 62918144, 196608, 131072, 327680, 210310144, 1322752, 4835840, 152257)),
+    ((2, 2, 33, 64, 8, 8, 3, 1, 0, 0), (45416448, 63327744, 294912, 135168, 337920, 213704192, 1322752, 3078656, 78529)),
+    ((1, 3, 64, 64, 8, 8, 5, 7, 1, 1), (58720256, 69209600, 294912, 196608, 360448, 265688064, 1681920, 5225984, 152257)),
+    ((2, 3, 40, 1, 8, 8, 3, 7, 0, 1), (1376256, 2209280, 442368, 245760, 128000, 7485952, 1683200, 5261824, 152257)),
+    ((2, 1, 33, 1, 8, 8, 3, 7, 0, 0), (688128, 747008, 147456, 67584, 38016, 3124224, 825856, 3981056, 152257)),
+    ((1, 2, 64, 1, 8, 8, 32, 1, 1, 0), (688128, 986624, 196608, 131072, 69632, 4240384, 699136, 2621440, 78529)),
+    ((3, 3, 31, 1, 8, 8, 2, 7, 0, 0), (1376256, 2209280, 442368, 285696, 148800, 8701952, 2521600, 6215936, 152257)),
+    ((1, 1, 1, 1, 2, 2, 1, 1, 0, 0), (229376, 251392, 49152, 1024, 576, 713728, 287488, 1854720, 78529)),
+    ((2, 2, 96, 128, 8, 8, 9, 7, 1, 1), (264241152, 128454144, 589824, 393216, 1769472, 1003560960, 2653184, 8027904, 152257)),
+    ((4, 3, 17, 64, 12, 20, 4, 7, 1, 0), (62390272, 70422016, 442368, 208896, 382976, 281816576, 3371520, 8035072, 152257)),
+]
+
+
+@pytest.mark.parametrize('shape,expected', PINNED_SIZES, ids=['-'.join(map(str, s)) for s, _ in PINNED_SIZES])
+def test_size_functions_keep_their_recorded_values(shape, expected):
+    B, V, R, S, H, W, P, n5, tables, d_features = shape
+    lib = _lib.lib()
+    got = (lib.mvnerf_stash_bytes(B, V, R, S), lib.mvnerf_field_backward_scratch_bytes(B, V, R, S), lib.mvnerf_query_vjp_scratch_bytes(B, V, R),
+           lib.mvnerf_query_workspace_bytes(B, V, R), lib.mvnerf_render_workspace_bytes(B, V, R, S),
+           lib.mvnerf_train_workspace_bytes(B, V, R, S, H, W, tables, d_features), lib.mvnerf_grasp_workspace_bytes(B, V, P, n5),
+           lib.mvnerf_language_workspace_bytes(B, V, H, W, P, n5), lib.mvnerf_language_grad_floats(n5))
+    assert got == expected

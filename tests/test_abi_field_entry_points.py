@@ -20,7 +20,7 @@ from thesis_clip_nerf_amd import _lib
 E_ARG, E_SHAPE, E_ALIGN = -1, -2, -3
 
 # everything that is not a pointer, by argument name
-BASE = {'B': 1, 'V': 1, 'R': 4, 'S': 64, 'H': 8, 'W': 8, 'near_': 0.3, 'far_': 1.3, 'q7_mode': 0, 'tables_ready': 0}
+BASE = {'B': 1, 'V': 1, 'R': 4, 'S': 64, 'N': 40, 'H': 8, 'W': 8, 'near_': 0.3, 'far_': 1.3, 'q7_mode': 0, 'tables_ready': 0}
 
 # Argument lists in ABI order (include/mvnerf_hip.h).  name* = must be 16-byte aligned, name? = optional (NULL in the baseline),
 # name~ = required, but only checked after the entry point's first launch: never faulted here.
@@ -34,6 +34,13 @@ _TEXELS = ' B V H W texel_table* texel_table_b? stream?'
 _RENDER_IN = 'rays_o~ rays_d~ images~ features~ intrinsics~ extrinsics_inv~ packed_coarse~ packed_fine '
 _RENDER_OUT = ('u_coarse u_fine B V R S H W near_ far_ q7_mode rgb depth fine_rgb fine_depth workspace* texel_tables? '
                'tables_ready stream?')
+# the backward and query entry points (recorded before their stash arithmetic and their walk through the trunk were shared)
+_BACKWARD = ('rays_o rays_d z images features texel_table?* texel_grad?* intrinsics extrinsics_inv net_keras* bwd_streams* stash* rgbs* '
+             'd_rgbs* B V R S H W scratch* grad d_z? d_features? stream?')
+_QUERY_VJP = ('points dirs images features* intrinsics extrinsics_inv bwd_streams* stash* g_acts* B V N H W scratch* d_points d_dirs '
+              'stream?')
+_QUERY_JVP = ('points dirs t_points t_dirs images features* intrinsics extrinsics_inv packed_net* B V N H W acts?* t_acts* workspace* '
+              'stream?')
 
 FIELD_CODES = {'null': E_ARG, 'misaligned': E_ALIGN, 'zero': E_ARG, 'hw1': E_SHAPE}
 STASH_CODES = {'null': E_ARG, 'misaligned': E_ALIGN, 'zero': E_ARG, 'hw1': E_ARG}
@@ -59,6 +66,14 @@ TEXEL_ROWS = [('second net without its table', dict(second_net=0), E_ARG, 'go to
 # what the entry point itself checks up front can be faulted (S first, so S = 0 is a shape error like every S != 64)
 RENDER_ROWS = [('S=32', dict(S=32), E_SHAPE, 'n_samples=64', False), ('S=128', dict(S=128), E_SHAPE, 'n_samples=64', False),
                ('S=0', dict(S=0), E_SHAPE, 'n_samples=64', False)]
+BACKWARD_CODES = {'null': E_ARG, 'misaligned': E_ALIGN, 'zero': E_ARG, 'hw1': E_ARG}
+QUERY_JVP_CODES = {'null': E_ARG, 'misaligned': E_ALIGN, 'zero': E_ARG, 'hw1': E_SHAPE}
+FUSED_ACTS_CODES = {'null': E_ARG, 'misaligned': E_ALIGN, 'zero': E_ARG}
+# V = 2 with a row count that is no multiple of 32: refused where the per-view tiles are walked; the tangent pass and the fused
+# activations have no such limit and go on to launch (code None: as the baseline)
+BACKWARD_ROWS = [('V=2,R*S=15', dict(V=2, R=15, S=1), E_SHAPE, 'multiple of 32', False)]
+QUERY_VJP_ROWS = [('V=2,N=40', dict(V=2), E_SHAPE, 'multiple of 32', False)]
+NO_TILE_LIMIT_ROWS = [('V=2,N=40 passes', dict(V=2), None, '', False)]
 
 # name, family the message must name, arguments, sizes that may not be 0, codes per fault class, extra rows
 ENTRY_POINTS = [
@@ -82,6 +97,10 @@ ENTRY_POINTS = [
     ('mvnerf_render_fwd', 'mvnerf_render_fwd', _RENDER_IN + _RENDER_OUT, 'BR', RENDER_CODES, RENDER_ROWS),
     ('mvnerf_render_fwd_split', 'mvnerf_render_fwd_split', _RENDER_IN + 'split_coarse split_fine ' + _RENDER_OUT, 'BR', RENDER_CODES,
      RENDER_ROWS),
+    ('mvnerf_field_backward_table', 'mvnerf_field_backward', _BACKWARD, 'BVRS', BACKWARD_CODES, BACKWARD_ROWS),
+    ('mvnerf_query_vjp', 'mvnerf_query_vjp', _QUERY_VJP, 'BVN', BACKWARD_CODES, QUERY_VJP_ROWS),
+    ('mvnerf_query_jvp', 'mvnerf_query_jvp', _QUERY_JVP, 'BVN', QUERY_JVP_CODES, NO_TILE_LIMIT_ROWS),
+    ('mvnerf_stash_fused_acts', 'mvnerf_stash_fused_acts', 'stash* B V N acts* stream?', 'BVN', FUSED_ACTS_CODES, NO_TILE_LIMIT_ROWS),
 ]
 
 

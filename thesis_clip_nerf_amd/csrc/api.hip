@@ -10,8 +10,7 @@
 
 #include <atomic>
 
-#include "../../include/mvnerf_hip.h"
-#include "mvnerf_kernels.h"
+#include "mvnerf_api.h"
 #include "mvnerf_math.h"
 #include "mvnerf_pack.h"
 
@@ -33,13 +32,7 @@ namespace {
 
 constexpr auto& fail = mvnerf::api_fail;
 
-int hip_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    return fail((int)e, "%s: %s", what, hipGetErrorString(e));
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+using mvnerf::aligned16, mvnerf::aligned4, mvnerf::hip_status, mvnerf::StashLayout;
 
 // The two arguments the _ex entry points add: `which` (-1 or a MVNERF_SPLIT_* value) is checked before everything else, the
 // alignment of `range_status` with the other alignments (after them).
@@ -60,15 +53,15 @@ struct Workspace {          // carve-up of the caller's scratch for mvnerf_rende
 
 Workspace carve(void* base, long n_rays, int V, int S) {
     Workspace w;
-    float* p = static_cast<float*>(base);
+    mvnerf::Bump ws(base, sizeof(float));           // (packed: the pieces follow each other float by float)
     const size_t n = (size_t)n_rays * S;
-    w.z = p;            p += n;
-    w.weights = p;      p += n;
-    w.z_all = p;        p += 2 * n;
-    w.rgbs_c = p;       p += 4 * n;
-    w.rgbs_f = p;       p += 8 * n;
-    w.dir_bias = p;     p += (size_t)n_rays * V * 128;
-    w.bytes = (size_t)(p - static_cast<float*>(base)) * sizeof(float);
+    w.z = ws.floats(n);
+    w.weights = ws.floats(n);
+    w.z_all = ws.floats(2 * n);
+    w.rgbs_c = ws.floats(4 * n);
+    w.rgbs_f = ws.floats(8 * n);
+    w.dir_bias = ws.floats((size_t)n_rays * V * 128);
+    w.bytes = ws.bytes();
     return w;
 }
 
@@ -100,11 +93,12 @@ int field_params(const char* who, const FieldArgs& a, FieldKind kind, mvnerf::Fi
     if (a.H < 2 || a.W < 2) return fail(kind.hw_code, "%s: source image %dx%d, need H,W >= 2 (bilinear taps)", who, a.H, a.W);
     if (kind.stash && a.V > 1 && ((long)a.R * a.S) % 32 != 0)
         return fail(MVNERF_E_SHAPE, "%s: R*S=%ld must be a multiple of 32 when V > 1", who, (long)a.R * a.S);
-    const long total = (long)a.B * a.R * a.S, n_tiles = (total + 31) / 32;
+    const StashLayout L(a.B, a.V, (long)a.R * a.S);
+    const long total = L.total, n_tiles = L.n_tiles;
     if (total >= (1L << 31) || (long)a.B * a.V * a.H * a.W >= (1L << 31))
         return fail(MVNERF_E_SHAPE, "%s: B*R*S=%ld or B*V*H*W too large for int32 indices", who, total);
-    if (kind.stash && (long)a.V * n_tiles >= (1L << 18))      // stash slots are addressed with 32-bit byte offsets (16 KiB per tile)
-        return fail(MVNERF_E_SHAPE, "%s: V*B*R*S/32 = %ld tiles per stash slot, at most 262143", who, (long)a.V * n_tiles);
+    if (kind.stash && L.view_tiles >= (1L << 18))             // stash slots are addressed with 32-bit byte offsets (16 KiB per tile)
+        return fail(MVNERF_E_SHAPE, "%s: V*B*R*S/32 = %ld tiles per stash slot, at most 262143", who, L.view_tiles);
     if (!aligned16(a.features) || !aligned16(a.texel_table) || !aligned16(a.packed_net) || !aligned16(a.second) || !aligned16(a.rgbs) ||
         !aligned16(a.tap_idx) || !aligned16(a.embedding) || !aligned16(a.acts_per_view) || !aligned16(a.acts_fused) || !aligned16(a.stash) ||
         !aligned16(a.workspace))           // (NULL counts as aligned: the optional ones are checked when given)
@@ -120,9 +114,9 @@ int field_params(const char* who, const FieldArgs& a, FieldKind kind, mvnerf::Fi
     p.n_tiles = n_tiles;
     if (a.stash) {
         p.stash = a.stash;
-        p.stash_stride = (long)a.V * n_tiles * 4096;
-        p.stash_fused = a.stash + 7 * p.stash_stride;
-        p.stash_fused_stride = n_tiles * 4096;
+        p.stash_stride = L.view_stride();
+        p.stash_fused = a.stash + L.fused_slot(0);
+        p.stash_fused_stride = L.fused_stride();
     }
     *out = p;
     return 0;
@@ -406,15 +400,50 @@ int mvnerf_finish_view(const float* rgb, const float* depth, long n, float* minm
 
 // ---- training --------------------------------------------------------------------------------------------
 namespace {
-long tiles_for(int B, int R, int S) { return ((long)B * R * S + 31) / 32; }
 constexpr int kBwdMaxWGs = 512;      // resident workgroups of the dW kernels (2 per CU)
 constexpr int kFusedBwdWGs = 512;    // fused dX+dW kernel: 2 waves/SIMD by registers -> 2 resident workgroups per CU
 static_assert(kBwdMaxWGs == kFusedBwdWGs, "partial_floats() assumes one workgroup budget for every weight-gradient kernel");
+
+// The backward walk through the trunk's residual blocks, 5..0, of mvnerf_field_backward_table and mvnerf_query_vjp: three tile buffers of
+// one per-view slot each at the front of `scratch` rotate through the roles g / dh / gn.  grad() is dL/d(output of the next block): the
+// caller puts its cotangent there first and finds dL/d(layer-0 output) there after block 0.  block(bi) hands out what the block's two
+// Dense launches read and write; what else they are given (weight gradients, partials, amax) and what enters between blocks is the caller's.
+struct TrunkBwd {
+    struct Block {
+        bool fused; long nt;             // blocks 3..5 work on the view mean: n_tiles tiles, the others on view_tiles
+        const float *pre_in, *pre_hid;   // stashed pre-activations: the block's input and its hidden layer
+        const float *w1, *w2;            // backward weight streams of the first and the second Dense
+        float *g, *dh, *gn;              // dL/d(block output), dL/d(hidden), dL/d(block input)
+    };
+    StashLayout L;
+    int B, V;
+    const float *stash, *bwd_streams;
+    float* scratch;
+    int g = 0;
+    float* buf(int i) const { return scratch + (size_t)(i % 3) * L.view_stride(); }
+    float* grad() const { return buf(g); }
+    // In front of block 2 the gradient of the view mean goes back to the views (reduce_mean, layers.py:368-370): the one launch in here.
+    hipError_t block(int bi, Block* b, hipStream_t st) {
+        if (bi == 2 && V > 1) {
+            const hipError_t e = mvnerf::launch_view_broadcast(buf(g), V, L.n_tiles / B, L.n_tiles, buf(g + 1), st);
+            if (e != hipSuccess) return e;
+            g = (g + 1) % 3;
+        }
+        b->fused = bi >= 3;
+        b->nt = b->fused ? L.n_tiles : L.view_tiles;
+        b->pre_in = stash + (b->fused ? L.fused_slot(2 * (bi - 3)) : L.view_slot(2 * bi));
+        b->pre_hid = stash + (b->fused ? L.fused_slot(2 * (bi - 3) + 1) : L.view_slot(2 * bi + 1));
+        b->w1 = bwd_streams + (size_t)(2 * bi) * mvnerf::kHiddenWFloats; b->w2 = b->w1 + mvnerf::kHiddenWFloats;
+        b->g = buf(g); b->dh = buf(g + 1); b->gn = buf(g + 2);
+        g = (g + 2) % 3;
+        return hipSuccess;
+    }
+};
 }  // namespace
 
 size_t mvnerf_stash_bytes(int B, int V, int R, int S) {
     if (B <= 0 || V <= 0 || R <= 0 || S <= 0) return 0;
-    return (size_t)(7 * V + 7) * tiles_for(B, R, S) * 128 * 32 * sizeof(float);     // 7 per-view + 7 fused slots
+    return StashLayout(B, V, (long)R * S).bytes();
 }
 
 // Per-workgroup partials of a weight-gradient span, summed in workgroup order by reduce_partials_kernel.  The three users:
@@ -434,7 +463,8 @@ std::atomic<int> g_deterministic{0};
 
 size_t mvnerf_field_backward_scratch_bytes(int B, int V, int R, int S) {
     if (B <= 0 || V <= 0 || R <= 0 || S <= 0) return 0;
-    return ((size_t)tiles_for(B, R, S) * ((size_t)3 * V * 128 + 32) * 32 + partial_floats(tiles_for(B, R, S), V)) * sizeof(float);
+    const long n_tiles = StashLayout(B, V, (long)R * S).n_tiles;          // three tile buffers, the read-out's cotangent tile, the partials
+    return ((size_t)n_tiles * ((size_t)3 * V * 128 + 32) * 32 + partial_floats(n_tiles, V)) * sizeof(float);
 }
 
 int mvnerf_set_deterministic(int on) { return g_deterministic.exchange(on ? 1 : 0); }
@@ -532,69 +562,55 @@ int mvnerf_field_backward_table(const float* rays_o, const float* rays_d, const 
     if (!aligned16(net_keras) || !aligned16(bwd_streams) || !aligned16(stash) || !aligned16(rgbs) || !aligned16(d_rgbs) || !aligned16(scratch))
         return fail(MVNERF_E_ALIGN, "mvnerf_field_backward: net_keras, bwd_streams, stash, rgbs, d_rgbs, scratch must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const long total = (long)B * R * S, n_tiles = (total + 31) / 32, view_tiles = n_tiles * V;
-    const size_t vslot = (size_t)view_tiles * 4096, fslot = (size_t)n_tiles * 4096;
-    float* buf[3] = {static_cast<float*>(scratch), static_cast<float*>(scratch) + vslot, static_cast<float*>(scratch) + 2 * vslot};
-    float* do_tl = static_cast<float*>(scratch) + 3 * vslot;
+    const char* const who = "mvnerf_field_backward";
+    const StashLayout L(B, V, (long)R * S);
+    const long total = L.total, n_tiles = L.n_tiles;
+    TrunkBwd walk = {L, B, V, stash, bwd_streams, static_cast<float*>(scratch)};
+    float* do_tl = static_cast<float*>(scratch) + 3 * L.view_stride();
     // per-workgroup partials of every weight-gradient span, added in workgroup order by reduce_partials_kernel: bit-identical from run
     // to run AND faster than fp32 atomics onto the same addresses (7.54 vs 7.60 ms per step at cfg2), so it is the only mode since
     // round 2; mvnerf_set_deterministic is kept for its callers and has no effect on the weight gradients any more
     float* part = do_tl + (size_t)n_tiles * 32 * 32;
-    auto view_slot = [&](int k) { return stash + (size_t)k * vslot; };                   // x0,h1,x1,h2,x2,h3,x3
-    auto fused_slot = [&](int m) { return stash + 7 * vslot + (size_t)m * fslot; };      // mean,h4,x4,h5,x5,h6,x6
-    hipError_t e;
-#define MV_TRY(call) if ((e = (call)) != hipSuccess) return hip_status(e, "mvnerf_field_backward")
     // max |g| slots of the 13 gradient tensors of the chain (zeroed here, filled by each tensor's producer)
     float* amax = part + partial_only_floats(n_tiles, V);
-    MV_TRY(mvnerf::launch_zero(amax, (size_t)kAmaxTensors * mvnerf::kBwdAmaxSlots * sizeof(float), st));
-    int am = 0;                                        // amax + 64 am belongs to buf[g]
+    MV_HIP(mvnerf::launch_zero(amax, (size_t)kAmaxTensors * mvnerf::kBwdAmaxSlots * sizeof(float), st), who);
+    int am = 0;                                        // amax + 64 am belongs to the block's g
     auto amax_of = [&](int k) { return amax + (size_t)k * mvnerf::kBwdAmaxSlots; };
     // read-out
-    MV_TRY(launch_readout_bwd(fused_slot(6), rgbs, d_rgbs, net_keras + kKerasWr, total, n_tiles, do_tl, buf[0], st, amax_of(0)));
-    MV_TRY(launch_dw_tile(fused_slot(6), 1, do_tl, 32, n_tiles, grad + kKerasWr, 4, 4, grad + kKerasBr, kBwdMaxWGs, part, st));
-    int g = 0;                                         // buf[g] holds dL/d(block output)
+    MV_HIP(launch_readout_bwd(stash + L.fused_slot(6), rgbs, d_rgbs, net_keras + kKerasWr, total, n_tiles, do_tl, walk.grad(), st, amax_of(0)), who);
+    MV_HIP(launch_dw_tile(stash + L.fused_slot(6), 1, do_tl, 32, n_tiles, grad + kKerasWr, 4, 4, grad + kKerasBr, kBwdMaxWGs, part, st), who);
     for (int bi = 5; bi >= 0; --bi) {
-        if (bi == 2 && V > 1) {                        // reduce_mean over views (layers.py:368-370)
-            const int gn = (g + 1) % 3;
-            MV_TRY(launch_view_broadcast(buf[g], V, n_tiles / B, n_tiles, buf[gn], st));
-            g = gn;
-        }
-        const bool fused = bi >= 3;
-        const long nt = fused ? n_tiles : view_tiles;
-        const float* pre_in = fused ? fused_slot(2 * (bi - 3)) : view_slot(2 * bi);
-        const float* pre_hid = fused ? fused_slot(2 * (bi - 3) + 1) : view_slot(2 * bi + 1);
+        TrunkBwd::Block b;
+        MV_HIP(walk.block(bi, &b, st), who);
         float* gb = grad + kKerasBlocks + bi * kKerasBlockStride;
-        const int dh = (g + 1) % 3, gn = (g + 2) % 3;
         // second Dense of the block: out = x_in + W2^T relu(hid) + b2      (dX and dW in one pass over the tiles)
-        MV_TRY(launch_dense_bwd_fused(buf[g], pre_hid, bwd_streams + (size_t)(2 * bi + 1) * kHiddenWFloats, nullptr, buf[dh], nt,
-                                      gb + kHidden * kHidden + kHidden, gb + 2 * kHidden * kHidden + kHidden, kFusedBwdWGs, part, st,
-                                      amax_of(am), amax_of(am + 1)));
+        MV_HIP(launch_dense_bwd_fused(b.g, b.pre_hid, b.w2, nullptr, b.dh, b.nt, gb + kHidden * kHidden + kHidden, gb + 2 * kHidden * kHidden + kHidden,
+                                      kFusedBwdWGs, part, st, amax_of(am), amax_of(am + 1)), who);
         // first Dense: hid = W1^T relu(x_in) + b1 ; the identity branch adds dL/d(out) back
-        MV_TRY(launch_dense_bwd_fused(buf[dh], pre_in, bwd_streams + (size_t)(2 * bi) * kHiddenWFloats, buf[g], buf[gn], nt, gb,
-                                      gb + kHidden * kHidden, kFusedBwdWGs, part, st, amax_of(am + 1), amax_of(am + 2)));
+        MV_HIP(launch_dense_bwd_fused(b.dh, b.pre_in, b.w1, b.g, b.gn, b.nt, gb, gb + kHidden * kHidden, kFusedBwdWGs, part, st, amax_of(am + 1),
+                                      amax_of(am + 2)), who);
         am += 2;                                       // (the view broadcast scales by 1 / V: its output keeps its input's bound)
-        g = gn;
     }
     // layer 0 (inputs recomputed)
+    const float* g0 = walk.grad();                         // dL/d(layer-0 output)
     FieldParams p = {};
     p.rays_o = rays_o; p.rays_d = rays_d; p.z = z; p.images = images; p.features = features;
     p.k4 = intrinsics; p.einv = extrinsics_inv;
     p.B = B; p.V = V; p.R = R; p.S = S; p.H = H; p.W = W; p.total = total; p.n_tiles = n_tiles;
     p.texel_table = texel_table;                           // only the sample-position gradient uses it (launch_field_dz)
     p.net = net_keras;                                     // (Keras layout here: field_dz_table_kernel reads W0's rgb rows from it)
-    MV_TRY(launch_dw0(p, buf[g], grad + kKerasW0, grad + kKerasB0, kBwdMaxWGs, part, st, amax_of(am)));
+    MV_HIP(launch_dw0(p, g0, grad + kKerasW0, grad + kKerasB0, kBwdMaxWGs, part, st, amax_of(am)), who);
     // d_features through the texel table (texel_grad given): the samples' g0 is scattered onto the 128-channel table gradient and W0 is
     // applied once per texel afterwards; the sample-position gradient then takes the table path as well
     const bool via_table = d_features && texel_table && texel_grad;
     if (via_table) {
         const long n_texels = (long)B * V * H * W;
-        MV_TRY(mvnerf::launch_zero(texel_grad, (size_t)n_texels * 128 * sizeof(float), st));
-        MV_TRY(launch_texel_scatter(p, buf[g], texel_grad, st));
-        MV_TRY(launch_texel_grad_to_features(texel_grad, net_keras + kKerasW0 + 123 * kHidden, n_texels, d_features, st));
+        MV_HIP(mvnerf::launch_zero(texel_grad, (size_t)n_texels * 128 * sizeof(float), st), who);
+        MV_HIP(launch_texel_scatter(p, g0, texel_grad, st), who);
+        MV_HIP(launch_texel_grad_to_features(texel_grad, net_keras + kKerasW0 + 123 * kHidden, n_texels, d_features, st), who);
     }
     if (d_z || (d_features && !via_table))
-        MV_TRY(launch_field_dz(p, buf[g], bwd_streams + (size_t)12 * kHiddenWFloats, d_z, nullptr, nullptr, via_table ? nullptr : d_features, st));
-#undef MV_TRY
+        MV_HIP(launch_field_dz(p, g0, bwd_streams + (size_t)12 * kHiddenWFloats, d_z, nullptr, nullptr, via_table ? nullptr : d_features, st), who);
     return 0;
 }
 
@@ -706,8 +722,7 @@ int mvnerf_query_jvp(const float* points, const float* dirs, const float* t_poin
 
 size_t mvnerf_query_vjp_scratch_bytes(int B, int V, int N) {
     if (B <= 0 || V <= 0 || N <= 0) return 0;
-    const size_t tiles = ((size_t)B * N + 31) / 32;
-    return (size_t)3 * V * tiles * 4096 * sizeof(float);
+    return (size_t)3 * StashLayout(B, V, N).view_stride() * sizeof(float);        // the three rotating tile buffers
 }
 
 int mvnerf_query_vjp(const float* points, const float* dirs, const float* images, const float* features,
@@ -723,42 +738,26 @@ int mvnerf_query_vjp(const float* points, const float* dirs, const float* images
     if (!aligned16(features) || !aligned16(bwd_streams) || !aligned16(stash) || !aligned16(g_acts) || !aligned16(scratch))
         return fail(MVNERF_E_ALIGN, "mvnerf_query_vjp: features, bwd_streams, stash, g_acts, scratch must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const long total = (long)B * N, n_tiles = (total + 31) / 32, view_tiles = n_tiles * V;
-    const size_t vslot = (size_t)view_tiles * 4096, fslot = (size_t)n_tiles * 4096;
-    float* buf[3] = {static_cast<float*>(scratch), static_cast<float*>(scratch) + vslot, static_cast<float*>(scratch) + 2 * vslot};
-    auto view_slot = [&](int k) { return stash + (size_t)k * vslot; };
-    auto fused_slot = [&](int m) { return stash + 7 * vslot + (size_t)m * fslot; };
-    hipError_t e;
-#define MV_TRY(call) if ((e = (call)) != hipSuccess) return hip_status(e, "mvnerf_query_vjp")
-    MV_TRY(launch_zero(d_points, (size_t)total * 3 * sizeof(float), st));
-    MV_TRY(launch_zero(d_dirs, (size_t)total * 3 * sizeof(float), st));
-    // buf[g] holds dL/d(block output); the cotangents of u3, u2, u1 and the view mean enter where those tensors are produced
-    MV_TRY(launch_rows_to_tl(g_acts + (size_t)3 * total * 128, total, n_tiles, 0, buf[0], st));
-    int g = 0;
+    const char* const who = "mvnerf_query_vjp";
+    const StashLayout L(B, V, N);
+    const long total = L.total, n_tiles = L.n_tiles;
+    TrunkBwd walk = {L, B, V, stash, bwd_streams, static_cast<float*>(scratch)};
+    MV_HIP(launch_zero(d_points, (size_t)total * 3 * sizeof(float), st), who);
+    MV_HIP(launch_zero(d_dirs, (size_t)total * 3 * sizeof(float), st), who);
+    // the cotangents of u3, u2, u1 and the view mean enter where those tensors are produced
+    MV_HIP(launch_rows_to_tl(g_acts + (size_t)3 * total * 128, total, n_tiles, 0, walk.grad(), st), who);
     for (int bi = 5; bi >= 0; --bi) {
-        if (bi == 2 && V > 1) {
-            const int gn = (g + 1) % 3;
-            MV_TRY(launch_view_broadcast(buf[g], V, n_tiles / B, n_tiles, buf[gn], st));
-            g = gn;
-        }
-        const bool fused = bi >= 3;
-        const long nt = fused ? n_tiles : view_tiles;
-        const float* pre_in = fused ? fused_slot(2 * (bi - 3)) : view_slot(2 * bi);
-        const float* pre_hid = fused ? fused_slot(2 * (bi - 3) + 1) : view_slot(2 * bi + 1);
-        const int dh = (g + 1) % 3, gn = (g + 2) % 3;
-        MV_TRY(launch_dense_bwd_fused(buf[g], pre_hid, bwd_streams + (size_t)(2 * bi + 1) * kHiddenWFloats, nullptr, buf[dh], nt,
-                                      nullptr, nullptr, kFusedBwdWGs, nullptr, st));
-        MV_TRY(launch_dense_bwd_fused(buf[dh], pre_in, bwd_streams + (size_t)(2 * bi) * kHiddenWFloats, buf[g], buf[gn], nt,
-                                      nullptr, nullptr, kFusedBwdWGs, nullptr, st));
-        g = gn;
-        if (fused) MV_TRY(launch_rows_to_tl(g_acts + (size_t)(bi - 3) * total * 128, total, n_tiles, 1, buf[g], st));
+        TrunkBwd::Block b;
+        MV_HIP(walk.block(bi, &b, st), who);
+        MV_HIP(launch_dense_bwd_fused(b.g, b.pre_hid, b.w2, nullptr, b.dh, b.nt, nullptr, nullptr, kFusedBwdWGs, nullptr, st), who);
+        MV_HIP(launch_dense_bwd_fused(b.dh, b.pre_in, b.w1, b.g, b.gn, b.nt, nullptr, nullptr, kFusedBwdWGs, nullptr, st), who);
+        if (b.fused) MV_HIP(launch_rows_to_tl(g_acts + (size_t)(bi - 3) * total * 128, total, n_tiles, 1, b.gn, st), who);
     }
     FieldParams p = {};
     p.rays_o = points; p.rays_d = dirs; p.z = nullptr; p.images = images; p.features = features;
     p.k4 = intrinsics; p.einv = extrinsics_inv;
     p.B = B; p.V = V; p.R = N; p.S = 1; p.H = H; p.W = W; p.total = total; p.n_tiles = n_tiles;
-    MV_TRY(launch_field_dz(p, buf[g], bwd_streams + (size_t)12 * kHiddenWFloats, nullptr, d_points, d_dirs, nullptr, st));
-#undef MV_TRY
+    MV_HIP(launch_field_dz(p, walk.grad(), bwd_streams + (size_t)12 * kHiddenWFloats, nullptr, d_points, d_dirs, nullptr, st), who);
     return 0;
 }
 
@@ -766,10 +765,10 @@ int mvnerf_stash_fused_acts(const float* stash, int B, int V, int N, float* acts
     if (!stash || !acts) return fail(MVNERF_E_ARG, "mvnerf_stash_fused_acts: null pointer");
     if (B <= 0 || V <= 0 || N <= 0) return fail(MVNERF_E_ARG, "mvnerf_stash_fused_acts: B=%d V=%d N=%d", B, V, N);
     if (!aligned16(stash) || !aligned16(acts)) return fail(MVNERF_E_ALIGN, "mvnerf_stash_fused_acts: stash, acts must be 16-byte aligned");
-    const long total = (long)B * N, n_tiles = (total + 31) / 32;
-    const size_t vslot = (size_t)n_tiles * V * 4096, fslot = (size_t)n_tiles * 4096;
+    const StashLayout L(B, V, N);
     // fused slots 0, 2, 4, 6 = view mean, u1, u2, u3 (the odd ones are the blocks' hidden pre-activations)
-    return hip_status(mvnerf::launch_tl_to_rows(stash + 7 * vslot, (long)(2 * fslot), 4, total, n_tiles, acts, static_cast<hipStream_t>(stream)),
+    return hip_status(mvnerf::launch_tl_to_rows(stash + L.fused_slot(0), 2 * L.fused_stride(), 4, L.total, L.n_tiles, acts,
+                                                static_cast<hipStream_t>(stream)),
                       "mvnerf_stash_fused_acts");
 }
 

@@ -8,13 +8,12 @@
 // synchronisation, no global state.
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvnerf_hip.h"
-#include "mvnerf_kernels.h"
+#include "mvnerf_api.h"
 
 namespace {
 
-constexpr size_t kAlign = 256;
-size_t up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+using mvnerf::aligned16;
+using mvnerf::aligned4;
 
 struct GraspWs {
     float *points, *dirs, *z, *rgbs, *acts, *c, *y, *tail_stash, *g_x, *g_acts, *d_points, *d_dirs;
@@ -26,31 +25,26 @@ struct GraspWs {
 
 GraspWs carve_grasp(void* base, int B, int V, int P, int n5) {
     GraspWs w;
-    char* p = static_cast<char*>(base);
-    auto take = [&](size_t bytes) {
-        char* q = p;
-        p += up(bytes);
-        return q;
-    };
+    mvnerf::Bump ws(base);
     w.n = (long)P * n5;
-    w.ld = V > 1 ? (w.n + 31) / 32 * 32 : w.n;
+    w.ld = mvnerf::pose_rows_ld(V, w.n);
     const size_t rows = (size_t)B * w.ld;
-    w.points = reinterpret_cast<float*>(take(rows * 3 * 4));
-    w.dirs = reinterpret_cast<float*>(take(rows * 3 * 4));
-    w.z = reinterpret_cast<float*>(take(rows * 4));
-    w.rgbs = reinterpret_cast<float*>(take(rows * 4 * 4));
-    w.field_ws = take(mvnerf_field_workspace_bytes(B, V, (int)w.ld));
-    w.stash = reinterpret_cast<float*>(take(mvnerf_stash_bytes(B, V, (int)w.ld, 1)));
-    w.acts = reinterpret_cast<float*>(take(rows * 4 * 128 * 4));
-    w.c = reinterpret_cast<float*>(take(rows * 256 * 4));
-    w.y = reinterpret_cast<float*>(take(rows * 64 * 4));
-    w.tail_stash = reinterpret_cast<float*>(take((size_t)B * P * mvnerf::grasp_tail_stash_floats() * 4));
-    w.g_x = reinterpret_cast<float*>(take(rows * 64 * 4));
-    w.g_acts = reinterpret_cast<float*>(take(rows * 4 * 128 * 4));
-    w.vjp_scratch = take(mvnerf_query_vjp_scratch_bytes(B, V, (int)w.ld));
-    w.d_points = reinterpret_cast<float*>(take(rows * 3 * 4));
-    w.d_dirs = reinterpret_cast<float*>(take(rows * 3 * 4));
-    w.bytes = (size_t)(p - static_cast<char*>(base));
+    w.points = ws.floats(rows * 3);
+    w.dirs = ws.floats(rows * 3);
+    w.z = ws.floats(rows);
+    w.rgbs = ws.floats(rows * 4);
+    w.field_ws = ws.take(mvnerf_field_workspace_bytes(B, V, (int)w.ld));
+    w.stash = static_cast<float*>(ws.take(mvnerf_stash_bytes(B, V, (int)w.ld, 1)));
+    w.acts = ws.floats(rows * 4 * 128);
+    w.c = ws.floats(rows * 256);
+    w.y = ws.floats(rows * 64);
+    w.tail_stash = ws.floats((size_t)B * P * mvnerf::grasp_tail_stash_floats());
+    w.g_x = ws.floats(rows * 64);
+    w.g_acts = ws.floats(rows * 4 * 128);
+    w.vjp_scratch = ws.take(mvnerf_query_vjp_scratch_bytes(B, V, (int)w.ld));
+    w.d_points = ws.floats(rows * 3);
+    w.d_dirs = ws.floats(rows * 3);
+    w.bytes = ws.bytes();
     return w;
 }
 
@@ -68,20 +62,6 @@ __global__ void pad_rows_kernel(float* __restrict__ points, float* __restrict__ 
     dirs[(b * ld + n + r) * 3 + k] = dirs[(b * ld + n - 1) * 3 + k];
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
-#define MV_RC(x)                  \
-    do {                          \
-        int rc_ = (x);            \
-        if (rc_ != 0) return rc_; \
-    } while (0)
-#define MV_HIP(x, who)                                                                                    \
-    do {                                                                                                  \
-        hipError_t e_ = (x);                                                                              \
-        if (e_ != hipSuccess) return mvnerf::api_fail((int)e_, "%s: %s", who, hipGetErrorString(e_));     \
-    } while (0)
-
 int validate(const mvnerf_grasp_call* c, bool want_grads, const char* who, GraspWs* out) {
     using mvnerf::api_fail;
     if (!c) return api_fail(MVNERF_E_ARG, "%s: null call", who);
@@ -92,12 +72,13 @@ int validate(const mvnerf_grasp_call* c, bool want_grads, const char* who, Grasp
     if (!sizes_ok(c->B, c->V, c->P, c->n5) || c->H < 2 || c->W < 2)
         return api_fail(MVNERF_E_ARG, "%s: B=%d V=%d H=%d W=%d P=%d n5=%d", who, c->B, c->V, c->H, c->W, c->P, c->n5);
     if (c->rep != 0 && c->rep != 1) return api_fail(MVNERF_E_SHAPE, "%s: rep=%d (0 quaternion, 1 6d)", who, c->rep);
-    if (!al16(c->features) || !al16(c->packed_net) || !al16(c->split) || !al16(c->bwd_streams) || !al16(c->head_packed) || !al16(c->tail_packed))
+    if (!aligned16(c->features) || !aligned16(c->packed_net) || !aligned16(c->split) || !aligned16(c->bwd_streams) ||
+        !aligned16(c->head_packed) || !aligned16(c->tail_packed))
         return api_fail(MVNERF_E_ALIGN, "%s: features, packed_net, split, bwd_streams, head_packed, tail_packed must be 16-byte aligned", who);
-    if (!al4(c->images) || !al4(c->intrinsics) || !al4(c->extrinsics_inv) || !al4(c->head_b4) || !al4(c->head_bc) || !al4(c->offsets) ||
-        !al4(c->t) || !al4(c->rot) || !al4(c->success) || !al4(c->g_t) || !al4(c->g_rot))
+    if (!aligned4(c->images) || !aligned4(c->intrinsics) || !aligned4(c->extrinsics_inv) || !aligned4(c->head_b4) || !aligned4(c->head_bc) ||
+        !aligned4(c->offsets) || !aligned4(c->t) || !aligned4(c->rot) || !aligned4(c->success) || !aligned4(c->g_t) || !aligned4(c->g_rot))
         return api_fail(MVNERF_E_ALIGN, "%s: float buffers must be 4-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(c->workspace) & 255u) != 0) return api_fail(MVNERF_E_ALIGN, "%s: workspace must be 256-byte aligned", who);
+    if (!mvnerf::aligned256(c->workspace)) return api_fail(MVNERF_E_ALIGN, "%s: workspace must be 256-byte aligned", who);
     *out = carve_grasp(c->workspace, c->B, c->V, c->P, c->n5);
     if (c->workspace_bytes < out->bytes)
         return api_fail(MVNERF_E_ARG, "%s: workspace %zu bytes, need %zu (mvnerf_grasp_workspace_bytes)", who, c->workspace_bytes, out->bytes);
@@ -115,16 +96,11 @@ int run(const mvnerf_grasp_call* c, bool want_grads, const char* who, mvnerf_str
     const size_t tail_stash = mvnerf::grasp_tail_stash_floats();
     // 1. poses -> query points
     MV_RC(mvnerf_pose_query_points(c->t, c->rot, c->rep, c->offsets, P, n5, B, w.ld, w.points, w.dirs, stream));
-    if (padded) {
-        const long n_pad = (long)B * (w.ld - w.n) * 3;
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, w.points, w.dirs, B, w.n, w.ld);
-        MV_HIP(hipGetLastError(), who);
-    }
+    MV_RC(mvnerf::pad_pose_rows(who, w.points, w.dirs, B, w.n, w.ld, st));
     // 2. the frozen trunk, pre-activations kept; its four fused activations as rows
     MV_HIP(mvnerf::launch_zero(w.z, (size_t)rows * 4, st), who);
-    MV_RC(mvnerf_field_eval_stash_split(w.points, w.dirs, w.z, c->images, c->features, nullptr, c->intrinsics, c->extrinsics_inv, c->packed_net,
-                                        c->split, B, V, ld, 1, c->H, c->W, w.rgbs, w.stash, w.field_ws, stream));
-    MV_RC(mvnerf_stash_fused_acts(w.stash, B, V, ld, w.acts, stream));
+    MV_RC(mvnerf::pose_rows_trunk(w.points, w.dirs, w.z, c->images, c->features, c->intrinsics, c->extrinsics_inv, c->packed_net, c->split, B, V,
+                                  w.ld, c->H, c->W, w.rgbs, w.stash, w.field_ws, w.acts, stream));
     // 3. the per-point read-out (pad rows included: they are whole rows of the same tensors)
     MV_RC(mvnerf_grasp_head_fwd(w.acts, c->head_packed, c->head_b4, c->head_bc, rows, w.c, w.y, stream));
     // 4. the per-pose read-out: a scene's P rows of n5 * 64 lie side by side in y; padded scenes are ld * 64 floats apart
@@ -149,6 +125,13 @@ int run(const mvnerf_grasp_call* c, bool want_grads, const char* who, mvnerf_str
 }
 
 }  // namespace
+
+int mvnerf::pad_pose_rows(const char* who, float* points, float* dirs, int B, long n, long ld, hipStream_t st) {
+    if (ld == n) return 0;
+    const long n_pad = (long)B * (ld - n) * 3;
+    hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, points, dirs, B, n, ld);
+    return hip_status(hipGetLastError(), who);
+}
 
 extern "C" {
 

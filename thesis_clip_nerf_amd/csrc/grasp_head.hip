@@ -17,9 +17,8 @@
 // 1.5 GFLOP): the point is launch count and HBM round trips, not the matrix rate.
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvnerf_hip.h"
+#include "mvnerf_api.h"
 #include "mvnerf_blocks.h"
-#include "mvnerf_kernels.h"
 #include "mvnerf_mfma.h"
 
 namespace mvnerf {
@@ -273,41 +272,41 @@ hipError_t launch_grasp_head_vjp_bwd(const float* t_acts, const float* g_y, cons
 // ---- C ABI ----------------------------------------------------------------------------------------------------------------------------------
 extern "C" {
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static int hs(hipError_t e, const char* who) { return e == hipSuccess ? 0 : mvnerf::api_fail((int)e, "%s: %s", who, hipGetErrorString(e)); }
+using mvnerf::aligned16;
+using mvnerf::hip_status;
 
 size_t mvnerf_grasp_head_packed_floats(void) { return mvnerf::grasp_head_packed_floats(); }
 
 int mvnerf_grasp_head_pack(const float* w4, const float* wc, float* packed, mvnerf_stream_t stream) {
     if (!w4 || !wc || !packed) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_pack: null pointer");
-    if (!al16(packed)) return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_head_pack: packed must be 16-byte aligned");
-    return hs(mvnerf::launch_grasp_head_pack(w4, wc, packed, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_pack");
+    if (!aligned16(packed)) return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_head_pack: packed must be 16-byte aligned");
+    return hip_status(mvnerf::launch_grasp_head_pack(w4, wc, packed, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_pack");
 }
 
 int mvnerf_grasp_head_fwd(const float* acts, const float* packed, const float* b4, const float* bc, long N, float* c, float* y,
                           mvnerf_stream_t stream) {
     if (!acts || !packed || !b4 || !bc || !c || !y) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_fwd: null pointer");
     if (N <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_fwd: N=%ld", N);
-    if (!al16(acts) || !al16(packed) || !al16(c) || !al16(y))
+    if (!aligned16(acts) || !aligned16(packed) || !aligned16(c) || !aligned16(y))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_head_fwd: acts, packed, c, y must be 16-byte aligned");
-    return hs(mvnerf::launch_grasp_head_fwd(acts, packed, b4, bc, N, c, y, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_fwd");
+    return hip_status(mvnerf::launch_grasp_head_fwd(acts, packed, b4, bc, N, c, y, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_fwd");
 }
 
 int mvnerf_grasp_head_vjp(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_v, float* q, float* g_u,
                           float* g_acts, mvnerf_stream_t stream) {
     if (!g_y || !c || !y || !packed || !g_v || !q || !g_u || !g_acts) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_vjp: null pointer");
     if (N <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_vjp: N=%ld", N);
-    if (!al16(g_y) || !al16(c) || !al16(y) || !al16(packed) || !al16(g_v) || !al16(q) || !al16(g_u) || !al16(g_acts))
+    if (!aligned16(g_y) || !aligned16(c) || !aligned16(y) || !aligned16(packed) || !aligned16(g_v) || !aligned16(q) || !aligned16(g_u) || !aligned16(g_acts))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_head_vjp: every buffer must be 16-byte aligned");
-    return hs(mvnerf::launch_grasp_head_vjp(g_y, c, y, packed, N, g_v, q, g_u, g_acts, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_vjp");
+    return hip_status(mvnerf::launch_grasp_head_vjp(g_y, c, y, packed, N, g_v, q, g_u, g_acts, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_vjp");
 }
 
 int mvnerf_grasp_head_vjp_acts(const float* g_y, const float* c, const float* y, const float* packed, long N, float* g_acts, mvnerf_stream_t stream) {
     if (!g_y || !c || !y || !packed || !g_acts) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_vjp_acts: null pointer");
     if (N <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_vjp_acts: N=%ld", N);
-    if (!al16(g_y) || !al16(c) || !al16(y) || !al16(packed) || !al16(g_acts))
+    if (!aligned16(g_y) || !aligned16(c) || !aligned16(y) || !aligned16(packed) || !aligned16(g_acts))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_head_vjp_acts: every buffer must be 16-byte aligned");
-    return hs(mvnerf::launch_grasp_head_vjp_acts(g_y, c, y, packed, N, g_acts, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_vjp_acts");
+    return hip_status(mvnerf::launch_grasp_head_vjp_acts(g_y, c, y, packed, N, g_acts, static_cast<hipStream_t>(stream)), "mvnerf_grasp_head_vjp_acts");
 }
 
 int mvnerf_grasp_head_vjp_bwd(const float* t_acts, const float* g_y, const float* c, const float* y, const float* q, const float* packed, long N,
@@ -315,9 +314,10 @@ int mvnerf_grasp_head_vjp_bwd(const float* t_acts, const float* g_y, const float
     if (!t_acts || !g_y || !c || !y || !q || !packed || !out_gy || !r || !m || !p)
         return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_vjp_bwd: null pointer");
     if (N <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_head_vjp_bwd: N=%ld", N);
-    if (!al16(t_acts) || !al16(g_y) || !al16(c) || !al16(y) || !al16(q) || !al16(packed) || !al16(out_gy) || !al16(r) || !al16(m) || !al16(p))
+    if (!aligned16(t_acts) || !aligned16(g_y) || !aligned16(c) || !aligned16(y) || !aligned16(q) || !aligned16(packed) || !aligned16(out_gy) ||
+        !aligned16(r) || !aligned16(m) || !aligned16(p))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_head_vjp_bwd: every buffer must be 16-byte aligned");
-    return hs(mvnerf::launch_grasp_head_vjp_bwd(t_acts, g_y, c, y, q, packed, N, out_gy, r, m, p, static_cast<hipStream_t>(stream)),
+    return hip_status(mvnerf::launch_grasp_head_vjp_bwd(t_acts, g_y, c, y, q, packed, N, out_gy, r, m, p, static_cast<hipStream_t>(stream)),
               "mvnerf_grasp_head_vjp_bwd");
 }
 

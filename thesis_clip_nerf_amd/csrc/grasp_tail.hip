@@ -20,9 +20,8 @@
 // blockIdx.y.  fp32 throughout (the fp32 MFMA multiplies exactly).
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvnerf_hip.h"
+#include "mvnerf_api.h"
 #include "mvnerf_blocks.h"
-#include "mvnerf_kernels.h"
 #include "mvnerf_mfma.h"
 #include "mvnerf_tail.h"
 
@@ -359,9 +358,9 @@ hipError_t launch_grasp_tail_vjp(const float* x, const float* g_s, const float* 
 // ---- C ABI ----------------------------------------------------------------------------------------------------------------------------------
 extern "C" {
 
-static bool tail_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static bool tail_al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-static int tail_hs(hipError_t e, const char* who) { return e == hipSuccess ? 0 : mvnerf::api_fail((int)e, "%s: %s", who, hipGetErrorString(e)); }
+using mvnerf::aligned16;
+using mvnerf::aligned4;
+using mvnerf::hip_status;
 constexpr long kTailMaxRows = 1L << 24;             // row * K stays far inside 63 bits, K itself inside an int
 
 size_t mvnerf_grasp_tail_packed_floats(int n5) { return n5 > 0 && n5 <= 4096 ? mvnerf::grasp_tail_packed_floats(n5) : 0; }
@@ -372,26 +371,26 @@ int mvnerf_grasp_tail_pack(const float* w0, const float* b0, const float* w1, co
     if (!w0 || !b0 || !w1 || !b1 || !ws || !w0b || !b0b || !w1b || !b1b || !w_out || !packed)
         return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_pack: null pointer (only b_out may be NULL)");
     if (n5 <= 0 || n5 > 4096) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_pack: n5=%d", n5);
-    if (!tail_al16(packed)) return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_tail_pack: packed must be 16-byte aligned");
+    if (!aligned16(packed)) return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_tail_pack: packed must be 16-byte aligned");
     const float* w[11] = {w0, b0, w1, b1, ws, w0b, b0b, w1b, b1b, w_out, b_out};
-    return tail_hs(mvnerf::launch_grasp_tail_pack(w, n5, packed, static_cast<hipStream_t>(stream)), "mvnerf_grasp_tail_pack");
+    return hip_status(mvnerf::launch_grasp_tail_pack(w, n5, packed, static_cast<hipStream_t>(stream)), "mvnerf_grasp_tail_pack");
 }
 
 int mvnerf_grasp_tail_fwd(const float* x, const float* packed, long M, int n5, float* success, float* stash, mvnerf_stream_t stream) {
     if (!x || !packed || !success) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_fwd: null pointer (only stash may be NULL)");
     if (M <= 0 || M > kTailMaxRows || n5 <= 0 || n5 > 4096) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_fwd: M=%ld n5=%d", M, n5);
-    if (!tail_al16(x) || !tail_al16(packed) || !tail_al16(stash) || !tail_al4(success))
+    if (!aligned16(x) || !aligned16(packed) || !aligned16(stash) || !aligned4(success))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_tail_fwd: x, packed, stash must be 16-byte aligned (success: 4)");
-    return tail_hs(mvnerf::launch_grasp_tail_fwd(x, packed, M, n5, success, stash, static_cast<hipStream_t>(stream)), "mvnerf_grasp_tail_fwd");
+    return hip_status(mvnerf::launch_grasp_tail_fwd(x, packed, M, n5, success, stash, static_cast<hipStream_t>(stream)), "mvnerf_grasp_tail_fwd");
 }
 
 int mvnerf_grasp_tail_vjp(const float* x, const float* g_s, const float* stash, const float* packed, long M, int n5, float* g_x,
                           mvnerf_stream_t stream) {
     if (!x || !stash || !packed || !g_x) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_vjp: null pointer (only g_s may be NULL)");
     if (M <= 0 || M > kTailMaxRows || n5 <= 0 || n5 > 4096) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_vjp: M=%ld n5=%d", M, n5);
-    if (!tail_al16(x) || !tail_al16(stash) || !tail_al16(packed) || !tail_al16(g_x) || !tail_al4(g_s))
+    if (!aligned16(x) || !aligned16(stash) || !aligned16(packed) || !aligned16(g_x) || !aligned4(g_s))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_tail_vjp: x, stash, packed, g_x must be 16-byte aligned (g_s: 4)");
-    return tail_hs(mvnerf::launch_grasp_tail_vjp(x, g_s, stash, packed, M, n5, g_x, static_cast<hipStream_t>(stream)), "mvnerf_grasp_tail_vjp");
+    return hip_status(mvnerf::launch_grasp_tail_vjp(x, g_s, stash, packed, M, n5, g_x, static_cast<hipStream_t>(stream)), "mvnerf_grasp_tail_vjp");
 }
 
 }  // extern "C"

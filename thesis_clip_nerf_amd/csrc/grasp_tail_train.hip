@@ -18,9 +18,8 @@
 // No sums cross workgroups; rows past M are clamped to row M - 1 on reads and never stored.  fp32 on v_mfma_f32_32x32x2_f32.
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvnerf_hip.h"
+#include "mvnerf_api.h"
 #include "mvnerf_blocks.h"
-#include "mvnerf_kernels.h"
 #include "mvnerf_mfma.h"
 #include "mvnerf_tail.h"
 
@@ -496,9 +495,9 @@ hipError_t launch_grasp_tail_vjp_bwd(const float* x, const float* t_x, const flo
 // ---- C ABI ----------------------------------------------------------------------------------------------------------------------------------
 extern "C" {
 
-static bool train_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static bool train_al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-static int train_hs(hipError_t e, const char* who) { return e == hipSuccess ? 0 : mvnerf::api_fail((int)e, "%s: %s", who, hipGetErrorString(e)); }
+using mvnerf::aligned16;
+using mvnerf::aligned4;
+using mvnerf::hip_status;
 constexpr long kTrainMaxRows = 1L << 24;            // row * K stays far inside 63 bits, K itself inside an int
 
 int mvnerf_grasp_tail_vjp_train(const float* x, const float* g_s, const float* stash, const float* packed, long M, int n5, float* g_x, float* cot,
@@ -506,10 +505,10 @@ int mvnerf_grasp_tail_vjp_train(const float* x, const float* g_s, const float* s
     if (!x || !stash || !packed || !g_x || !cot || !act || !ex)
         return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_vjp_train: null pointer (only g_s may be NULL)");
     if (M <= 0 || M > kTrainMaxRows || n5 <= 0 || n5 > 4096) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_vjp_train: M=%ld n5=%d", M, n5);
-    if (!train_al16(x) || !train_al16(stash) || !train_al16(packed) || !train_al16(g_x) || !train_al16(cot) || !train_al16(act) || !train_al16(ex) ||
-        !train_al4(g_s))
+    if (!aligned16(x) || !aligned16(stash) || !aligned16(packed) || !aligned16(g_x) || !aligned16(cot) || !aligned16(act) || !aligned16(ex) ||
+        !aligned4(g_s))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_grasp_tail_vjp_train: x, stash, packed, g_x, cot, act, ex must be 16-byte aligned (g_s: 4)");
-    return train_hs(mvnerf::launch_grasp_tail_vjp_train(x, g_s, stash, packed, M, n5, g_x, cot, act, ex, static_cast<hipStream_t>(stream)),
+    return hip_status(mvnerf::launch_grasp_tail_vjp_train(x, g_s, stash, packed, M, n5, g_x, cot, act, ex, static_cast<hipStream_t>(stream)),
                     "mvnerf_grasp_tail_vjp_train");
 }
 
@@ -518,11 +517,11 @@ int mvnerf_grasp_tail_vjp_bwd(const float* x, const float* t_x, const float* g_s
     if (!x || !t_x || !stash || !cot || !packed || !out_gs || !cot2 || !tan || !dex)
         return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_vjp_bwd: null pointer (only g_s and out_x may be NULL)");
     if (M <= 0 || M > kTrainMaxRows || n5 <= 0 || n5 > 4096) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_grasp_tail_vjp_bwd: M=%ld n5=%d", M, n5);
-    if (!train_al16(x) || !train_al16(t_x) || !train_al16(stash) || !train_al16(cot) || !train_al16(packed) || !train_al16(out_x) ||
-        !train_al16(cot2) || !train_al16(tan) || !train_al16(dex) || !train_al4(g_s) || !train_al4(out_gs))
+    if (!aligned16(x) || !aligned16(t_x) || !aligned16(stash) || !aligned16(cot) || !aligned16(packed) || !aligned16(out_x) ||
+        !aligned16(cot2) || !aligned16(tan) || !aligned16(dex) || !aligned4(g_s) || !aligned4(out_gs))
         return mvnerf::api_fail(MVNERF_E_ALIGN,
                                 "mvnerf_grasp_tail_vjp_bwd: x, t_x, stash, cot, packed, out_x, cot2, tan, dex must be 16-byte aligned (g_s, out_gs: 4)");
-    return train_hs(mvnerf::launch_grasp_tail_vjp_bwd(x, t_x, g_s, stash, cot, packed, M, n5, out_gs, out_x, cot2, tan, dex,
+    return hip_status(mvnerf::launch_grasp_tail_vjp_bwd(x, t_x, g_s, stash, cot, packed, M, n5, out_gs, out_x, cot2, tan, dex,
                                                       static_cast<hipStream_t>(stream)),
                     "mvnerf_grasp_tail_vjp_bwd");
 }

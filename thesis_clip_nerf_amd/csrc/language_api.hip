@@ -19,13 +19,12 @@
 // synchronisation, no global state, no atomics of its own (mvnerf_query_vjp's view sum for V > 1 is the one unordered sum of the step).
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvnerf_hip.h"
-#include "mvnerf_kernels.h"
+#include "mvnerf_api.h"
 
 namespace {
 
-constexpr size_t kAlign = 256;
-size_t up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+using mvnerf::aligned16;
+using mvnerf::aligned4;
 
 constexpr long kHeadGrad = 4 * 64 * 128 + 4 * 64 + 64 * 256 + 64;          // floats of d_w4, d_b4, d_wc, d_bc
 
@@ -64,19 +63,9 @@ size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 LangWs carve(void* base, int B, int V, int np, int n5) {
     LangWs w;
-    char* ptr = static_cast<char*>(base);
-    auto take = [&](size_t floats) {
-        char* q = ptr;
-        ptr += up(floats * 4);
-        return reinterpret_cast<float*>(q);
-    };
-    auto take_bytes = [&](size_t bytes) {
-        char* q = ptr;
-        ptr += up(bytes);
-        return static_cast<void*>(q);
-    };
+    mvnerf::Bump ws(base);
     w.n = (long)np * n5;
-    w.ld = V > 1 ? (w.n + 31) / 32 * 32 : w.n;
+    w.ld = mvnerf::pose_rows_ld(V, w.n);
     w.N = (long)B * w.n;
     w.M = (long)B * np;
     w.M8 = (w.M + 7) / 8 * 8;
@@ -84,28 +73,28 @@ LangWs carve(void* base, int B, int V, int np, int n5) {
     const bool padded = w.ld > w.n;
     const size_t rows = (size_t)B * w.ld, N = (size_t)w.N, NR = (size_t)w.NR, M8 = (size_t)w.M8, slack = (NR - N) * 128;
     const int K = 64 * n5, ld = (int)w.ld;
-    w.points = take(rows * 3); w.dirs = take(rows * 3); w.z = take(rows); w.rgbs = take(rows * 4);
-    w.d_points = take(rows * 3); w.d_dirs = take(rows * 3); w.t_points = take(rows * 3); w.t_dirs = take(rows * 3);
-    w.field_ws = take_bytes(mvnerf_field_workspace_bytes(B, V, ld));
-    w.stash = static_cast<float*>(take_bytes(mvnerf_stash_bytes(B, V, ld, 1)));
-    w.vjp_scratch = take_bytes(mvnerf_query_vjp_scratch_bytes(B, V, ld));
-    w.jvp_ws = take_bytes(mvnerf_query_workspace_bytes(B, V, ld));
-    w.acts = take(4 * N * 128 + slack); w.t_acts = take(4 * N * 128 + slack); w.g_acts = take(4 * N * 128);
+    w.points = ws.floats(rows * 3); w.dirs = ws.floats(rows * 3); w.z = ws.floats(rows); w.rgbs = ws.floats(rows * 4);
+    w.d_points = ws.floats(rows * 3); w.d_dirs = ws.floats(rows * 3); w.t_points = ws.floats(rows * 3); w.t_dirs = ws.floats(rows * 3);
+    w.field_ws = ws.take(mvnerf_field_workspace_bytes(B, V, ld));
+    w.stash = static_cast<float*>(ws.take(mvnerf_stash_bytes(B, V, ld, 1)));
+    w.vjp_scratch = ws.take(mvnerf_query_vjp_scratch_bytes(B, V, ld));
+    w.jvp_ws = ws.take(mvnerf_query_workspace_bytes(B, V, ld));
+    w.acts = ws.floats(4 * N * 128 + slack); w.t_acts = ws.floats(4 * N * 128 + slack); w.g_acts = ws.floats(4 * N * 128);
     if (padded) {
-        w.acts_p = take(4 * rows * 128); w.g_acts_p = take(4 * rows * 128); w.t_acts_p = take(4 * rows * 128);
+        w.acts_p = ws.floats(4 * rows * 128); w.g_acts_p = ws.floats(4 * rows * 128); w.t_acts_p = ws.floats(4 * rows * 128);
     } else {
         w.acts_p = w.acts; w.g_acts_p = w.g_acts; w.t_acts_p = w.t_acts;
     }
-    w.c = take(NR * 256); w.y = take(NR * 64); w.g_v = take(NR * 64); w.q = take(NR * 256); w.g_u = take(NR * 256);
-    w.r = take(NR * 256); w.m = take(NR * 64); w.p = take(NR * 256); w.out_gy = take(NR * 64);
-    w.g_x = take(NR * 64); w.ex = take(NR * 64); w.out_x = take(NR * 64); w.dex = take(NR * 64);
-    w.tail_stash = take(M8 * mvnerf::grasp_tail_stash_floats()); w.g_s = take(M8); w.out_gs = take(M8);
-    w.cot = take(M8 * 320); w.act = take(M8 * 320); w.cot2 = take(M8 * 256); w.tan = take(M8 * 320);
-    w.grads_t = take(M8 * 3); w.grads_r = take(M8 * 6); w.c_t = take(M8 * 3); w.c_r = take(M8 * 6);
-    w.head_packed = take(mvnerf_grasp_head_packed_floats());
-    w.tail_packed = take(mvnerf_grasp_tail_packed_floats(n5));
+    w.c = ws.floats(NR * 256); w.y = ws.floats(NR * 64); w.g_v = ws.floats(NR * 64); w.q = ws.floats(NR * 256); w.g_u = ws.floats(NR * 256);
+    w.r = ws.floats(NR * 256); w.m = ws.floats(NR * 64); w.p = ws.floats(NR * 256); w.out_gy = ws.floats(NR * 64);
+    w.g_x = ws.floats(NR * 64); w.ex = ws.floats(NR * 64); w.out_x = ws.floats(NR * 64); w.dex = ws.floats(NR * 64);
+    w.tail_stash = ws.floats(M8 * mvnerf::grasp_tail_stash_floats()); w.g_s = ws.floats(M8); w.out_gs = ws.floats(M8);
+    w.cot = ws.floats(M8 * 320); w.act = ws.floats(M8 * 320); w.cot2 = ws.floats(M8 * 256); w.tan = ws.floats(M8 * 320);
+    w.grads_t = ws.floats(M8 * 3); w.grads_r = ws.floats(M8 * 6); w.c_t = ws.floats(M8 * 3); w.c_r = ws.floats(M8 * 6);
+    w.head_packed = ws.floats(mvnerf_grasp_head_packed_floats());
+    w.tail_packed = ws.floats(mvnerf_grasp_tail_packed_floats(n5));
     const size_t G = (size_t)grad_layout(n5).total;
-    w.g1 = take(G); w.g2 = take(G); w.g3 = take((size_t)kHeadGrad);
+    w.g1 = ws.floats(G); w.g2 = ws.floats(G); w.g3 = ws.floats((size_t)kHeadGrad);
     size_t sc = 0;
     sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)NR, 64, 128, 4, 1));
     sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)NR, 64, 256, 1, 1));
@@ -113,8 +102,8 @@ LangWs carve(void* base, int B, int V, int np, int n5) {
     sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)M8, 64, K, 1, 1));
     sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)M8, 64, 128, 1, 1));
     sc = max_sz(sc, mvnerf_gemm_tn_batched_scratch_bytes((int)M8, 64, 64, 2, 1));
-    w.gemm_scratch = take_bytes(sc + 16);
-    w.bytes = (size_t)(ptr - static_cast<char*>(base));
+    w.gemm_scratch = ws.take(sc + 16);
+    w.bytes = ws.bytes();
     return w;
 }
 
@@ -134,16 +123,6 @@ __global__ void zero_list_kernel(ZeroList z) {
     float* p = z.ptr[blockIdx.y];
     const long n = z.count[blockIdx.y];
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = 0.0f;
-}
-
-// rows n .. ld of every scene repeat row n - 1 (whole tiles for the multi-view kernels; as mvnerf_grasp_opt_step)
-__global__ void pad_rows_kernel(float* __restrict__ points, float* __restrict__ dirs, int B, long n, long ld) {
-    const long pad = ld - n, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)B * pad * 3) return;
-    const long b = idx / (pad * 3), r = (idx / 3) % pad;
-    const int k = (int)(idx % 3);
-    points[(b * ld + n + r) * 3 + k] = points[(b * ld + n - 1) * 3 + k];
-    dirs[(b * ld + n + r) * 3 + k] = dirs[(b * ld + n - 1) * 3 + k];
 }
 
 // (groups, src_ld, 128) -> (groups, dst_ld, 128): rows below `n` copied, rows n .. dst_ld zero.  Compacts the trunk's padded rows
@@ -200,20 +179,6 @@ __global__ void sum_grads_kernel(const float* __restrict__ g1, const float* __re
     out[i] = i < n_head ? s + g3[i] : s;
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
-#define MV_RC(x)                  \
-    do {                          \
-        int rc_ = (x);            \
-        if (rc_ != 0) return rc_; \
-    } while (0)
-#define MV_HIP(x, who)                                                                                    \
-    do {                                                                                                  \
-        hipError_t e_ = (x);                                                                              \
-        if (e_ != hipSuccess) return mvnerf::api_fail((int)e_, "%s: %s", who, hipGetErrorString(e_));     \
-    } while (0)
-
 const char* const kWho = "mvnerf_language_loss_and_grads";
 
 int validate(const mvnerf_language_call* c, LangWs* out) {
@@ -231,15 +196,16 @@ int validate(const mvnerf_language_call* c, LangWs* out) {
     if (c->rep != 0 && c->rep != 1) return api_fail(MVNERF_E_SHAPE, "%s: rep=%d (0 quaternion, 1 6d)", who, c->rep);
     if (c->loss_kind != MVNERF_LOSS_KL_DIVERGENCE && c->loss_kind != MVNERF_LOSS_CROSS_ENTROPY)
         return api_fail(MVNERF_E_SHAPE, "%s: loss_kind=%d (0 kl_divergence, 1 cross_entropy)", who, c->loss_kind);
-    if (!al16(c->features) || !al16(c->packed_net) || !al16(c->split) || !al16(c->bwd_streams) || !al16(c->grads))
+    if (!aligned16(c->features) || !aligned16(c->packed_net) || !aligned16(c->split) || !aligned16(c->bwd_streams) || !aligned16(c->grads))
         return api_fail(MVNERF_E_ALIGN, "%s: features, packed_net, split, bwd_streams, grads must be 16-byte aligned", who);
     for (int i = 0; i < 11; ++i)
-        if (!al4(c->tail_w[i])) return api_fail(MVNERF_E_ALIGN, "%s: tail_w[%d] must be 4-byte aligned", who, i);
-    if (!al4(c->images) || !al4(c->intrinsics) || !al4(c->extrinsics_inv) || !al4(c->head_w4) || !al4(c->head_wc) || !al4(c->head_b4) || !al4(c->head_bc) || !al4(c->offsets) ||
-        !al4(c->t_landscape) || !al4(c->rot_landscape) || !al4(c->t_grad) || !al4(c->rot_grad) || !al4(c->label_landscape) ||
-        !al4(c->label_grad_t) || !al4(c->label_grad_r) || !al4(c->prediction) || !al4(c->scalars))
+        if (!aligned4(c->tail_w[i])) return api_fail(MVNERF_E_ALIGN, "%s: tail_w[%d] must be 4-byte aligned", who, i);
+    if (!aligned4(c->images) || !aligned4(c->intrinsics) || !aligned4(c->extrinsics_inv) || !aligned4(c->head_w4) || !aligned4(c->head_wc) ||
+        !aligned4(c->head_b4) || !aligned4(c->head_bc) || !aligned4(c->offsets) ||
+        !aligned4(c->t_landscape) || !aligned4(c->rot_landscape) || !aligned4(c->t_grad) || !aligned4(c->rot_grad) || !aligned4(c->label_landscape) ||
+        !aligned4(c->label_grad_t) || !aligned4(c->label_grad_r) || !aligned4(c->prediction) || !aligned4(c->scalars))
         return api_fail(MVNERF_E_ALIGN, "%s: float buffers must be 4-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(c->workspace) & 255u) != 0) return api_fail(MVNERF_E_ALIGN, "%s: workspace must be 256-byte aligned", who);
+    if (!mvnerf::aligned256(c->workspace)) return api_fail(MVNERF_E_ALIGN, "%s: workspace must be 256-byte aligned", who);
     *out = carve(c->workspace, c->B, c->V, c->np, c->n5);
     if (c->workspace_bytes < out->bytes)
         return api_fail(MVNERF_E_ARG, "%s: workspace %zu bytes, need %zu (mvnerf_language_workspace_bytes)", who, c->workspace_bytes, out->bytes);
@@ -279,10 +245,7 @@ struct Step {
         for (int b = 0; b < c->B; ++b)
             MV_RC(mvnerf_pose_query_points(t + (size_t)b * c->np * 3, rot + (size_t)b * c->np * rd, c->rep, c->offsets, c->np, c->n5, 1, w.ld,
                                            w.points + (size_t)b * w.ld * 3, w.dirs + (size_t)b * w.ld * 3, stream));
-        const long n_pad = (long)c->B * (w.ld - w.n) * 3;
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, st, w.points, w.dirs, c->B, w.n, w.ld);
-        MV_HIP(hipGetLastError(), kWho);
-        return 0;
+        return mvnerf::pad_pose_rows(kWho, w.points, w.dirs, c->B, w.n, w.ld, st);
     }
 
     int copy_rows(const float* src, float* dst, long src_ld, long dst_ld) {
@@ -296,9 +259,8 @@ struct Step {
     // points -> trunk (pre-activations kept) -> fused activations -> head -> tail
     int forward(const float* t, const float* rot, float* success) {
         MV_RC(points(t, rot));
-        MV_RC(mvnerf_field_eval_stash_split(w.points, w.dirs, w.z, c->images, c->features, nullptr, c->intrinsics, c->extrinsics_inv, c->packed_net,
-                                            c->split, c->B, c->V, (int)w.ld, 1, c->H, c->W, w.rgbs, w.stash, w.field_ws, stream));
-        MV_RC(mvnerf_stash_fused_acts(w.stash, c->B, c->V, (int)w.ld, w.acts_p, stream));
+        MV_RC(mvnerf::pose_rows_trunk(w.points, w.dirs, w.z, c->images, c->features, c->intrinsics, c->extrinsics_inv, c->packed_net, c->split,
+                                      c->B, c->V, w.ld, c->H, c->W, w.rgbs, w.stash, w.field_ws, w.acts_p, stream));
         if (padded) MV_RC(copy_rows(w.acts_p, w.acts, w.ld, w.n));
         MV_RC(mvnerf_grasp_head_fwd(w.acts, w.head_packed, c->head_b4, c->head_bc, w.N, w.c, w.y, stream));
         return mvnerf_grasp_tail_fwd(w.y, w.tail_packed, w.M, c->n5, success, w.tail_stash, stream);

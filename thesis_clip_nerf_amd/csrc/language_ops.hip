@@ -9,8 +9,7 @@
 // hundred floats; each thread walks its rows in order and a fixed LDS tree adds the threads (no atomics: the same bits from run to run).
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvnerf_hip.h"
-#include "mvnerf_kernels.h"
+#include "mvnerf_api.h"
 #include "mvnerf_language.h"
 
 namespace mvnerf {
@@ -68,8 +67,8 @@ __global__ __launch_bounds__(kLossThreads) void cosine_loss_kernel(const float* 
 
 extern "C" {
 
-static bool al4l(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-static int hs_loss(hipError_t e, const char* who) { return e == hipSuccess ? 0 : mvnerf::api_fail((int)e, "%s: %s", who, hipGetErrorString(e)); }
+using mvnerf::aligned4;
+using mvnerf::hip_status;
 
 int mvnerf_landscape_loss(const float* y, const float* label, int B, int np, int kind, float weight, float* g_y, float* loss,
                           mvnerf_stream_t stream) {
@@ -77,22 +76,22 @@ int mvnerf_landscape_loss(const float* y, const float* label, int B, int np, int
     if (B <= 0 || np <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_landscape_loss: B=%d np=%d", B, np);
     if (kind != MVNERF_LOSS_KL_DIVERGENCE && kind != MVNERF_LOSS_CROSS_ENTROPY)
         return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_landscape_loss: kind=%d (0 kl_divergence, 1 cross_entropy)", kind);
-    if (!al4l(y) || !al4l(label) || !al4l(g_y) || !al4l(loss)) return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_landscape_loss: buffers must be 4-byte aligned");
+    if (!aligned4(y) || !aligned4(label) || !aligned4(g_y) || !aligned4(loss)) return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_landscape_loss: buffers must be 4-byte aligned");
     // kl_divergence is one loss per batch element, summed by the step; cross_entropy is their mean
     const float coef = kind == MVNERF_LOSS_CROSS_ENTROPY ? weight / (float)B : weight;
     hipLaunchKernelGGL(mvnerf::landscape_loss_kernel, dim3(1), dim3(mvnerf::kLossThreads), 0, static_cast<hipStream_t>(stream), y, label, B, np, kind,
                        coef, g_y, loss);
-    return hs_loss(hipGetLastError(), "mvnerf_landscape_loss");
+    return hip_status(hipGetLastError(), "mvnerf_landscape_loss");
 }
 
 int mvnerf_cosine_loss(const float* x, const float* label, long rows, int dim, float scale, float* g_x, float* loss, mvnerf_stream_t stream) {
     if (!x || !label || !g_x || !loss) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_cosine_loss: null pointer");
     if (rows <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_cosine_loss: rows=%ld", rows);
     if (dim != 3 && dim != 4 && dim != 6) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_cosine_loss: dim=%d (3, 4, or 6 = two halves of 3)", dim);
-    if (!al4l(x) || !al4l(label) || !al4l(g_x) || !al4l(loss)) return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_cosine_loss: buffers must be 4-byte aligned");
+    if (!aligned4(x) || !aligned4(label) || !aligned4(g_x) || !aligned4(loss)) return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_cosine_loss: buffers must be 4-byte aligned");
     hipLaunchKernelGGL(mvnerf::cosine_loss_kernel, dim3(1), dim3(mvnerf::kLossThreads), 0, static_cast<hipStream_t>(stream), x, label, rows, dim,
                        -(scale / (float)rows), g_x, loss);
-    return hs_loss(hipGetLastError(), "mvnerf_cosine_loss");
+    return hip_status(hipGetLastError(), "mvnerf_cosine_loss");
 }
 
 }  // extern "C"

@@ -23,11 +23,11 @@ struct FieldParams {
     float* embedding;      // optional (B,R,S,128): trunk output before the read-out
     float* acts_view;      // optional (4,B*V,R,S,128): layer 0 and the 3 per-view blocks (complete_output)
     float* acts_fused;     // optional (4,B,R,S,128): view mean and the 3 fusion blocks (complete_output)
-    // training mode (kStash): pre-activation tensors in tile layout [slot][tile][128][32]
-    float* stash;          // 7 per-view slots (x0,h1,x1,h2,x2,h3,x3), tile = view tile (b*V+v)*tiles_per_b + k
-    long stash_stride;     // floats per per-view slot = V * n_tiles * 4096
-    float* stash_fused;    // 7 fused slots (mean,h4,x4,h5,x5,h6,x6), tile = b*tiles_per_b + k
-    long stash_fused_stride;   // floats per fused slot = n_tiles * 4096
+    // training mode (kStash): pre-activation tensors in tile layout [slot][tile][128][32]; the slots and their order: StashLayout, mvnerf_api.h
+    float* stash;          // the 7 per-view slots
+    long stash_stride;     // floats per per-view slot (StashLayout::view_stride)
+    float* stash_fused;    // the 7 fused slots, behind them
+    long stash_fused_stride;   // floats per fused slot (StashLayout::fused_stride)
     int B, V, R, S, H, W;
     long total;            // B*R*S samples
     long n_tiles;          // ceil(total / 32)

@@ -16,8 +16,7 @@
 // ~2 x B * P * n5 * 24 per step); the point is to replace ~60 torch launches per step and keep the whole step capturable.
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvnerf_hip.h"
-#include "mvnerf_kernels.h"
+#include "mvnerf_api.h"
 #include "mvnerf_pose.h"
 
 namespace mvnerf {
@@ -131,10 +130,8 @@ __global__ void pose_adam_step_kernel(pose::AdamConfig c, int rep, int P, const 
 // ---- C ABI ----------------------------------------------------------------------------------------------------------------------------------
 extern "C" {
 
-static bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-static int hs_pose(hipError_t e, const char* who) {
-    return e == hipSuccess ? 0 : mvnerf::api_fail((int)e, "%s: %s", who, hipGetErrorString(e));
-}
+using mvnerf::aligned4;
+using mvnerf::hip_status;
 
 int mvnerf_pose_query_points(const float* t, const float* rot, int rep, const float* offsets, int P, int n5, int B, long ld, float* points,
                              float* dirs, mvnerf_stream_t stream) {
@@ -142,12 +139,12 @@ int mvnerf_pose_query_points(const float* t, const float* rot, int rep, const fl
     if (P <= 0 || n5 <= 0 || B <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_pose_query_points: P=%d n5=%d B=%d", P, n5, B);
     if (rep != 0 && rep != 1) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_query_points: rep=%d (0 quaternion, 1 6d)", rep);
     if (ld < (long)P * n5) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_query_points: ld=%ld < P*n5=%ld", ld, (long)P * n5);
-    if (!al4(t) || !al4(rot) || !al4(offsets) || !al4(points) || !al4(dirs))
+    if (!aligned4(t) || !aligned4(rot) || !aligned4(offsets) || !aligned4(points) || !aligned4(dirs))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_pose_query_points: buffers must be 4-byte aligned");
     const long n = (long)P * n5;
     hipLaunchKernelGGL(mvnerf::pose_query_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        t, rot, rep, offsets, P, n5, B, ld, points, dirs);
-    return hs_pose(hipGetLastError(), "mvnerf_pose_query_points");
+    return hip_status(hipGetLastError(), "mvnerf_pose_query_points");
 }
 
 int mvnerf_pose_query_vjp(const float* rot, int rep, const float* offsets, const float* d_points, const float* d_dirs, int P, int n5, int B,
@@ -156,12 +153,12 @@ int mvnerf_pose_query_vjp(const float* rot, int rep, const float* offsets, const
     if (P <= 0 || n5 <= 0 || B <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_pose_query_vjp: P=%d n5=%d B=%d", P, n5, B);
     if (rep != 0 && rep != 1) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_query_vjp: rep=%d (0 quaternion, 1 6d)", rep);
     if (ld < (long)P * n5) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_query_vjp: ld=%ld < P*n5=%ld", ld, (long)P * n5);
-    if (!al4(rot) || !al4(offsets) || !al4(d_points) || !al4(d_dirs) || !al4(d_t) || !al4(d_rot))
+    if (!aligned4(rot) || !aligned4(offsets) || !aligned4(d_points) || !aligned4(d_dirs) || !aligned4(d_t) || !aligned4(d_rot))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_pose_query_vjp: buffers must be 4-byte aligned");
     const int waves = mvnerf::kVjpWaves;
     hipLaunchKernelGGL(mvnerf::pose_query_vjp_kernel, dim3((unsigned)((P + waves - 1) / waves)), dim3(64 * waves), 0,
                        static_cast<hipStream_t>(stream), rot, rep, offsets, d_points, d_dirs, P, n5, B, ld, scale, d_t, d_rot);
-    return hs_pose(hipGetLastError(), "mvnerf_pose_query_vjp");
+    return hip_status(hipGetLastError(), "mvnerf_pose_query_vjp");
 }
 
 int mvnerf_pose_query_jvp(const float* rot, int rep, const float* offsets, const float* c_t, const float* c_rot, int P, int n5, int B, long ld,
@@ -170,12 +167,12 @@ int mvnerf_pose_query_jvp(const float* rot, int rep, const float* offsets, const
     if (P <= 0 || n5 <= 0 || B <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_pose_query_jvp: P=%d n5=%d B=%d", P, n5, B);
     if (rep != 0 && rep != 1) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_query_jvp: rep=%d (0 quaternion, 1 6d)", rep);
     if (ld < (long)P * n5) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_query_jvp: ld=%ld < P*n5=%ld", ld, (long)P * n5);
-    if (!al4(rot) || !al4(offsets) || !al4(c_t) || !al4(c_rot) || !al4(t_points) || !al4(t_dirs))
+    if (!aligned4(rot) || !aligned4(offsets) || !aligned4(c_t) || !aligned4(c_rot) || !aligned4(t_points) || !aligned4(t_dirs))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_pose_query_jvp: buffers must be 4-byte aligned");
     const long n = (long)P * n5;
     hipLaunchKernelGGL(mvnerf::pose_query_jvp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), rot, rep,
                        offsets, c_t, c_rot, P, n5, B, ld, t_points, t_dirs);
-    return hs_pose(hipGetLastError(), "mvnerf_pose_query_jvp");
+    return hip_status(hipGetLastError(), "mvnerf_pose_query_jvp");
 }
 
 int mvnerf_pose_adam_step(const mvnerf_pose_adam_config* cfg, int rep, int P, const int* train_flags, int* counters, const float* g_t,
@@ -184,8 +181,8 @@ int mvnerf_pose_adam_step(const mvnerf_pose_adam_config* cfg, int rep, int P, co
         return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_pose_adam_step: null pointer");
     if (P <= 0) return mvnerf::api_fail(MVNERF_E_ARG, "mvnerf_pose_adam_step: P=%d", P);
     if (rep != 0 && rep != 1) return mvnerf::api_fail(MVNERF_E_SHAPE, "mvnerf_pose_adam_step: rep=%d (0 quaternion, 1 6d)", rep);
-    if (!al4(train_flags) || !al4(counters) || !al4(g_t) || !al4(g_rot) || !al4(m_t) || !al4(v_t) || !al4(m_r) || !al4(v_r) || !al4(t) ||
-        !al4(rot))
+    if (!aligned4(train_flags) || !aligned4(counters) || !aligned4(g_t) || !aligned4(g_rot) || !aligned4(m_t) || !aligned4(v_t) || !aligned4(m_r) ||
+        !aligned4(v_r) || !aligned4(t) || !aligned4(rot))
         return mvnerf::api_fail(MVNERF_E_ALIGN, "mvnerf_pose_adam_step: buffers must be 4-byte aligned");
     mvnerf::pose::AdamConfig c;
     for (int v = 0; v < 2; ++v) { c.lr0[v] = cfg->lr0[v]; c.decay[v] = cfg->decay[v]; }
@@ -194,7 +191,7 @@ int mvnerf_pose_adam_step(const mvnerf_pose_adam_config* cfg, int rep, int P, co
     for (int i = 0; i < 3; ++i) { c.lo[i] = cfg->lo[i]; c.hi[i] = cfg->hi[i]; }
     hipLaunchKernelGGL(mvnerf::pose_adam_step_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), c,
                        rep, P, train_flags, counters, g_t, g_rot, m_t, v_t, m_r, v_r, t, rot);
-    return hs_pose(hipGetLastError(), "mvnerf_pose_adam_step");
+    return hip_status(hipGetLastError(), "mvnerf_pose_adam_step");
 }
 
 }  // extern "C"

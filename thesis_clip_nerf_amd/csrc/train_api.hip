@@ -16,14 +16,10 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "../../include/mvnerf_hip.h"
-#include "mvnerf_kernels.h"
+#include "mvnerf_api.h"
 #include "mvnerf_math.h"
 
 namespace {
-
-constexpr size_t kAlign = 256;
-size_t up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
 
 struct TrainWs {
     float *z, *weights, *z_all, *rgbs_c, *rgbs_f, *d_rgb, *d_fine, *d_rgbs_c, *d_rgbs_f, *d_z_all, *d_w, *field_ws, *tables, *texel_grad;
@@ -35,33 +31,28 @@ struct TrainWs {
 
 TrainWs carve_train(void* base, int B, int V, int R, int S, int H, int W, int use_tables, int want_d_features) {
     TrainWs w;
-    char* p = static_cast<char*>(base);
+    mvnerf::Bump ws(base);
     const size_t n = (size_t)B * R * S, rays = (size_t)B * R;
-    auto take = [&](size_t bytes) {
-        char* q = p;
-        p += up(bytes);
-        return q;
-    };
-    w.z = reinterpret_cast<float*>(take(n * 4));
-    w.weights = reinterpret_cast<float*>(take(n * 4));
-    w.z_all = reinterpret_cast<float*>(take(2 * n * 4));
-    w.rank = reinterpret_cast<int32_t*>(take(n * 4));
-    w.rgbs_c = reinterpret_cast<float*>(take(4 * n * 4));
-    w.rgbs_f = reinterpret_cast<float*>(take(8 * n * 4));
-    w.d_rgb = reinterpret_cast<float*>(take(rays * 3 * 4));
-    w.d_fine = reinterpret_cast<float*>(take(rays * 3 * 4));
-    w.d_rgbs_c = reinterpret_cast<float*>(take(4 * n * 4));
-    w.d_rgbs_f = reinterpret_cast<float*>(take(8 * n * 4));
-    w.d_z_all = reinterpret_cast<float*>(take(2 * n * 4));
-    w.d_w = reinterpret_cast<float*>(take(n * 4));
-    w.field_ws = reinterpret_cast<float*>(take(mvnerf_field_workspace_bytes(B, V, R)));
-    w.stash_c = reinterpret_cast<float*>(take(mvnerf_stash_bytes(B, V, R, S)));
-    w.stash_f = reinterpret_cast<float*>(take(mvnerf_stash_bytes(B, V, R, 2 * S)));
-    w.bwd_scratch = take(mvnerf_field_backward_scratch_bytes(B, V, R, 2 * S));
+    w.z = ws.floats(n);
+    w.weights = ws.floats(n);
+    w.z_all = ws.floats(2 * n);
+    w.rank = static_cast<int32_t*>(ws.take(n * 4));
+    w.rgbs_c = ws.floats(4 * n);
+    w.rgbs_f = ws.floats(8 * n);
+    w.d_rgb = ws.floats(rays * 3);
+    w.d_fine = ws.floats(rays * 3);
+    w.d_rgbs_c = ws.floats(4 * n);
+    w.d_rgbs_f = ws.floats(8 * n);
+    w.d_z_all = ws.floats(2 * n);
+    w.d_w = ws.floats(n);
+    w.field_ws = static_cast<float*>(ws.take(mvnerf_field_workspace_bytes(B, V, R)));
+    w.stash_c = static_cast<float*>(ws.take(mvnerf_stash_bytes(B, V, R, S)));
+    w.stash_f = static_cast<float*>(ws.take(mvnerf_stash_bytes(B, V, R, 2 * S)));
+    w.bwd_scratch = ws.take(mvnerf_field_backward_scratch_bytes(B, V, R, 2 * S));
     const size_t tb = mvnerf_texel_table_bytes(B, V, H, W);
-    w.tables = use_tables ? reinterpret_cast<float*>(take(2 * tb)) : nullptr;
-    w.texel_grad = (use_tables && want_d_features) ? reinterpret_cast<float*>(take(tb)) : nullptr;
-    w.bytes = (size_t)(p - static_cast<char*>(base));
+    w.tables = use_tables ? static_cast<float*>(ws.take(2 * tb)) : nullptr;
+    w.texel_grad = (use_tables && want_d_features) ? static_cast<float*>(ws.take(tb)) : nullptr;
+    w.bytes = ws.bytes();
     return w;
 }
 
@@ -74,14 +65,9 @@ size_t mvnerf_train_workspace_bytes(int B, int V, int R, int S, int H, int W, in
     return carve_train(nullptr, B, V, R, S, H, W, use_texel_tables, want_d_features).bytes;
 }
 
-#define MV_RC(x)                 \
-    do {                         \
-        int rc_ = (x);           \
-        if (rc_ != 0) return rc_; \
-    } while (0)
-
 int mvnerf_loss_and_grads(const mvnerf_train_call* c, mvnerf_stream_t stream) {
     using mvnerf::api_fail;
+    const char* const who = "mvnerf_loss_and_grads";
     if (!c) return api_fail(MVNERF_E_ARG, "mvnerf_loss_and_grads: null call");
     if (!c->rays_o || !c->rays_d || !c->images || !c->features || !c->intrinsics || !c->extrinsics_inv || !c->u_coarse || !c->u_fine ||
         !c->labels || !c->net_coarse || !c->net_fine || !c->packed_coarse || !c->packed_fine || !c->bwd_streams_coarse ||
@@ -92,7 +78,7 @@ int mvnerf_loss_and_grads(const mvnerf_train_call* c, mvnerf_stream_t stream) {
     const int B = c->B, V = c->V, R = c->R, S = c->S, H = c->H, W = c->W;
     if (B <= 0 || V <= 0 || R <= 0 || H < 2 || W < 2) return api_fail(MVNERF_E_ARG, "mvnerf_loss_and_grads: B=%d V=%d R=%d H=%d W=%d", B, V, R, H, W);
     if (S != 64) return api_fail(MVNERF_E_SHAPE, "mvnerf_loss_and_grads: S=%d, only the reference's n_samples=64 is built", S);
-    if ((reinterpret_cast<uintptr_t>(c->workspace) & 255u) != 0)
+    if (!mvnerf::aligned256(c->workspace))
         return api_fail(MVNERF_E_ALIGN, "mvnerf_loss_and_grads: workspace must be 256-byte aligned");
     const int want_df = c->d_features != nullptr;
     const TrainWs w = carve_train(c->workspace, B, V, R, S, H, W, c->use_texel_tables, want_df);
@@ -125,12 +111,12 @@ int mvnerf_loss_and_grads(const mvnerf_train_call* c, mvnerf_stream_t stream) {
                                       c->packed_fine, B, V, R, 2 * S, H, W, w.rgbs_f, w.stash_f, w.field_ws, stream));
     MV_RC(mvnerf_composite(w.z_all, w.rgbs_f, n_rays, 2 * S, c->fine_rgb, c->fine_depth, nullptr, stream));
     // ---- loss = MSE(y, rgb) + MSE(y, fine_rgb) (model_v0.py:193) and its gradient w.r.t. the two images ----
-    if (mvnerf::launch_zero(c->loss, sizeof(float), st) != hipSuccess) return api_fail(1, "mvnerf_loss_and_grads: launch_zero failed");
+    MV_HIP(mvnerf::launch_zero(c->loss, sizeof(float), st), who);
     MV_RC(mvnerf_mse_grad(c->rgb, c->labels, (long)n_rays * 3, w.d_rgb, c->loss, stream));
     MV_RC(mvnerf_mse_grad(c->fine_rgb, c->labels, (long)n_rays * 3, w.d_fine, c->loss, stream));
     // ---- backward ----
-    if (mvnerf::launch_zero(c->grad, 2 * (size_t)mvnerf::kNetParams * sizeof(float), st) != hipSuccess) return 1;
-    if (want_df && mvnerf::launch_zero(c->d_features, (size_t)B * V * H * W * 256 * sizeof(float), st) != hipSuccess) return 1;
+    MV_HIP(mvnerf::launch_zero(c->grad, 2 * (size_t)mvnerf::kNetParams * sizeof(float), st), who);
+    if (want_df) MV_HIP(mvnerf::launch_zero(c->d_features, (size_t)B * V * H * W * 256 * sizeof(float), st), who);
     float* gc = c->grad;
     float* gf = c->grad + mvnerf::kNetParams;
     MV_RC(mvnerf_composite_bwd(w.z_all, w.rgbs_f, w.d_fine, nullptr, nullptr, n_rays, 2 * S, w.d_rgbs_f, c->stop_fine_z ? nullptr : w.d_z_all,
@@ -138,8 +124,7 @@ int mvnerf_loss_and_grads(const mvnerf_train_call* c, mvnerf_stream_t stream) {
     MV_RC(mvnerf_field_backward_table(c->rays_o, c->rays_d, w.z_all, c->images, c->features, tab_f, w.texel_grad, c->intrinsics, c->extrinsics_inv,
                                       c->net_fine, c->bwd_streams_fine, w.stash_f, w.rgbs_f, w.d_rgbs_f, B, V, R, 2 * S, H, W, w.bwd_scratch, gf,
                                       c->stop_fine_z ? nullptr : w.d_z_all, c->d_features, stream));
-    if (c->fine_grad_event && hipEventRecord(static_cast<hipEvent_t>(c->fine_grad_event), st) != hipSuccess)
-        return api_fail(1, "mvnerf_loss_and_grads: hipEventRecord(fine_grad_event) failed");
+    if (c->fine_grad_event) MV_HIP(hipEventRecord(static_cast<hipEvent_t>(c->fine_grad_event), st), who);
     const float* d_w = nullptr;
     if (!c->stop_fine_z) {                                                  // fine loss -> fine sample depths -> sample_pdf -> coarse weights (F12)
         MV_RC(mvnerf_resample_bwd(w.z, w.weights, c->u_fine, w.rank, w.d_z_all, n_rays, S, c->q7_mode, w.d_w, stream));
