@@ -758,6 +758,17 @@ int mvnerf_render_fwd_split_ex(const float* rays_o, const float* rays_d, const f
                                float* rgb, float* depth, float* fine_rgb, float* fine_depth, void* workspace, float* texel_tables,
                                int tables_ready, int which, float* range_status, mvnerf_stream_t stream);
 
+/* The tail of both feature producers as one launch (layers.py:459-477 ConvFusion + :617-618,658-659 UpSampling2D(bilinear);
+ * legacy_layers.py:154-191 CombineCLIPVisualV0):  out = bilinear_x2( act([a | b]) . weight ).
+ * a (N,h,w,Ca), b (N,h,w,Cb): fp32, NHWC contiguous, concatenated in that order; weight (Ca+Cb, 256) row-major, the Keras
+ * (1,1,Cin,256) kernel as stored.  act: 0 identity, 1 relu, 2 elu (alpha 1), applied to the concatenated input before the product.
+ * out (N,2h,2w,256) NHWC: fp32, or bf16 (round to nearest even, the last operation) when out_bf16 != 0.  The product is exact-fp32 MFMA
+ * with fp32 accumulation in a fixed order; the up-sampling uses half-pixel centres with clamped indices (weights 3/4, 1/4).  The
+ * low-resolution product never reaches global memory: no workspace, no atomics, bit-identical from run to run.
+ * Ca, Cb: multiples of 16, each >= 16, Ca + Cb <= 512 (else MVNERF_E_SHAPE; so is act outside 0..2).  All four pointers 16-byte aligned. */
+int mvnerf_fuse_upsample2x(const float* a, const float* b, const float* weight, int N, int h, int w, int Ca, int Cb, int act,
+                           void* out, int out_bf16, mvnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,7 @@ SIGNATURES = {
                                 [c_int, c_void_p]),
     'mvnerf_render_fwd_split_ex': (c_int, [c_void_p] * 12 + [c_int] * 6 + [c_double, c_double, c_int] + [c_void_p] * 6 +
                                    [c_int, c_int, c_void_p, c_void_p]),
+    'mvnerf_fuse_upsample2x': (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

@@ -209,17 +209,52 @@ class VisualFeatures(nn.Module):
         return torch.cat([latents, self.conv_features(x)], 1)                  # NCHW view, channels-last storage
 
 
-class CombineCLIPVisualV0(nn.Module):
-    """legacy_layers.py:154-191: [resize(clip stage-1 map, (H/2, W/2)) | visual features] -> 1x1 conv (no bias) -> x2 bilinear."""
+_ACT_CODES = {None: 0, 'relu': 1, 'elu': 2}
+_ACT_FNS = {None: lambda x: x, 'relu': F.relu, 'elu': F.elu}
 
-    def __init__(self, half_size=(240, 320), clip_channels=256, visual_channels=256, filters=256):
+
+def _wants_fused(fused_tail, *tensors):
+    """The fused-tail switch: True | False | 'auto' = on the GPU and nothing in the call needs a gradient (the fused pass has no backward)."""
+    if fused_tail not in (True, False, 'auto'):
+        raise ValueError(f"fused_tail: {fused_tail!r}, expected True, False or 'auto'")
+    if fused_tail is False:
+        return False
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+    on_gpu = all(t.is_cuda for t in tensors)
+    if fused_tail is True:
+        if needs_grad:
+            raise RuntimeError('fused_tail=True: the fused tail has no backward pass; run under torch.no_grad(), freeze the inputs, '
+                               "or use fused_tail='auto'")
+        return True                                                  # (a CPU tensor fails in ops: there is no CPU path)
+    return on_gpu and not needs_grad
+
+
+def conv_fusion_tail(a, b, conv, activation=None, fused=False, out_dtype=None):
+    """`up_sample(conv(act([a | b])))` of NCHW a, b with a bias-free 1x1 `conv` to 256 filters -> (N, 256, 2h, 2w), channels-last storage.
+    fused: one ops.fuse_upsample2x call, which writes NHWC in `out_dtype` (fp32 | bf16) directly; else torch (fp32; the caller casts)."""
+    if not fused:
+        return _up(conv(_ACT_FNS[activation](torch.cat([a, b], 1))), 2)
+    from . import ops
+    nhwc = lambda t: t.detach().permute(0, 2, 3, 1).contiguous()      # free when the storage is channels-last already
+    weight = conv.weight.detach().reshape(conv.out_channels, conv.in_channels).t().contiguous()      # (Cin, 256): the Keras kernel as stored
+    out = ops.fuse_upsample2x(nhwc(a), nhwc(b), weight, _ACT_CODES[activation], out_dtype or torch.float32)
+    return out.permute(0, 3, 1, 2)
+
+
+class CombineCLIPVisualV0(nn.Module):
+    """legacy_layers.py:154-191: [resize(clip stage-1 map, (H/2, W/2)) | visual features] -> 1x1 conv (no bias) -> x2 bilinear.
+    fused_tail (default False: torch): concat + conv + up-sampling as one HIP pass, see :func:`conv_fusion_tail`."""
+
+    def __init__(self, half_size=(240, 320), clip_channels=256, visual_channels=256, filters=256, fused_tail=False):
         super().__init__()
         self.conv = SameConv2d(clip_channels + visual_channels, filters, 1, bias=False)
         self.half_size = tuple(half_size)
+        self.fused_tail = fused_tail
 
-    def forward(self, clip_256, visual_features):
-        fusion = torch.cat([_resize(clip_256, self.half_size), visual_features], 1)
-        return _up(self.conv(fusion), 2)
+    def forward(self, clip_256, visual_features, out_dtype=None):
+        clip = _resize(clip_256, self.half_size)
+        fused = _wants_fused(self.fused_tail, clip, visual_features, self.conv.weight)
+        return conv_fusion_tail(clip, visual_features, self.conv, None, fused, out_dtype)
 
 
 class SyntheticCLIPStage1(nn.Module):
@@ -265,6 +300,259 @@ class FeatureProducer(nn.Module):
         out = fused.permute(0, 2, 3, 1)
         out = out.to(self.out_dtype)
         return out if out.is_contiguous() else out.contiguous()
+
+
+# ---- the language fusion (layers.py:414-520, 593-660) ------------------------------------------------------------------------
+def _activation(name):
+    if name not in ('relu', 'elu'):
+        raise ValueError(f'activation {name} not supported')
+    return _ACT_FNS[name]
+
+
+class DoubleConv(nn.Module):
+    """layers.py:414-434: two bias-free 3x3 convolutions, the activation after each."""
+
+    def __init__(self, c_in, filters, activation='relu'):
+        super().__init__()
+        self.conv_1 = SameConv2d(c_in, filters, 3, bias=False)
+        self.conv_2 = SameConv2d(filters, filters, 3, bias=False)
+        self.act = _activation(activation)
+
+    def forward(self, x):
+        return self.act(self.conv_2(self.act(self.conv_1(x))))
+
+
+class Up(nn.Module):
+    """layers.py:437-456: [x2 bilinear of x | CLIP stage map resized to `shape`] -> DoubleConv."""
+
+    def __init__(self, shape, c_in, c_clip, filters, activation='relu'):
+        super().__init__()
+        self.shape = tuple(shape)
+        self.double_conv = DoubleConv(c_in + c_clip, filters, activation)
+
+    def forward(self, x, clip_x):
+        return self.double_conv(torch.cat([_up(x, 2), _resize(clip_x, self.shape)], 1))
+
+
+class ConvFusion(nn.Module):
+    """layers.py:459-477: activation([x1 | x2]) -> bias-free 1x1 convolution (the activation comes BEFORE the convolution)."""
+
+    def __init__(self, c_in, filters, activation='relu'):
+        super().__init__()
+        self.conv = SameConv2d(c_in, filters, 1, bias=False)
+        self.activation = activation
+        self.act = _activation(activation)
+
+    def forward(self, x1, x2):
+        return self.conv(self.act(torch.cat([x1, x2], 1)))
+
+
+class Tile(nn.Module):
+    """layers.py:494-520: the text embedding through a bias-free Dense (use_dense) or cut to its first `filters` entries (`Slice`),
+    as one value per channel; the reference repeats it over `shape`, here it broadcasts."""
+
+    def __init__(self, text_dim=1024, filters=256, use_dense=True):
+        super().__init__()
+        if not use_dense and filters > text_dim:
+            raise ValueError(f'Slice: {filters} filters from a text embedding of {text_dim}')
+        self.filters = filters
+        self.dense = nn.Linear(text_dim, filters, bias=False) if use_dense else None
+        if use_dense:
+            nn.init.xavier_uniform_(self.dense.weight)
+
+    def forward(self, clip_textuals):
+        x = self.dense(clip_textuals) if self.dense is not None else clip_textuals[:, :self.filters]
+        return x[:, :, None, None]
+
+
+class MultiplyFusion(nn.Module):
+    """layers.py:480-491: the feature map times the tiled text embedding, channel by channel."""
+
+    def __init__(self, text_dim=1024, filters=256, use_dense=True):
+        super().__init__()
+        self.tile = Tile(text_dim, filters, use_dense)
+
+    def forward(self, clip_x, clip_textuals):
+        return clip_x * self.tile(clip_textuals)
+
+
+class CombineCLIPVisualV4(nn.Module):
+    """layers.py:593-660 (`LanguageNeRF.combine_clip_visual`, model_v4.py:176-190: use_dense=True, activation='elu'): a U-Net over the
+    CLIP stage maps, the text embedding multiplied in at three scales, the visual features fused in at three scales; ends with the
+    tail of :class:`CombineCLIPVisualV0` (`conv_fusion_3` + `up_sample`).  up3_filters=128 is V4, 256 is V3 (:523-590), which differs
+    in nothing else.  Inputs are NCHW (channels-last storage); the pooled CLIP vector is carried and not used, as in the reference.
+    fused_tail: 'auto' | True | False - the tail as one HIP pass (:func:`conv_fusion_tail`) when on the GPU and nothing needs a gradient.
+    Parity unpinned, like the rest of this file."""
+
+    def __init__(self, use_dense=False, activation='relu', half_size=(240, 320), clip_channels=(256, 512, 1024, 2048), text_dim=1024,
+                 widths=(1024, 512, 256), up3_filters=128, visual_channels=256, filters=256, fused_tail='auto'):
+        super().__init__()
+        hh, hw = half_size
+        if hh % 8 or hw % 8:
+            raise ValueError(f'half size {half_size}: both must be multiples of 8 (three x2 up-samplings end there)')
+        c1, c2, c3, c4 = clip_channels
+        w1, w2, w3 = widths
+        self.half_size = (hh, hw)
+        self.size_1, self.size_2, self.size_3 = (hh // 2, hw // 2), (hh // 4, hw // 4), (hh // 8, hw // 8)
+        self.activation = activation
+        self.act = _activation(activation)
+        self.conv = SameConv2d(c4, w1, 3, bias=False)                                   # Conv2D(..., activation=activation)
+        self.multiply_fusion_1 = MultiplyFusion(text_dim, w1, use_dense)
+        self.up_1 = Up(self.size_2, w1, c3, w2, activation)
+        self.multiply_fusion_2 = MultiplyFusion(text_dim, w2, use_dense)
+        self.conv_fusion_1 = ConvFusion(w2 + visual_channels, w2, activation)
+        self.up_2 = Up(self.size_1, w2, c2, w3, activation)
+        self.multiply_fusion_3 = MultiplyFusion(text_dim, w3, use_dense)
+        self.conv_fusion_2 = ConvFusion(w3 + visual_channels, w3, activation)
+        self.up_3 = Up(self.half_size, w3, c1, up3_filters, activation)
+        self.conv_fusion_3 = ConvFusion(up3_filters + visual_channels, filters, activation)
+        self.fused_tail = fused_tail
+
+    def forward(self, clip_outputs, visual_features, clip_textuals, out_dtype=None):
+        _clip_visuals, clip_l1, clip_l2, clip_l3, clip_l4 = clip_outputs
+        vis_1 = _resize(visual_features, self.size_1)
+        vis_2 = _resize(visual_features, self.size_2)
+        x = self.act(self.conv(_resize(clip_l4, self.size_3)))
+        x = self.multiply_fusion_1(x, clip_textuals)
+        x = self.up_1(x, clip_l3)
+        x = self.multiply_fusion_2(x, clip_textuals)
+        x = self.conv_fusion_1(x, vis_2)
+        x = self.up_2(x, clip_l2)
+        x = self.multiply_fusion_3(x, clip_textuals)
+        x = self.conv_fusion_2(x, vis_1)
+        x = self.up_3(x, clip_l1)
+        fused = _wants_fused(self.fused_tail, x, visual_features, self.conv_fusion_3.conv.weight)
+        return conv_fusion_tail(x, visual_features, self.conv_fusion_3.conv, self.activation, fused, out_dtype)
+
+
+# ---- stand-ins for CLIP (its RN50 trunk, text transformer and BPE vocabulary are not available offline) ------------------------------
+class SyntheticCLIPPyramid(nn.Module):
+    """Frozen, seeded stand-in for the CLIP RN50 visual trunk with its stage outputs (clip/model.py): images (N, 3, H, W) ->
+    (pooled (N, embed_dim), stage maps (N, c_i, s_i, s_i) for the four stages).  Not trained, carries no semantics."""
+
+    def __init__(self, channels=(256, 512, 1024, 2048), sizes=(56, 28, 14, 7), embed_dim=1024, seed=0):
+        super().__init__()
+        g = torch.Generator().manual_seed(seed)
+        self.register_buffer('w_stem', torch.randn(channels[0], 3, 7, 7, generator=g) * 0.1)
+        for i in range(1, 4):
+            self.register_buffer(f'w_{i}', torch.randn(channels[i], channels[i - 1], 1, 1, generator=g) * (2.0 / channels[i - 1]) ** 0.5)
+        self.register_buffer('w_pool', torch.randn(embed_dim, channels[3], generator=g) * (1.0 / channels[3]) ** 0.5)
+        self.sizes = tuple((s, s) if isinstance(s, int) else tuple(s) for s in sizes)
+
+    @torch.no_grad()
+    def forward(self, x_nchw):
+        maps = [F.relu(F.adaptive_avg_pool2d(F.conv2d(x_nchw, self.w_stem, stride=2, padding=3), self.sizes[0]))]
+        for i in range(1, 4):
+            maps.append(F.relu(F.conv2d(F.adaptive_avg_pool2d(maps[-1], self.sizes[i]), getattr(self, f'w_{i}'))))
+        pooled = F.linear(maps[-1].mean((2, 3)), self.w_pool)
+        return (pooled, *maps)
+
+
+class SyntheticCLIPText(nn.Module):
+    """Frozen, seeded stand-in for CLIP's text transformer: token ids (N, 77) int32 (0 = padding) -> (N, embed_dim).  A token
+    table times a position table, summed over the instruction and scaled to unit RMS: different instructions give different
+    embeddings, word order counts, nothing is learnt."""
+
+    def __init__(self, vocab_size=49408, embed_dim=1024, context_length=77, seed=0):
+        super().__init__()
+        g = torch.Generator().manual_seed(seed)
+        self.register_buffer('token_table', torch.randn(vocab_size, embed_dim, generator=g))
+        self.register_buffer('position_table', 1.0 + 0.5 * torch.randn(context_length, embed_dim, generator=g))
+
+    @torch.no_grad()
+    def forward(self, tokens):
+        tokens = torch.as_tensor(tokens, device=self.token_table.device).long()
+        if tokens.dim() != 2 or tokens.shape[1] != self.position_table.shape[0]:
+            raise ValueError(f'tokens: shape {tuple(tokens.shape)}, expected (N, {self.position_table.shape[0]})')
+        mask = (tokens != 0).to(self.token_table.dtype)[..., None]
+        e = (self.token_table[tokens % self.token_table.shape[0]] * self.position_table * mask).sum(1)
+        return e / e.pow(2).mean(1, keepdim=True).sqrt().clamp_min(1e-6)
+
+
+def tokenize(texts, context_length=77):
+    """The shape and dtype of the reference's `clip/utils.tokenize`: str or list of str -> int32 (N, context_length), zero padded.
+    The ids are NOT CLIP's (its BPE vocabulary is not available offline): words and punctuation marks, lower-cased, get the id
+    1 + crc32(word) mod 49 405, between a start (49 406) and an end (49 407) id as CLIP places them.  Deterministic across runs."""
+    import re
+    import zlib
+    if isinstance(texts, str):
+        texts = [texts]
+    out = np.zeros((len(texts), context_length), dtype=np.int32)
+    for n, text in enumerate(texts):
+        words = re.findall(r'[a-z0-9]+|[^\sa-z0-9]', text.lower())
+        ids = [49406] + [1 + zlib.crc32(word.encode('utf-8')) % 49405 for word in words] + [49407]
+        if len(ids) > context_length:
+            raise RuntimeError(f'Input {text!r} is too long for context length {context_length}')
+        out[n, :len(ids)] = ids
+    return out
+
+
+class LanguageFeatureProducer(nn.Module):
+    """`LanguageNeRF`'s encoder prologue (model_v4.py:176-190, 277-288) as one frozen callable: images (N, H, W, 3) in [0, 1] and an
+    instruction - `tokens` (N | 1, 77) int32 through the text stand-in, or a ready `text_embedding` (N | 1, text_dim) - ->
+    combined_features (N, H, W, 256), NHWC-contiguous in `out_dtype`.  VisualFeatures + the CLIP pyramid + the text embedding +
+    CombineCLIPVisualV4(use_dense=True, activation='elu').  Nothing in it trains (the reference's tape watches `grasp_readout` only),
+    so with fused_tail='auto' the tail is the fused HIP pass whenever the producer is on the GPU."""
+
+    def __init__(self, original_image_size=(480, 640), out_dtype=torch.float32, fused_tail='auto', n_features=256, clip_pyramid=None,
+                 clip_text=None, combine_kw=None, **visual_kw):
+        super().__init__()
+        h, w = original_image_size
+        if h % 16 or w % 16:
+            raise ValueError('image height and width must be multiples of 16 (the fusion starts at 1/16 resolution)')
+        self.visual_features = VisualFeatures(n_features, original_image_size, **visual_kw)
+        self.clip_pyramid = clip_pyramid if clip_pyramid is not None else SyntheticCLIPPyramid()
+        self.clip_text = clip_text if clip_text is not None else SyntheticCLIPText()
+        kw = dict(use_dense=True, activation='elu', half_size=(h // 2, w // 2), visual_channels=n_features, fused_tail=fused_tail)
+        kw.update(combine_kw or {})
+        self.combine_clip_visual = CombineCLIPVisualV4(**kw)
+        self.out_dtype = out_dtype
+        self.requires_grad_(False)
+        self.eval()
+
+    def train(self, mode=True):
+        return super().train(False)                                    # frozen: stays in inference mode
+
+    @torch.no_grad()
+    def forward(self, images_nhwc, tokens=None, text_embedding=None):
+        if (tokens is None) == (text_embedding is None):
+            raise ValueError('give exactly one of tokens (N, 77) and text_embedding (N, text_dim)')
+        text = self.clip_text(tokens) if text_embedding is None else text_embedding
+        text = text.to(images_nhwc.dtype).expand(images_nhwc.shape[0], -1)
+        visual = self.visual_features(images_nhwc)
+        pyramid = self.clip_pyramid(images_nhwc.permute(0, 3, 1, 2))
+        fused = self.combine_clip_visual(pyramid, visual, text, out_dtype=self.out_dtype)      # (N, 256, H, W), channels-last storage
+        out = fused.permute(0, 2, 3, 1).to(self.out_dtype)
+        return out if out.is_contiguous() else out.contiguous()
+
+
+COMBINE_CLIP_VISUAL_V4_VARIABLES = ('conv', 'multiply_fusion_1.tile.dense', 'up_1.double_conv.conv_1', 'up_1.double_conv.conv_2',
+                                    'multiply_fusion_2.tile.dense', 'conv_fusion_1.conv', 'up_2.double_conv.conv_1',
+                                    'up_2.double_conv.conv_2', 'multiply_fusion_3.tile.dense', 'conv_fusion_2.conv',
+                                    'up_3.double_conv.conv_1', 'up_3.double_conv.conv_2', 'conv_fusion_3.conv')
+
+
+def load_combine_clip_visual_v4(module, arrays):
+    """`CombineCLIPVisualV4.weights` (Keras lists a model's variables in the order `__init__` assigns its layers, layers.py:597-618)
+    as plain arrays -> `module`, in place: COMBINE_CLIP_VISUAL_V4_VARIABLES, i.e. 13 kernels with use_dense=True (36 814 848 floats at
+    the reference's sizes) and the 10 non-Dense ones with use_dense=False (`Slice` has no variable).  Conv2D kernels are (kh, kw, in,
+    out), Dense kernels (in, out).  A shape mismatch raises and names the variable.  PARITY UNPINNED: the order could not be checked
+    against a TensorFlow dump here."""
+    names = [n for n in COMBINE_CLIP_VISUAL_V4_VARIABLES if module.multiply_fusion_1.tile.dense is not None or not n.endswith('.dense')]
+    arrays = list(arrays)
+    if len(arrays) != len(names):
+        raise ValueError(f'combine_clip_visual: {len(arrays)} variables, expected {len(names)}: {names}')
+    with torch.no_grad():
+        for name, array in zip(names, arrays):
+            layer = module.get_submodule(name)
+            array = np.asarray(array)
+            is_dense = isinstance(layer, nn.Linear)
+            expected = ((layer.in_features, layer.out_features) if is_dense else
+                        (*layer.kernel_size, layer.in_channels, layer.out_channels))
+            if tuple(array.shape) != expected:
+                raise ValueError(f'combine_clip_visual: variable {name!r} has shape {tuple(array.shape)}, expected {expected}')
+            t = torch.as_tensor(array).to(layer.weight.dtype)
+            layer.weight.copy_(t.T if is_dense else t.permute(3, 2, 0, 1))
 
 
 # ---- Keras variables -> this package (plain arrays; no TensorFlow needed) ------------------------------------------------
@@ -519,7 +807,9 @@ def count_parameters(module):
     return sum(p.numel() for p in module.parameters())
 
 
-__all__ = ['FeatureProducer', 'VisualFeatures', 'CombineCLIPVisualV0', 'ConvolutionalEncoder', 'VisionTransformerEncoder',
+__all__ = ['FeatureProducer', 'LanguageFeatureProducer', 'CombineCLIPVisualV4', 'DoubleConv', 'Up', 'ConvFusion', 'Tile',
+           'MultiplyFusion', 'SyntheticCLIPPyramid', 'SyntheticCLIPText', 'tokenize', 'conv_fusion_tail', 'load_combine_clip_visual_v4',
+           'COMBINE_CLIP_VISUAL_V4_VARIABLES', 'VisualFeatures', 'CombineCLIPVisualV0', 'ConvolutionalEncoder', 'VisionTransformerEncoder',
            'VisionTransformer', 'TransformerBlock', 'SyntheticCLIPStage1', 'flat_net_from_keras', 'keras_from_flat_net',
            'make_encoder_optimizer', 'KerasAdam', 'convolutional_encoder_weights', 'warmup_lr_lambda', 'load_conv', 'load_conv_transpose', 'load_dense', 'load_batchnorm', 'load_mha',
            'load_combine_clip_visual', 'load_grasp_readout', 'load_convolutional_encoder', 'load_transformer_block', 'count_parameters']

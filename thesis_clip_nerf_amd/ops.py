@@ -1472,3 +1472,31 @@ def pose_adam_step(cfg, train_flags, counters, g_t, g_rot, m_t, v_t, m_r, v_r, t
         rc = _lib.lib().mvnerf_pose_adam_step(ctypes.byref(cfg), rep, p, _p(train_flags), _p(counters), _p(g_t), _p(g_rot), _p(m_t),
                                               _p(v_t), _p(m_r), _p(v_r), _p(t), _p(rot), _stream(t))
     _lib.check(rc, 'pose_adam_step')
+
+
+FUSE_ACTIVATIONS = {None: 0, 'identity': 0, 'relu': 1, 'elu': 2}
+
+
+def fuse_upsample2x(a, b, weight, act, out_dtype=torch.float32, out=None):
+    """mvnerf_fuse_upsample2x: a (N,h,w,Ca), b (N,h,w,Cb) fp32 NHWC, weight (Ca+Cb,256) (the Keras 1x1 kernel as stored) ->
+    bilinear_x2(act([a | b]) . weight) as (N,2h,2w,256) NHWC in fp32 or bf16; act: 0 | 'identity', 1 | 'relu', 2 | 'elu'."""
+    _chk(a, 'a', shape=(None, None, None, None))
+    n, h, w, ca = a.shape
+    _chk(b, 'b', shape=(n, h, w, None))
+    cb = b.shape[3]
+    _chk(weight, 'weight', shape=(ca + cb, 256))
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'out_dtype: {out_dtype}, expected torch.float32 or torch.bfloat16')
+    if not isinstance(act, int):
+        if act not in FUSE_ACTIVATIONS:
+            raise ValueError(f'act: {act!r}, expected one of {list(FUSE_ACTIVATIONS)} or 0, 1, 2')
+        act = FUSE_ACTIVATIONS[act]
+    if out is None:
+        out = torch.empty((n, 2 * h, 2 * w, 256), dtype=out_dtype, device=a.device)
+    else:
+        _chk(out, 'out', dtype=out_dtype, shape=(n, 2 * h, 2 * w, 256))
+    with torch.cuda.device(a.device):
+        rc = _lib.lib().mvnerf_fuse_upsample2x(_p(a), _p(b), _p(weight), n, h, w, ca, cb, int(act), _p(out),
+                                               int(out_dtype == torch.bfloat16), _stream(a))
+    _lib.check(rc, 'fuse_upsample2x')
+    return out

@@ -6,7 +6,10 @@ Same structure and names as the reference - `LanguageDataGenerator`, `get_inputs
 
 * the dataset submodule (`load_dataset_language`, absent from the reference tree) -> :class:`SyntheticLanguageDataset`;
 * the frozen encoders (CLIP + visual features) -> a per-view feature map supplied by the dataset, since `combined_features` is an
-  input of the hot path; CLIP tokens are not produced (`inputs[7]` is None);
+  input of the hot path.  By default that is the synthetic bump map and `inputs[7]` (the CLIP tokens) is None; with
+  :class:`EncodedLanguageDataset` (`--encoder v4`) the map comes from `encoders.LanguageFeatureProducer` - the reference's
+  CombineCLIPVisualV4 on stand-ins for CLIP - run on the view and on the tokens of the scene's instruction, and `with_tokens=True`
+  puts those tokens, int32 (B, 77), into `inputs[7]`;
 * `OracleAgent.calculate_error` (src/lib/agents, absent) -> :func:`grasp_error`, the vendored `transformation_difference`;
 * `manipulation_tasks.Affine` / scipy `Rotation` -> the NumPy restatements below, with scipy's operation order;
 * hydra -> argparse; wandb -> a callback; loguru -> `log`.
@@ -27,6 +30,7 @@ import torch
 from ._lib import NET_PARAMS
 from .grasp_optimizer import DEFAULT_WORKSPACE_BOUNDS, DNGFOptimizer, compute_results
 from .lmvnerf import LanguageNeRF, categorical_crossentropy_from_logits, kl_divergence, store_trunk
+from .encoders import tokenize
 from .model import camera_parameters
 from .synthetic import glorot_net, pinhole, ring_pose
 from .train_nerf import init_training_session
@@ -220,19 +224,60 @@ class SyntheticLanguageDataset:
         img = self.colors[i][p].astype(np.float32) / np.float32(255)
         return np.tanh((img * 2 - 1) @ self.proj + (3 * bump)[..., None] * self.grasp_direction)
 
+    OBJECT_NAMES = ('red block', 'green bowl', 'blue mug')
+
+    def instruction(self, i):
+        """The scene's instruction, from its task_info: which of its objects to pick."""
+        objects = sorted(self.task_info[i])
+        target = self.task_info[i][objects[i % len(objects)]]['id']
+        return f'pick up the {self.OBJECT_NAMES[target % len(self.OBJECT_NAMES)]}, object {target + 1} of {len(objects)}'
+
+
+class EncodedLanguageDataset:
+    """A language dataset whose feature maps come from the frozen encoders: every attribute of `dataset`, plus `tokens(i)` - the
+    scene's instruction as int32 (77,) - and `feature_map(i, p)` = `producer` (encoders.LanguageFeatureProducer, already on the
+    device it is to run on) on view p with scene i's tokens.  device=None: the map as a float32 NumPy array (the host path of the
+    generator); a device: a tensor there in the producer's out_dtype, which `LanguageDataGenerator(device=...)` keeps without a host
+    round trip."""
+
+    def __init__(self, dataset, producer, device=None):
+        self.dataset, self.producer = dataset, producer
+        self.device = torch.device(device) if device is not None else None
+
+    def __getattr__(self, name):                     # (only reached for what this object does not have itself)
+        if name in ('dataset', 'producer', 'device'):
+            raise AttributeError(name)
+        return getattr(self.dataset, name)
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def tokens(self, i):
+        return tokenize([self.dataset.instruction(i)])[0]
+
+    def feature_map(self, i, p, instruction=None):
+        """instruction: another text than the scene's own (what would the map be had the user asked for something else?)."""
+        where = next(self.producer.parameters()).device
+        image = torch.from_numpy((self.dataset.colors[i][p][..., :3] / 255.0).astype(np.float32)).to(where)
+        tokens = self.tokens(i) if instruction is None else tokenize([instruction])[0]
+        out = self.producer(image[None], tokens=torch.from_numpy(tokens[None]).to(where))[0]
+        return out.float().cpu().numpy() if self.device is None else out.to(self.device)
+
 
 class LanguageDataGenerator:
     """data_generator/language.py + base.py: keras-Sequence semantics, numpy's global RNG drawn in the reference's order (per batch:
     np.random.choice of views per scene; Affine.random for the negatives and the rotation negatives per scene; np.random.randint and the
     augmentations per scene).  `batch` -> ((inputs, features), [landscape labels, d_t, d_r]) with inputs = [translations, rotations of
-    the landscape poses, translations, rotations of the gradient poses, images, intrinsics, extrinsics_inv, None (CLIP tokens)]: what
-    `LanguageNeRF.train_step(data, combined_features)` takes.
+    the landscape poses, translations, rotations of the gradient poses, images, intrinsics, extrinsics_inv, CLIP tokens]: what
+    `LanguageNeRF.train_step(data, combined_features)` takes.  The tokens are None unless with_tokens is set: then `dataset.tokens(i)`
+    of the batch, int32 (B, 77) (the feature maps of an :class:`EncodedLanguageDataset` already carry the instruction; the model
+    reads `inputs[:7]`).
 
     device: keep every view used (image, feature map, cameras) resident on that GPU after its first use and assemble the batch there;
     only the pose arrays (a few KB) cross PCIe per step.  The batches are bit-identical to the host path's (NumPy float32 arrays)."""
 
     def __init__(self, dataset, workspace_bounds, n_views=1, batch_size=1, shuffle=True, pose_augmentation_factor=1, n_future_poses=5,
-                 fixed_orientation=None, rotation_representation='quaternion', device=None):
+                 fixed_orientation=None, rotation_representation='quaternion', device=None, with_tokens=False):
         if rotation_representation not in ('quaternion', '6d'):
             raise ValueError('Unknown rotation representation: ' + rotation_representation)
         self.future_poses = n_future_poses
@@ -249,6 +294,7 @@ class LanguageDataGenerator:
         self.rotation_representation = rotation_representation
         self.device = torch.device(device) if device is not None else None
         self._resident = {}
+        self.with_tokens = with_tokens
         self.n_points_train = self.future_poses * self.pose_augmentation_factor
         if self.fixed_orientation is not None:
             self.n_negative = self.n_points_train - self.future_poses
@@ -293,7 +339,8 @@ class LanguageDataGenerator:
             ds, dev = self.dataset, self.device
             einv, k4 = camera_parameters(ds.cameras[i][p])
             host = ((ds.colors[i][p][..., :3] / 255.0).astype(np.float32), ds.feature_map(i, p), einv.astype(np.float32), k4.astype(np.float32))
-            self._resident[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in host)
+            self._resident[key] = tuple(a.to(dev) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                                        for a in host)
         return self._resident[key]
 
     def get_data_camera_device(self, batch, view_indices):
@@ -351,14 +398,19 @@ class LanguageDataGenerator:
             landscape, grad = ([torch.from_numpy(a).to(self.device) for a in arrays] for arrays in (landscape, grad))
         else:
             images, intrinsics, extrinsics_inv, features = self.get_data_camera(batch, view_indices)
-        inputs = [landscape[0], landscape[1], grad[0], grad[1], images, intrinsics, extrinsics_inv, None]
+        tokens = None
+        if self.with_tokens:
+            tokens = np.stack([self.dataset.tokens(i) for i in batch]).astype(np.int32)
+            if self.device is not None:
+                tokens = torch.from_numpy(tokens).to(self.device)
+        inputs = [landscape[0], landscape[1], grad[0], grad[1], images, intrinsics, extrinsics_inv, tokens]
         return (inputs, features), [landscape[2], grad[2], grad[3]]
 
 
-def get_inputs(dataset, sample_idx, n_images, device=None):
+def get_inputs(dataset, sample_idx, n_images, device=None, with_tokens=False):
     """utils/util.py:74-114: views 0-2 for n_images = 3, views 3-4 for n_images = 2 -> (input_data [images (1, n, H, W, 3),
-    intrinsics, extrinsics_inv (1, n, 4, 4), tokens (None)], features (1, n, H, W, 256), task_info, grasp_pose (4, 4)).  device: the
-    arrays as float32 tensors there (copied once; the validation passes then read them in place)."""
+    intrinsics, extrinsics_inv (1, n, 4, 4), tokens (None, or int32 (1, 77) with with_tokens)], features (1, n, H, W, 256), task_info,
+    grasp_pose (4, 4)).  device: the arrays as float32 tensors there (copied once; the validation passes then read them in place)."""
     if n_images == 2:
         views = range(3, 5)
     elif n_images == 3:
@@ -369,12 +421,19 @@ def get_inputs(dataset, sample_idx, n_images, device=None):
     observations = np.array([[dataset.colors[sample_idx][i][..., :3] / 255.0 for i in views]], dtype=np.float32)
     intrinsics = np.array([[c[1] for c in cams]], dtype=np.float32)
     extrinsics_inv = np.array([[c[0] for c in cams]], dtype=np.float32)
-    features = np.array([[dataset.feature_map(sample_idx, i) for i in views]], dtype=np.float32)
+    maps = [dataset.feature_map(sample_idx, i) for i in views]
+    tokens = dataset.tokens(sample_idx)[None].astype(np.int32) if with_tokens else None
     input_data = [observations, intrinsics, extrinsics_inv]
     if device is not None:
         input_data = [torch.from_numpy(a).to(device) for a in input_data]
-        features = torch.from_numpy(features).to(device)
-    return input_data + [None], features, dataset.task_info[sample_idx], dataset.grasp_poses[sample_idx]
+        if isinstance(maps[0], torch.Tensor):                                # an encoded dataset on a device: no host round trip
+            features = torch.stack([m.to(device=device, dtype=torch.float32) for m in maps])[None]
+        else:
+            features = torch.from_numpy(np.array([maps], dtype=np.float32)).to(device)
+        tokens = torch.from_numpy(tokens).to(device) if with_tokens else None
+    else:
+        features = np.array([maps], dtype=np.float32)
+    return input_data + [tokens], features, dataset.task_info[sample_idx], dataset.grasp_poses[sample_idx]
 
 
 # ---- validation (utils/optimization.py, utils/util.py) -----------------------------------------------------------------------------------
@@ -547,6 +606,9 @@ def main(argv=None):
     ap.add_argument('--size', default='32', help='image size: H or HxW (reference 480x640)')
     ap.add_argument('--n-scenes', type=int, default=16)
     ap.add_argument('--n-perspectives', type=int, default=5)
+    ap.add_argument('--encoder', default='none', choices=['none', 'v4'],
+                    help="where the feature maps come from: 'none' the synthetic bump map; 'v4' encoders.LanguageFeatureProducer "
+                         '(CombineCLIPVisualV4 on CLIP stand-ins) on each view and the tokens of its instruction')
     ap.add_argument('--host-batches', action='store_true', help='assemble batches in NumPy on the host (default: on the GPU)')
     args = ap.parse_args(argv)
     height, width = _size(args.size)
@@ -554,9 +616,15 @@ def main(argv=None):
     dev = 'cuda:0'
     train = SyntheticLanguageDataset(args.n_scenes, args.n_perspectives, height, width, bounds, seed=0)
     valid = SyntheticLanguageDataset(max(args.valid_samples) + 1, args.n_perspectives, height, width, bounds, seed=1)
+    with_tokens = args.encoder == 'v4'
+    if with_tokens:
+        from .encoders import LanguageFeatureProducer
+        producer = LanguageFeatureProducer((height, width)).to(dev)
+        train, valid = (EncodedLanguageDataset(d, producer, None if args.host_batches else dev) for d in (train, valid))
     generator = LanguageDataGenerator(train, bounds, n_views=args.n_views, batch_size=args.batch_size,
                                       pose_augmentation_factor=args.pose_augmentation_factor, n_future_poses=args.n_future_poses,
-                                      rotation_representation=args.rotation_representation, device=None if args.host_batches else dev)
+                                      rotation_representation=args.rotation_representation, device=None if args.host_batches else dev,
+                                      with_tokens=with_tokens)
     loss, softmax_before_loss = select_loss(args.loss)
     model = LanguageNeRF(np.zeros(NET_PARAMS, dtype=np.float32), n_points_train=args.pose_augmentation_factor * args.n_future_poses,
                          n_views=args.n_views, batch_size=args.batch_size, rotation_representation=args.rotation_representation,
@@ -576,7 +644,7 @@ def main(argv=None):
     optimizer = DNGFOptimizer(model, workspace_bounds=bounds, n_initial_guesses=args.n_initial_guesses, n_images=args.n_images,
                               clip_translation=True, rotation_representation=args.rotation_representation)
     optimizer.compile(graph=args.graph, fused=args.fused_validation)
-    valid_data = [get_inputs(valid, i, args.n_images, device=dev) for i in args.valid_samples]
+    valid_data = [get_inputs(valid, i, args.n_images, device=dev, with_tokens=with_tokens) for i in args.valid_samples]
     optimization_config = dict(n_optimization_steps=args.n_optimization_steps, init_lr_t=args.init_lr_t, init_lr_r=args.init_lr_r,
                                decay_t=args.decay_t, decay_r=args.decay_r)
     start = time.time()
