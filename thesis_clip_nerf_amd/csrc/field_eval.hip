@@ -282,33 +282,13 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * kWaves, kMultiView ? kMvOcc
     }
 }
 
-// ---- per-(view, ray) layer-0 seed: b0 + W0[60:120]^T PE(cam dir)  (the direction is constant along a ray) ----
-// One wavefront per (b*V+v, ray).  Output in accumulator order [h][nb][r] so the field kernel loads it like a bias.
+// ---- per-(view, ray) layer-0 seed (dir_seed_row, mvnerf_field_common.h): one wavefront per (b*V+v, ray) ----
 __global__ __launch_bounds__(256) void dir_bias_kernel(FieldParams p) {
     const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);          // over B*V*R
+    const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);          // over B*V*R
     if (row >= (long)p.B * p.V * p.R) return;
     const int bv = (int)(row / p.R);
-    const long ray = (long)(bv / p.V) * p.R + (row - (long)bv * p.R);
-    const float dx = p.rays_d[3 * ray + 0], dy = p.rays_d[3 * ray + 1], dz = p.rays_d[3 * ray + 2];
-    const float* E = p.einv + 16 * bv;
-    // lane m < 60 evaluates PE feature m = d*20 + 2k + f (nerf_utils.py:124 layout) of cam dir (Q3: w = 1)
-    const int m = lane < 60 ? lane : 59;
-    const int d = m / 20, k = (m % 20) >> 1, f = m & 1;
-    const float cd = row_dot4(E, d, dx, dy, dz, 1.0f);
-    float sv, cv;
-    sincos_f32(cd * (3.14159274101257324f * (float)(1 << k)), &sv, &cv);
-    const float mine = f ? cv : sv;
-    const float* wd = p.net + kPackW0Dir;
-    float a0 = p.net[kPackB0Plain + lane], a1 = p.net[kPackB0Plain + 64 + lane];
-    for (int mm = 0; mm < 60; ++mm) {
-        const float pv = __shfl(mine, mm);
-        a0 = fmaf(pv, wd[mm * 128 + lane], a0);
-        a1 = fmaf(pv, wd[mm * 128 + 64 + lane], a1);
-    }
-    float* out = p.dir_bias + 128 * row;
-    out[acc_slot(lane)] = a0;
-    out[acc_slot(64 + lane)] = a1;
+    dir_seed_row(p, bv, (int)(row - (long)bv * p.R), lane, p.net + kPackW0Dir);
 }
 
 // ---- texel table: T[b*V+v][y][x][.] = W0[123:379]^T features[b,v,y,x,:] in accumulator order [h][nb][r] ----
@@ -317,7 +297,13 @@ __global__ __launch_bounds__(256) void dir_bias_kernel(FieldParams p) {
 // runs 32 steps of 4 k-steps: A = feature groups 8..39 of the packed layer-0 kernel (chunk (g, nb)), B = channels
 // 8q + 4h + {0..3} of this lane's texel.  Two accumulators alternate so consecutive MFMAs do not depend on each other.
 // A second net (net1 / table1, workgroups of 8 waves) shares the staged rows: coarse and fine tables from ONE read of
-// the feature maps.
+// the feature maps.  Split form (gridDim.y == 2, workgroups of 4 waves): workgroup (x, y) projects net y and stages the rows
+// for itself - the launcher's choice while the shared form would leave compute units without a workgroup; every wave runs the
+// same MFMA sequence in both forms.
+// kHoist (the launcher's choice for maps of fewer blocks than compute units, where a wave has its SIMD to itself): the wave's 32 A
+// chunks are requested in front of the stage and held in 128 registers; otherwise they are read four steps ahead inside the MFMA run
+// (56 registers: a large map keeps four 8-wave workgroups per compute unit, whose stages and stores overlap each other's MFMAs).
+template <bool kHoist>
 __global__ __launch_bounds__(512) void project_texels_kernel(const float* __restrict__ features,
                                                              const float* __restrict__ net0, const float* __restrict__ net1,
                                                              long n_texels, float* __restrict__ table0,
@@ -326,11 +312,20 @@ __global__ __launch_bounds__(512) void project_texels_kernel(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nb = wv & 3;
-    const float* net = wv < 4 ? net0 : net1;
-    float* table = wv < 4 ? table0 : table1;
+    const bool second = wv >= 4 || blockIdx.y != 0;
+    const float* net = second ? net1 : net0;
+    float* table = second ? table1 : table0;
     const long t0 = (long)blockIdx.x * 32;
     const f32x4* fsrc = reinterpret_cast<const f32x4*>(features);
     const int nthreads = blockDim.x;
+    // the wave's 32 A chunks (32 KiB of the packed layer-0 kernel, one float4 per lane and step) do not depend on the staged rows:
+    // kHoist requests all of them here, so that the MFMA run below waits for memory once and not once per group of steps
+    const f32x4* w = reinterpret_cast<const f32x4*>(net) + ((long)kL0GroupFeat * 4 + nb) * 64 + lane;
+    f32x4 a[kHoist ? 32 : 1];
+    if (kHoist) {
+#pragma unroll
+        for (int q = 0; q < 32; ++q) a[q] = w[(long)q * 256];
+    }
     for (int m = 0; m < 2048 / nthreads; ++m) {
         const int idx = tid + nthreads * m;                 // float4 index inside the 32 x 64 block
         const int row = idx >> 6, chunk = idx & 63;
@@ -339,16 +334,23 @@ __global__ __launch_bounds__(512) void project_texels_kernel(const float* __rest
         srow[row * 64 + (chunk ^ (row & 15))] = fsrc[t * 64 + chunk];
     }
     __syncthreads();
-    const f32x4* w = reinterpret_cast<const f32x4*>(net) + ((long)kL0GroupFeat * 4 + nb) * 64 + lane;
     f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         acc0[r] = 0.0f;
         acc1[r] = 0.0f;
     }
-#pragma unroll 4
+    constexpr int kUnrollSteps = kHoist ? 16 : 4;
+#pragma unroll kUnrollSteps
     for (int q = 0; q < 32; q += 2) {
-        const f32x4 a0 = w[(long)q * 256], a1 = w[(long)(q + 1) * 256];
+        f32x4 a0, a1;
+        if constexpr (kHoist) {
+            a0 = a[q];
+            a1 = a[q + 1];
+        } else {
+            a0 = w[(long)q * 256];
+            a1 = w[(long)(q + 1) * 256];
+        }
         const f32x4 b0 = srow[j * 64 + ((2 * q + h) ^ (j & 15))], b1 = srow[j * 64 + ((2 * q + 2 + h) ^ (j & 15))];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -370,8 +372,18 @@ __global__ __launch_bounds__(512) void project_texels_kernel(const float* __rest
 
 hipError_t launch_project_texels(const float* features, const float* packed_net, const float* packed_net1, long n_texels,
                                  float* table, float* table1, hipStream_t stream) {
-    hipLaunchKernelGGL(project_texels_kernel, dim3((unsigned)((n_texels + 31) / 32)), dim3(packed_net1 ? 512 : 256), 0, stream,
-                       features, packed_net, packed_net1, n_texels, table, table1);
+    static DeviceSetup setup;
+    int cus = 0;
+    hipError_t e = device_setup(setup, {}, &cus);
+    if (e != hipSuccess) return e;
+    const long blocks = (n_texels + 31) / 32;
+    // two nets on a small map: the shared stage would occupy `blocks` compute units with two waves per SIMD queueing on one matrix
+    // pipe and leave the others idle; one 4-wave workgroup per (block, net) reads the rows twice (L2) and uses twice as many units.
+    // From `cus` blocks on the feature rows are the traffic and the stage stays shared.
+    const bool small = blocks < cus, split = packed_net1 && small;
+    const dim3 grid((unsigned)blocks, split ? 2 : 1), block(packed_net1 && !split ? 512 : 256);
+    if (small) hipLaunchKernelGGL(project_texels_kernel<true>, grid, block, 0, stream, features, packed_net, packed_net1, n_texels, table, table1);
+    else hipLaunchKernelGGL(project_texels_kernel<false>, grid, block, 0, stream, features, packed_net, packed_net1, n_texels, table, table1);
     return hipGetLastError();
 }
 

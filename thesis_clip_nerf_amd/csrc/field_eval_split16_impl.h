@@ -36,6 +36,7 @@
 //                  fp32 range).
 #include <hip/hip_runtime.h>
 
+#include "mvnerf_field_common.h"
 #include "mvnerf_kernels.h"
 #include "mvnerf_launch.h"
 #include "mvnerf_math.h"
@@ -79,8 +80,6 @@ using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
-// read-only kernel inputs at a wave-uniform address, read through the constant address space: scalar loads
-using cfloat = const __attribute__((address_space(4))) float;
 
 // ---- weight stream: 1 KiB chunks [lane][8 bf16]; chunk = 24 * kstep + 3 * rb + piece ------------------------------------
 //   k-steps 0..1  : layer 0, PE(cam xyz) + rgb: lane group g, slot e = 8 t + jj (16 slots per group)
@@ -262,13 +261,15 @@ __device__ __forceinline__ int ring16_start_chunk(int p, int V, int l0_units) {
 // `slot`: three wave-instructions per wave, each moving 1 KiB (lane l: 16 bytes at wave base + 16 l); wave w of the 8 covers bytes
 // [1024 w, 1024 w + 1024) of each 8 KiB third.  The source is a scalar base plus the lane's constant 32-bit offset (the instruction's
 // saddr form): no 64-bit vector address arithmetic per k-step.
+constexpr int kR16DmaRequests = 3;           // wave-instructions per wave and position (what a vmcnt count of "one position" is)
 __device__ __forceinline__ void ring16_dma(const Ring16& r, int start, int slot) {
     const unsigned char* src = reinterpret_cast<const unsigned char*>(r.w) + (unsigned)start;
     const int dst = (int)(unsigned long)(__attribute__((address_space(3))) unsigned char*)r.lds + slot + r.wave_off;
     // (inline asm: through the builtin the compiler widens the lane offset to 64 bits and adds it on the vector ALU per request; s_nop:
     // the M0 write must be one instruction away from the request that reads it.  M0 is declared clobbered.)
+    static_assert(kR16DmaRequests * 8192 == kS16SlotChunks * 1024, "a position is kR16DmaRequests requests of 8 KiB (8 waves x 1 KiB)");
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < kR16DmaRequests; ++i)
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(r.lane_off), "s"(src + 8192 * i), "s"(dst + 8192 * i) : "memory", "m0");
 }
 
@@ -561,11 +562,50 @@ __global__ __launch_bounds__(512, 2) void MVS16_KERNEL(FieldParams p, const f32x
     __syncthreads();                                                        // the position table is written
     ring.lane_off = 16 * tid;
     ring.wave_off = 1024 * wave;
+    // The plain single-view inference variants form the layer-0 seed rows of their own rays here instead of a dir_bias_kernel launch in
+    // front of every field launch.  The 32 KiB of the packed net from W0_dir on (the 60 rows, b0 behind them) go into the gather stages -
+    // free until the first gather - by LDS-DMA, requested in front of the ring's first two positions: the rows are formed while those land.
+    constexpr bool kSeedHere = !kMultiView && !kAux && !kStash;
+    float* seed_w = reinterpret_cast<float*>(smem_s16 + kRingBytes);
+    if (kSeedHere) {
+        static_assert(kPackTotal - kPackW0Dir >= 8192 && kPackB0Plain + 128 - kPackW0Dir <= 8192 && kW * 32 * kS16StageRowBytes >= 32768,
+                      "four 8 KiB requests: inside the packed net, covering W0_dir and b0, inside the gather stages");
+        const unsigned char* src = reinterpret_cast<const unsigned char*>(p.net + kPackW0Dir);
+        const int dst = (int)(unsigned long)(__attribute__((address_space(3))) unsigned char*)seed_w + ring.wave_off;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(ring.lane_off), "s"(src + 8192 * i), "s"(dst + 8192 * i) : "memory", "m0");
+    }
     ring16_dma(ring, __builtin_amdgcn_readfirstlane(table[0]), ring.cur);   // prologue: positions 0 and 1
     ring16_dma(ring, __builtin_amdgcn_readfirstlane(table[1]), ring.nxt);
     ring.start_pf = table[2];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // all but the requests of the ring's two positions, issued last: the four above (requests return in order)
+    if (kSeedHere) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * kR16DmaRequests) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if (kSeedHere) {
+        // Every ray that a tile of this workgroup's groups touches (a group = 256 consecutive samples, clamped to the last one as the
+        // tiles clamp), dealt to the eight waves in turn, one row per wavefront (dir_seed_row: the arithmetic of dir_bias_kernel).  A ray
+        // whose samples lie in two groups is formed by both workgroups - the same bits to the same address - and each workgroup reads
+        // only behind its own stores: every wave drains them (vmcnt(0)) in front of the barrier, the reads miss the compute unit's L1
+        // (no line of p.dir_bias is in it before) - no fence wider than the workgroup.
+        const unsigned last_sample = (unsigned)p.total - 1u, S = (unsigned)p.S, R = (unsigned)p.R;
+        const int groups = ((int)p.n_tiles + kW - 1) / kW;
+        int turn = 0;
+#pragma unroll 1
+        for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+            const unsigned first = (unsigned)grp * (32u * kW), end = first + (32u * kW - 1u);
+            const int ray_hi = __builtin_amdgcn_readfirstlane((int)((end < last_sample ? end : last_sample) / S));
+#pragma unroll 1
+            for (int ray = __builtin_amdgcn_readfirstlane((int)(first / S)); ray <= ray_hi; ++ray, ++turn)
+                if ((turn & (kW - 1)) == wave) {
+                    const int b = __builtin_amdgcn_readfirstlane((int)((unsigned)ray / R));
+                    dir_seed_row(p, b, ray - b * (int)R, lane, seed_w);
+                }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // the rows are stored, the ring's two positions have landed
+        __syncthreads();
+    }
 #pragma unroll
     for (int q = 0; q < 3; ++q) ring.a0[q] = __builtin_bit_cast(u32x4, ring16_cur(ring)[q * 64 + lane]);
 
@@ -1039,8 +1079,10 @@ hipError_t MVS16_LAUNCH_FN(const FieldParams& p, const void* packed_split16, hip
                                         {&MVS16_KERNEL<false, false, false, true>, lds_bytes}, {&MVS16_KERNEL<false, true, false, true>, lds_bytes},
                                         {&MVS16_KERNEL<true, false, false, true>, lds_bytes}, {&MVS16_KERNEL<true, true, false, true>, lds_bytes}}, &cus);
     if (e != hipSuccess) return e;
-    if ((e = launch_dir_bias(p, stream)) != hipSuccess) return e;
     const bool mv = p.V > 1;
+    const bool aux = p.tap_idx || p.pix || p.embedding || p.acts_view || p.acts_fused;
+    // the plain single-view inference variants form their seed rows themselves (kSeedHere); every other one reads dir_bias_kernel's
+    if ((mv || aux || p.stash) && (e = launch_dir_bias(p, stream)) != hipSuccess) return e;
     const long n_groups = (p.n_tiles + 7) / 8;
     const long resident = (long)cus;                                        // persistent: one workgroup per CU
     const unsigned wgs = (unsigned)(n_groups < resident ? n_groups : resident);
@@ -1051,7 +1093,6 @@ hipError_t MVS16_LAUNCH_FN(const FieldParams& p, const void* packed_split16, hip
 #else
 #define MVS16_LAUNCH(MV, PROJ, AUX, STASH) hipLaunchKernelGGL((MVS16_KERNEL<MV, PROJ, AUX, STASH>), grid, block, lds_bytes, stream, p, w)
 #endif
-    const bool aux = p.tap_idx || p.pix || p.embedding || p.acts_view || p.acts_fused;
     if (p.stash && p.V > 1 && ((long)p.R * p.S) % 32 != 0) return hipErrorInvalidValue;     // tiles must not straddle scenes
     if (p.stash) {
         const int variant = (mv ? 2 : 0) + (p.texel_table ? 1 : 0);

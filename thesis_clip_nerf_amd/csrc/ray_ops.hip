@@ -165,10 +165,18 @@ hipError_t launch_composite(const float* z, const float* rgbs, int n_rays, int S
     return hipGetLastError();
 }
 
+// per-lane predicate -> wave-wide mask (the compare writes it straight into a scalar register pair), and r += 1 in the lanes of a
+// mask: the mask is the carry-in of one add
+__device__ __forceinline__ unsigned long long lanes_where(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
+__device__ __forceinline__ void count_lanes(int& r, unsigned long long mask) {
+    asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(r) : "s"(mask) : "vcc");
+}
+
 // ---- a13/a14: sample_pdf (nerf_utils.py:143-176) + sort-merge (model_v0.py:150-156), S = 64 ----
 // The sums that decide the integer outputs (w_sum, cdf) are strictly sequential in fp32, as in the
-// oracle: every lane runs the same 62-step loop over wave-private LDS (broadcast reads), so all
-// lanes hold bit-identical values.  `above` is the reference's tf.scan: a count of cdf_j <= u.
+// oracle: every lane runs the same 62-step w_sum loop over wave-private LDS (broadcast reads), so all
+// lanes hold bit-identical values; the cdf's prefix sums are run by lane 0 and handed on through LDS.
+// `above` is the reference's tf.scan: a count of cdf_j <= u.
 // Core of sample_pdf for one ray on one wavefront.  On entry bins[0..62] and pdf[0..61] (= weights +
 // 1e-5) are in wave-private LDS and fenced; lane l draws the sample for uniform u.
 __device__ __forceinline__ float sample_pdf_core(const float* bins, float* pdf, float* cdf, int lane, float u,
@@ -180,12 +188,14 @@ __device__ __forceinline__ float sample_pdf_core(const float* bins, float* pdf, 
     lds_fence();
     if (lane < NW) pdf[lane] = pdf[lane] / wsum;
     lds_fence();
-    float run = 0.0f, mycdf = 0.0f;
-    for (int k = 0; k < NW; ++k) {                                   // cdf_j = sum_{k<j} pdf_k, sequential
-        run = run + pdf[k];
-        if (lane == k + 1) mycdf = run;
+    if (lane == 0) {                                                 // cdf_j = sum_{k<j} pdf_k, sequential: one lane runs the sum and
+        float run = 0.0f;                                            // stores every prefix (a store is no vector-ALU instruction; a
+        cdf[0] = 0.0f;                                               // select per step and lane is)         cdf_0 = 0 (:149)
+        for (int k = 0; k < NW; ++k) {
+            run = run + pdf[k];
+            cdf[k + 1] = run;
+        }
     }
-    if (lane < NB) cdf[lane] = mycdf;                                // cdf_0 = 0 (:149)
     lds_fence();
 
     above = 0;
@@ -214,7 +224,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
                                                        int32_t* __restrict__ below_out,
                                                        int32_t* __restrict__ rank_out) {
     constexpr int S = 64, NB = 63, NW = 62;
-    __shared__ float lds[kRaysPerWG][7 * 64];
+    __shared__ __attribute__((aligned(16))) float lds[kRaysPerWG][7 * 64];
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     const int ray = blockIdx.x * kRaysPerWG + wv;
@@ -242,11 +252,24 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
     // ascending sort of the 128 depths (tf.sort, model_v0.py:156) by rank; ties broken by index
     vals[64 + lane] = zf;
     lds_fence();
+    // rank = number of elements in front in the (value, index) order: element k precedes element i when vk < vi, or vk == vi and
+    // k < i.  Every compare is one wave-wide mask (lane = i); `k < i` is a constant mask per k, so a coarse depth against a coarse
+    // one (and a fine against a fine) costs two compares, a coarse depth against a fine one - always the lower index - one `<=`, a
+    // fine against a coarse one `<`.  The depths arrive four per LDS broadcast read.
     int r0 = 0, r1 = 0;
-    for (int k = 0; k < 128; ++k) {
-        const float vk = vals[k];
-        r0 += (vk < zi || (vk == zi && k < lane)) ? 1 : 0;
-        r1 += (vk < zf || (vk == zf && k < 64 + lane)) ? 1 : 0;
+    const f32x4* vals4 = reinterpret_cast<const f32x4*>(vals);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const f32x4 vc = vals4[q], vf = vals4[16 + q];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int k = 4 * q + e;
+            const unsigned long long behind = k < 63 ? ~0ull << (k + 1) : 0ull;          // lanes i > k
+            count_lanes(r0, lanes_where(vc[e] < zi) | (lanes_where(vc[e] == zi) & behind));
+            count_lanes(r1, lanes_where(vc[e] <= zf));
+            count_lanes(r0, lanes_where(vf[e] < zi));
+            count_lanes(r1, lanes_where(vf[e] < zf) | (lanes_where(vf[e] == zf) & behind));
+        }
     }
     sorted[r0] = zi;
     sorted[r1] = zf;
