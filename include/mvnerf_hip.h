@@ -421,6 +421,44 @@ int mvnerf_query_vjp(const float* points, const float* dirs, const float* images
                      const float* g_acts, int B, int V, int N, int H, int W, void* scratch, float* d_points, float* d_dirs,
                      mvnerf_stream_t stream);
 
+/* ---- The same field with its hidden layers on the bf16 matrix pipe (bf16 weights and MFMA inputs, fp32 accumulate: BASELINE.json
+ * config 3), for consumers that wait on the trunk's input gradient at inference time (DNGFOptimizer.optimize_pose,
+ * lmvnerf/grasp_optimizer.py:158-184, through LanguageNeRF._call, lmvnerf/model_v4.py:208-265).  The frozen trunk's backward needs one
+ * thing from the forward, the sign of each pre-activation (ResNetMLPBlock, layers.py:229-231: relu in front of both Dense layers), so the
+ * forward keeps 1 bit where mvnerf_field_eval_stash keeps an fp32 value.
+ *
+ * relu_bits: mvnerf_relu_bits_bytes(B,V,N) bytes, 16-byte aligned.  One bit per pre-activation, [fp32 accumulator > 0], for the 6 per-view
+ *   tensors x0,h1,x1,h2,x2,h3 (the mvnerf_stash_bytes slots without x3) and the 6 fused tensors mean,h4,x4,h5,x5,h6 (without x6).
+ *   64-bit words [view tile (b V + v) tiles_per_b + k][6][64], then [tile b tiles_per_b + k][6][64]; a tile is 32 consecutive points.
+ *   Word `lane` = (j = lane % 32, h = lane / 32) of a (tile, tensor) belongs to point j of the tile; its bit 16 nb + r is feature
+ *   32 nb + 8 (r / 4) + 4 h + r % 4: the accumulator register r of output block nb that lane holds in both kernels.
+ * mvnerf_pack_bwd_streams_bf16: the twelve hidden kernels transposed, each fp32 weight rounded once to the nearest-even bf16 (the values of
+ *   mvnerf_pack_net_bf16), as the A-operand stream of the backward walk: 32 KiB per layer, block 5 (second Dense, first Dense), 4, ... 0.
+ * mvnerf_query_stash_bf16: the forward; acts (4,B,N,128) = view mean, u1, u2, u3 as rows, relu_bits as above.  packed16:
+ *   mvnerf_pack_net_bf16; workspace: mvnerf_query_workspace_bytes(B,V,N).
+ * mvnerf_trunk_vjp_bf16: cotangents g_acts (4,B,N,128) -> g0_tl = dL/d(layer-0 output) in tile layout [view tile][128][32]
+ *   (mvnerf_query_vjp_bf16_scratch_bytes(B,V,N) bytes), one launch.  Per block, walking backwards: g_rh = bf16(g) W2^T,
+ *   g_hid = g_rh o bits(h), g_x = g + (bf16(g_hid) W1^T) o bits(x), accumulation and residual add in fp32; the cotangents of u3, u2, u1
+ *   and the mean enter in fp32 where those tensors are produced (the order of mvnerf_query_vjp); the mean's goes to each view as g / V
+ *   (reduce_mean, layers.py:368-370).
+ * mvnerf_query_vjp_bf16: that launch followed by the fp32 layer-0 pass of mvnerf_query_vjp (bwd_streams: mvnerf_pack_bwd_streams, of which
+ *   only the layer-0 slabs are read) -> d_points, d_dirs (B,N,3).
+ * All three: N % 32 == 0 when V > 1, at most 262143 view tiles.  No gradient of the gradient: the second derivative stays fp32
+ *   (mvnerf_query_jvp). */
+size_t mvnerf_relu_bits_bytes(int B, int V, int N);
+size_t mvnerf_bwd_streams_bf16_bytes(void);
+int mvnerf_pack_bwd_streams_bf16(const float* net_keras, void* bwd16, mvnerf_stream_t stream);
+int mvnerf_query_stash_bf16(const float* points, const float* dirs, const float* images, const float* features, const float* intrinsics,
+                            const float* extrinsics_inv, const float* packed_net, const void* packed16, int B, int V, int N, int H, int W,
+                            float* acts, void* relu_bits, void* workspace, mvnerf_stream_t stream);
+int mvnerf_trunk_vjp_bf16(const void* bwd16, const void* relu_bits, const float* g_acts, int B, int V, int N, float* g0_tl,
+                          mvnerf_stream_t stream);
+size_t mvnerf_query_vjp_bf16_scratch_bytes(int B, int V, int N);
+int mvnerf_query_vjp_bf16(const float* points, const float* dirs, const float* images, const float* features, const float* intrinsics,
+                          const float* extrinsics_inv, const float* bwd_streams, const void* bwd16, const void* relu_bits,
+                          const float* g_acts, int B, int V, int N, int H, int W, void* scratch, float* d_points, float* d_dirs,
+                          mvnerf_stream_t stream);
+
 /* The four fused activations (view mean, u1, u2, u3 - layers.py:376-377, what LanguageNeRF._call keeps as outputs[4:],
  * lmvnerf/model_v4.py:261-262) of a stash written by mvnerf_field_eval_stash with R = N, S = 1, as row-major acts (4, B*N, 128):
  * the stash holds them in the tile layout [tile][feature][32 points]; one transposing pass through LDS.  acts 16-byte aligned. */
@@ -589,6 +627,16 @@ int mvnerf_grasp_success_and_gradients(const mvnerf_grasp_call* call, mvnerf_str
 /* Stages 1-8: the above followed by mvnerf_pose_adam_step on t, rot (arguments as there; cfg is [host]). */
 int mvnerf_grasp_opt_step(const mvnerf_grasp_call* call, const mvnerf_pose_adam_config* cfg, const int* train_flags, int* counters, float* m_t,
                           float* v_t, float* m_r, float* v_r, mvnerf_stream_t stream);
+
+/* The same three calls with the trunk on the bf16 matrix pipe (DNGFOptimizer.optimize_pose, lmvnerf/grasp_optimizer.py:158-184, under
+ * BASELINE.json config 3): stage 2 is mvnerf_query_stash_bf16, stage 6 mvnerf_query_vjp_bf16, everything else as above.  The call is the
+ * same struct (`split` is not read and may be NULL); packed16: mvnerf_pack_net_bf16, bwd16: mvnerf_pack_bwd_streams_bf16, both 16-byte
+ * aligned.  workspace: mvnerf_grasp_workspace_bytes_bf16 (relu bits in place of the stash). */
+size_t mvnerf_grasp_workspace_bytes_bf16(int B, int V, int P, int n5);
+int mvnerf_grasp_success_bf16(const mvnerf_grasp_call* call, const void* packed16, const void* bwd16, mvnerf_stream_t stream);
+int mvnerf_grasp_success_and_gradients_bf16(const mvnerf_grasp_call* call, const void* packed16, const void* bwd16, mvnerf_stream_t stream);
+int mvnerf_grasp_opt_step_bf16(const mvnerf_grasp_call* call, const void* packed16, const void* bwd16, const mvnerf_pose_adam_config* cfg,
+                               const int* train_flags, int* counters, float* m_t, float* v_t, float* m_r, float* v_r, mvnerf_stream_t stream);
 
 /* ---- the losses of LanguageNeRF.train_step (lmvnerf/model_v4.py:277-318) with their cotangents.  One workgroup each, fixed-order sums, no
  * atomics: the same bits from run to run. ---- */

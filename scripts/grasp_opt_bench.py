@@ -12,7 +12,16 @@ Usage: python scripts/grasp_opt_bench.py [--poses 4096] [--images 3] [--size 480
 --step: which step runs - torch (stage 4 as torch modules + autograd, the default) and / or fused (compile(fused=True): the whole step
 one call of mvnerf_grasp_opt_step).  With both, the four legs (torch / fused x eager / graph) alternate inside every round of one process;
 the fused legs report as step_fused_eager_ms / step_fused_graph_ms.
---trace N: only N eager steps of the first --step leg after two warm-up steps (for rocprofv3 --kernel-trace: calls / N = launches per step)."""
+--trace N: only N eager steps of the first --step leg after two warm-up steps (for rocprofv3 --kernel-trace: calls / N = launches per step).
+--compute-dtype bf16: the A/B of DESIGN.md 12.2 instead of the report above - the fused fp32 step and the fused bf16 step (trunk forward
+with relu bits + trunk VJP on the bf16 MFMA) in this one process, both warmed up, in alternating rounds; the trunk stages alone for both;
+rel-L2 of success, g_t, g_rot between the two on the same poses.  Writes profiles/grasp_bf16_bench.json (--out) and exits with status 1
+unless the bf16 step is faster by more than the spread of the rounds.  With --trace the traced leg uses that compute dtype.
+--merge-traces F32_DIR BF16_DIR: no GPU work - reads the *_kernel_trace.csv that two runs of their own
+(rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/grasp_opt_bench.py --step fused --compute-dtype DT --trace N)
+left in the two directories and adds the per-kernel split, microseconds per step, to the JSON of --out."""
+import csv
+import glob
 import argparse
 import json
 import os
@@ -36,7 +45,42 @@ ap.add_argument('--steps', type=int, default=16, help='n_optimization_steps per 
 ap.add_argument('--reps', type=int, default=10, help='timed steps per leg')
 ap.add_argument('--trace', type=int, default=0)
 ap.add_argument('--step', nargs='+', choices=['torch', 'fused'], default=['torch'], help='step legs to time (alternating rounds)')
+ap.add_argument('--compute-dtype', choices=['f32', 'bf16'], default='f32')
+ap.add_argument('--rounds', type=int, default=7, help='alternating rounds of the --compute-dtype bf16 A/B')
+ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'grasp_bf16_bench.json'))
+ap.add_argument('--merge-traces', nargs=2, metavar=('F32_DIR', 'BF16_DIR'))
 args = ap.parse_args()
+
+
+def kernel_split(trace_dir):
+    """{kernel: [launches per step, us per step]} over the steps of a --trace run (its two warm-up steps included)."""
+    acc, steps = {}, 0
+    for path in glob.glob(os.path.join(trace_dir, '**', '*_kernel_trace.csv'), recursive=True):
+        for r in csv.DictReader(open(path)):
+            name = r['Kernel_Name'].replace('(anonymous namespace)::', '').split('(')[0].replace('void ', '')
+            calls, ns = acc.get(name, (0, 0))
+            acc[name] = (calls + 1, ns + int(r['End_Timestamp']) - int(r['Start_Timestamp']))
+    steps = acc.get('mvnerf::pose_adam_step_kernel', (0, 0))[0]          # one launch per step
+    if not steps:
+        raise SystemExit(f'{trace_dir}: no kernel trace of a grasp step')
+    return steps, {k: [round(c / steps, 2), round(ns / steps / 1e3, 2)] for k, (c, ns) in sorted(acc.items(), key=lambda kv: -kv[1][1])
+                   if k.startswith('mvnerf::')}
+
+
+if args.merge_traces:
+    with open(args.out) as f:
+        res = json.load(f)
+    for dt, d in zip(('f32', 'bf16'), args.merge_traces):
+        steps, split = kernel_split(d)
+        res[f'kernels_{dt}'] = {'traced_steps': steps, 'launches_and_us_per_step': split,
+                                'sum_us_per_step': round(sum(v[1] for v in split.values()), 1)}
+    res['kernels_note'] = ('per kernel of libmvnerf_hip.so: [launches per step, microseconds per step] from rocprofv3 --kernel-trace runs of '
+                           'their own (eager fused steps, two of them warm-up); the step times above come from the run without a profiler')
+    with open(args.out, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+    print(json.dumps({k: res[k] for k in ('kernels_f32', 'kernels_bf16')}))
+    sys.exit(0)
 dev = torch.device('cuda:0')
 h, w = args.size
 P, NI = args.poses, args.images
@@ -52,8 +96,9 @@ torch.manual_seed(0)
 model = LanguageNeRF(sc['fine'], n_views=1, rotation_representation='6d', device=dev)
 
 
-def optimiser(graph, fused=False):
-    opt = DNGFOptimizer(model, BOUNDS, n_initial_guesses=P, n_images=NI, clip_translation=True, rotation_representation='6d')
+def optimiser(graph, fused=False, compute_dtype='f32'):
+    opt = DNGFOptimizer(model, BOUNDS, n_initial_guesses=P, n_images=NI, clip_translation=True, rotation_representation='6d',
+                        compute_dtype=compute_dtype)
     opt.compile(graph=graph, fused=fused)
     opt.set_initial_guesses([g[:1] for g in opt.generate_initial_guesses(rng=np.random.default_rng(0))])
     opt.bind(inputs, feats)
@@ -71,15 +116,84 @@ def timed(fn, reps):
 
 
 if args.trace:
-    opt = optimiser(False, args.step[0] == 'fused')
+    opt = optimiser(False, args.step[0] == 'fused', args.compute_dtype)
     for _ in range(2):
         opt.optimize_pose(inputs, feats, [True, False])
     torch.cuda.synchronize()
     for i in range(args.trace):
         opt.optimize_pose(inputs, feats, [i % 2 == 0, i % 2 == 1])
     torch.cuda.synchronize()
-    print(json.dumps({'trace_steps': args.trace, 'step': args.step[0], 'poses': P, 'images': NI}))
+    print(json.dumps({'trace_steps': args.trace, 'step': args.step[0], 'compute_dtype': args.compute_dtype, 'poses': P, 'images': NI}))
     sys.exit(0)
+
+
+def rel_l2(a, b):
+    return float((a.double() - b.double()).norm() / b.double().norm())
+
+
+def bf16_ab():
+    """Fused fp32 step against fused bf16 step, one process, alternating rounds."""
+    n5 = model.n_transforms_to_check
+    res = {'poses': P, 'images': NI, 'views': 1, 'size': [h, w], 'rotation': '6d', 'query_points_per_step': NI * P * n5, 'reps': args.reps,
+           'rounds': args.rounds}
+    opts = {dt: optimiser(False, True, dt) for dt in ('f32', 'bf16')}
+    # the same poses through both: what the bf16 trunk changes in one step's outputs
+    out = {}
+    for dt, opt in opts.items():
+        s, g_t, g_r = opt.success_and_gradients()
+        out[dt] = (s.clone(), g_t.clone(), g_r.clone())
+    for i, name in enumerate(('success', 'g_t', 'g_rot')):
+        res[f'rel_l2_{name}_bf16_vs_f32'] = rel_l2(out['bf16'][i], out['f32'][i])
+    for opt in opts.values():                                # warm-up: every kernel loaded, every buffer sized
+        for _ in range(3):
+            opt.optimize_pose(inputs, feats, [True, False])
+    rounds = {dt: [] for dt in opts}
+    for _ in range(args.rounds):
+        for dt, opt in opts.items():
+            rounds[dt].append(timed(lambda: opt.optimize_pose(inputs, feats, [True, False]), args.reps))
+    for dt, v in rounds.items():
+        res[f'step_fused_{dt}_ms'] = float(np.median(v))
+        res[f'step_fused_{dt}_ms_rounds'] = [round(x, 4) for x in v]
+        res[f'step_fused_{dt}_ms_spread'] = float(max(v) - min(v))
+    # the two trunk stages alone, on the bound query points of each optimiser
+    for dt, opt in opts.items():
+        bd, st = opt._bound, opt._bound['state']
+        g_acts = torch.randn((4, NI, bd['ld'], 128), generator=gen, device=dev).mul_(1e-3)
+        if dt == 'bf16':
+            fwd = lambda: ops.query_stash_bf16(bd['points'], bd['dirs'], *st.geo, st.packed, st.packed16, relu_bits=bd['stash'])
+            vjp = lambda: ops.query_vjp_bf16(bd['points'], bd['dirs'], *st.geo, st.bwd_streams, st.bwd16, bd['stash'], g_acts)
+            g0 = lambda: ops.trunk_vjp_bf16(st.bwd16, bd['stash'], g_acts, 1)
+        else:
+            def fwd():
+                ops.query_stash(bd['points'], bd['dirs'], *st.geo, st.packed, stash=bd['stash'], packed_split=st.packed_split)
+                ops.stash_fused_acts(bd['stash'], NI, 1, bd['ld'])
+            vjp = lambda: ops.query_vjp(bd['points'], bd['dirs'], *st.geo, st.bwd_streams, bd['stash'], g_acts)
+            g0 = None
+        for name, fn in (('trunk_fwd', fwd), ('trunk_vjp', vjp), ('trunk_vjp_hidden_layers', g0)):
+            if fn is not None:
+                fn()
+                res[f'{name}_{dt}_ms'] = timed(fn, args.reps)
+        res[f'stash_bytes_{dt}'] = int(bd['stash'].numel())
+        res[f'grasp_workspace_bytes_{dt}'] = ops.grasp_workspace_bytes(NI, 1, P, n5, bf16=dt == 'bf16')
+    gap = res['step_fused_f32_ms'] - res['step_fused_bf16_ms']
+    spread = max(res['step_fused_f32_ms_spread'], res['step_fused_bf16_ms_spread'])
+    res['step_f32_over_bf16'] = res['step_fused_f32_ms'] / res['step_fused_bf16_ms']
+    res['gap_ms'], res['spread_ms'] = gap, spread
+    res['bf16_faster_beyond_spread'] = bool(gap > spread)
+    res['stages_note'] = ('trunk_fwd_f32 = query_stash + stash_fused_acts (the stash and the re-layout that hands the activations on as rows); '
+                          'trunk_fwd_bf16 = query_stash_bf16 alone (it writes rows and relu bits); trunk_vjp_* = the whole input gradient '
+                          'incl. the fp32 layer-0 pass; trunk_vjp_hidden_layers_bf16 = trunk_vjp_bf16_kernel alone.  The stages the two steps '
+                          'share (pose kernels, head, tail, Adam) are in the per-kernel split (kernels_*), merged from trace runs.')
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+    print(json.dumps(res))
+    return 0 if res['bf16_faster_beyond_spread'] else 1
+
+
+if args.compute_dtype == 'bf16':
+    sys.exit(bf16_ab())
 
 n_query = NI * P * model.n_transforms_to_check
 res = {'poses': P, 'images': NI, 'views': 1, 'size': [h, w], 'rotation': '6d', 'query_points_per_step': n_query}

@@ -88,6 +88,13 @@ SIGNATURES = {
     'mvnerf_query_jvp': (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p] * 4),
     'mvnerf_query_vjp_scratch_bytes': (c_size_t, [c_int] * 3),
     'mvnerf_query_vjp': (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p] * 4),
+    'mvnerf_relu_bits_bytes': (c_size_t, [c_int] * 3),
+    'mvnerf_bwd_streams_bf16_bytes': (c_size_t, []),
+    'mvnerf_pack_bwd_streams_bf16': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'mvnerf_query_stash_bf16': (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_void_p] * 4),
+    'mvnerf_trunk_vjp_bf16': (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 2),
+    'mvnerf_query_vjp_bf16_scratch_bytes': (c_size_t, [c_int] * 3),
+    'mvnerf_query_vjp_bf16': (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p] * 4),
     'mvnerf_stash_fused_acts': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'mvnerf_texel_table_bytes': (c_size_t, [c_int] * 4),
     'mvnerf_project_texels': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
@@ -164,6 +171,10 @@ SIGNATURES = {
     'mvnerf_grasp_success': (c_int, [ctypes.POINTER(GraspCall), c_void_p]),
     'mvnerf_grasp_success_and_gradients': (c_int, [ctypes.POINTER(GraspCall), c_void_p]),
     'mvnerf_grasp_opt_step': (c_int, [ctypes.POINTER(GraspCall), ctypes.POINTER(PoseAdamConfig)] + [c_void_p] * 7),
+    'mvnerf_grasp_workspace_bytes_bf16': (c_size_t, [c_int] * 4),
+    'mvnerf_grasp_success_bf16': (c_int, [ctypes.POINTER(GraspCall)] + [c_void_p] * 3),
+    'mvnerf_grasp_success_and_gradients_bf16': (c_int, [ctypes.POINTER(GraspCall)] + [c_void_p] * 3),
+    'mvnerf_grasp_opt_step_bf16': (c_int, [ctypes.POINTER(GraspCall), c_void_p, c_void_p, ctypes.POINTER(PoseAdamConfig)] + [c_void_p] * 7),
     'mvnerf_train_workspace_bytes': (c_size_t, [c_int] * 8),
     'mvnerf_loss_and_grads': (c_int, [ctypes.POINTER(TrainCall), c_void_p]),
     'mvnerf_apply_gradients': (c_int, [ctypes.POINTER(TrainCall), ctypes.POINTER(AdamState), c_void_p]),

@@ -761,6 +761,104 @@ int mvnerf_query_vjp(const float* points, const float* dirs, const float* images
     return 0;
 }
 
+// ---- the same field on the bf16 matrix pipe: relu bits instead of a stash, one launch for the twelve hidden layers (query_bf16.hip) ----
+size_t mvnerf_relu_bits_bytes(int B, int V, int N) {
+    if (B <= 0 || V <= 0 || N <= 0) return 0;
+    const StashLayout L(B, V, N);
+    return (size_t)(L.view_tiles + L.n_tiles) * 6 * 512;                  // 6 slots per view tile and per tile, 1 bit x 128 x 32 each
+}
+
+size_t mvnerf_bwd_streams_bf16_bytes(void) { return mvnerf::bwd_streams_bf16_bytes(); }
+
+int mvnerf_pack_bwd_streams_bf16(const float* net_keras, void* bwd16, mvnerf_stream_t stream) {
+    if (!net_keras || !bwd16) return fail(MVNERF_E_ARG, "mvnerf_pack_bwd_streams_bf16: null pointer");
+    if (!aligned16(bwd16)) return fail(MVNERF_E_ALIGN, "mvnerf_pack_bwd_streams_bf16: bwd16 must be 16-byte aligned");
+    return hip_status(mvnerf::launch_pack_bwd_streams_bf16(net_keras, bwd16, static_cast<hipStream_t>(stream)), "mvnerf_pack_bwd_streams_bf16");
+}
+
+namespace {
+// sizes of the three bf16 query entry points: 0 or the error code
+int query_bf16_sizes(const char* who, int B, int V, int N) {
+    if (B <= 0 || V <= 0 || N <= 0) return fail(MVNERF_E_ARG, "%s: bad sizes", who);
+    if (V > 1 && N % 32 != 0) return fail(MVNERF_E_SHAPE, "%s: N=%d must be a multiple of 32 when V > 1", who, N);
+    const StashLayout L(B, V, N);
+    if (L.total >= (1L << 31) || L.view_tiles >= (1L << 18))              // g0 tiles are addressed with 32-bit byte offsets (16 KiB per tile)
+        return fail(MVNERF_E_SHAPE, "%s: V*B*N/32 = %ld tiles, at most 262143", who, L.view_tiles);
+    return 0;
+}
+}  // namespace
+
+int mvnerf_query_stash_bf16(const float* points, const float* dirs, const float* images, const float* features, const float* intrinsics,
+                            const float* extrinsics_inv, const float* packed_net, const void* packed16, int B, int V, int N, int H, int W,
+                            float* acts, void* relu_bits, void* workspace, mvnerf_stream_t stream) {
+    const char* const who = "mvnerf_query_stash_bf16";
+    if (!points || !dirs || !images || !features || !intrinsics || !extrinsics_inv || !packed_net || !packed16 || !acts || !relu_bits ||
+        !workspace)
+        return fail(MVNERF_E_ARG, "%s: null pointer", who);
+    if (H < 2 || W < 2) return fail(MVNERF_E_ARG, "%s: bad sizes", who);
+    if (const int rc = query_bf16_sizes(who, B, V, N)) return rc;
+    if ((long)B * V * H * W >= (1L << 31)) return fail(MVNERF_E_SHAPE, "%s: B*V*H*W too large for int32 indices", who);
+    if (!aligned16(features) || !aligned16(packed_net) || !aligned16(packed16) || !aligned16(acts) || !aligned16(relu_bits) ||
+        !aligned16(workspace))
+        return fail(MVNERF_E_ALIGN, "%s: features, packed nets, acts, relu_bits, workspace must be 16-byte aligned", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const StashLayout L(B, V, N);
+    // workspace (mvnerf_query_workspace_bytes): the layer-0 seeds, then the field pass's z = 0 and its read-out nobody asked for
+    float* const ws = static_cast<float*>(workspace);
+    float* const z = ws + (size_t)B * V * N * 128;
+    float* const rgbs = z + ((L.total + 3) & ~3L);
+    MV_HIP(mvnerf::launch_zero(z, (size_t)L.total * sizeof(float), st), who);
+    mvnerf::FieldParams p = {};
+    p.rays_o = points; p.rays_d = dirs; p.z = z; p.images = images; p.features = features;
+    p.k4 = intrinsics; p.einv = extrinsics_inv; p.net = packed_net; p.rgbs = rgbs; p.acts_fused = acts; p.dir_bias = ws;
+    p.B = B; p.V = V; p.R = N; p.S = 1; p.H = H; p.W = W; p.total = L.total; p.n_tiles = L.n_tiles;
+    return hip_status(mvnerf::launch_field_eval_bf16_bits(p, packed16, relu_bits, st), who);
+}
+
+int mvnerf_trunk_vjp_bf16(const void* bwd16, const void* relu_bits, const float* g_acts, int B, int V, int N, float* g0_tl,
+                          mvnerf_stream_t stream) {
+    const char* const who = "mvnerf_trunk_vjp_bf16";
+    if (!bwd16 || !relu_bits || !g_acts || !g0_tl) return fail(MVNERF_E_ARG, "%s: null pointer", who);
+    if (const int rc = query_bf16_sizes(who, B, V, N)) return rc;
+    if (!aligned16(bwd16) || !aligned16(relu_bits) || !aligned16(g_acts) || !aligned16(g0_tl))
+        return fail(MVNERF_E_ALIGN, "%s: bwd16, relu_bits, g_acts, g0_tl must be 16-byte aligned", who);
+    const StashLayout L(B, V, N);
+    return hip_status(mvnerf::launch_trunk_vjp_bf16(bwd16, relu_bits, g_acts, B, V, L.total, L.n_tiles, g0_tl, static_cast<hipStream_t>(stream)), who);
+}
+
+size_t mvnerf_query_vjp_bf16_scratch_bytes(int B, int V, int N) {
+    if (B <= 0 || V <= 0 || N <= 0) return 0;
+    return (size_t)StashLayout(B, V, N).view_stride() * sizeof(float);            // g0, one tile buffer
+}
+
+int mvnerf_query_vjp_bf16(const float* points, const float* dirs, const float* images, const float* features, const float* intrinsics,
+                          const float* extrinsics_inv, const float* bwd_streams, const void* bwd16, const void* relu_bits,
+                          const float* g_acts, int B, int V, int N, int H, int W, void* scratch, float* d_points, float* d_dirs,
+                          mvnerf_stream_t stream) {
+    using namespace mvnerf;
+    const char* const who = "mvnerf_query_vjp_bf16";
+    if (!points || !dirs || !images || !features || !intrinsics || !extrinsics_inv || !bwd_streams || !bwd16 || !relu_bits || !g_acts ||
+        !scratch || !d_points || !d_dirs)
+        return fail(MVNERF_E_ARG, "%s: null pointer", who);
+    if (H < 2 || W < 2) return fail(MVNERF_E_ARG, "%s: bad sizes", who);
+    if (const int rc = query_bf16_sizes(who, B, V, N)) return rc;
+    if (!aligned16(features) || !aligned16(bwd_streams) || !aligned16(bwd16) || !aligned16(relu_bits) || !aligned16(g_acts) ||
+        !aligned16(scratch))
+        return fail(MVNERF_E_ALIGN, "%s: features, bwd_streams, bwd16, relu_bits, g_acts, scratch must be 16-byte aligned", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const StashLayout L(B, V, N);
+    float* const g0 = static_cast<float*>(scratch);
+    MV_HIP(launch_zero(d_points, (size_t)L.total * 3 * sizeof(float), st), who);
+    MV_HIP(launch_zero(d_dirs, (size_t)L.total * 3 * sizeof(float), st), who);
+    MV_HIP(launch_trunk_vjp_bf16(bwd16, relu_bits, g_acts, B, V, L.total, L.n_tiles, g0, st), who);
+    FieldParams p = {};
+    p.rays_o = points; p.rays_d = dirs; p.z = nullptr; p.images = images; p.features = features;
+    p.k4 = intrinsics; p.einv = extrinsics_inv;
+    p.B = B; p.V = V; p.R = N; p.S = 1; p.H = H; p.W = W; p.total = L.total; p.n_tiles = L.n_tiles;
+    MV_HIP(launch_field_dz(p, g0, bwd_streams + (size_t)12 * kHiddenWFloats, nullptr, d_points, d_dirs, nullptr, st), who);
+    return 0;
+}
+
 int mvnerf_stash_fused_acts(const float* stash, int B, int V, int N, float* acts, mvnerf_stream_t stream) {
     if (!stash || !acts) return fail(MVNERF_E_ARG, "mvnerf_stash_fused_acts: null pointer");
     if (B <= 0 || V <= 0 || N <= 0) return fail(MVNERF_E_ARG, "mvnerf_stash_fused_acts: B=%d V=%d N=%d", B, V, N);

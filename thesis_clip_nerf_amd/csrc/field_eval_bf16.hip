@@ -14,6 +14,8 @@
 //    bf16 only when a register block is fed as the next MFMA's B operand (v_cvt_pk_bf16_f32); gathered
 //    features are lerped in fp32, rounded once, and transposed through a wave-private bf16 LDS image.
 //  * the per-(view, ray) layer-0 seed (b0 + W0_dir^T PE(dir)) is the fp32 one of dir_bias_kernel.
+//  * kBits (query points, direct form): the kernel also writes one relu bit per pre-activation that the frozen trunk's backward crosses
+//    (ReluBits, mvnerf_ring16.h; mvnerf_query_stash_bf16) - all that trunk_vjp_bf16_kernel (query_bf16.hip) needs of this forward.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -23,11 +25,9 @@
 #include "mvnerf_launch.h"
 #include "mvnerf_math.h"
 #include "mvnerf_mfma.h"
+#include "mvnerf_ring16.h"
 
 namespace mvnerf {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x8 = __attribute__((ext_vector_type(8))) float;
 
 // ---- bf16 weight stream: 1 KiB chunks [lane][8 bf16], A operand of one (k-step of 16, 32-wide output block) ----
 //   layer 0 : k-steps 0..3  = PE(cam xyz) (lower half-wave sin rows, upper cos rows) + rgb rows, 16 chunks
@@ -87,68 +87,21 @@ static bool bf16x_enabled() {
     return !(e && e[0] == 's');
 }
 
-// ---- the segment ring ----------------------------------------------------------------------------------------
-// A workgroup of kWgWaves waves shares the weight stream through a ring of kRing LDS slots of kSegChunks chunks
-// (kKs k-steps x 4 output blocks), filled by LDS-DMA, 2 wave-instructions (2 KiB) per wave and segment.
+// ---- the forward weight stream through the segment ring (mvnerf_ring16.h) -------------------------------------
 // Per tile the waves consume, for every view, the layer-0 segments (PE + rgb; the feature rows unless they come from
 // the texel table) and the 3 per-view blocks, then the 3 fusion blocks and the read-out.  Position p in [0, P) ->
-// first chunk of the segment.  The weights are the same for every tile, so positions wrap modulo P.
-// The ring is LDS-DMA with 5 slots: a register-staged double buffer (two slots, no counted vmcnt) measured equal at cfg2 and
-// 14 % slower at V = 3 / 480x640 (profiles/r02_ab_bf16_staged_*.log).
-constexpr int kWgWaves = 8;                                    // one 512-thread workgroup per CU (see the top of this file)
-constexpr int kSegChunks = 2 * kWgWaves;                       // 16 chunks of 1 KiB
-constexpr int kKs = kSegChunks / 4;                            // k-steps (of 16 rows) per segment: 4
-constexpr int kRing = 5, kAhead = 3, kSegF4 = kSegChunks * 64;  // float4 per slot
-constexpr int kHiddenUnits = 192 / kSegChunks;                 // segments of 3 blocks (6 Dense layers x 32 chunks)
-
-struct Ring {
-    const f32x4* w16;
-    f32x4* base;        // LDS
-    int c;              // ring slot of the current segment
-    int p, P, V;
-    int l0_units;       // layer-0 segments per view: PE + rgb only (texel table) or PE + rgb + 256 feature rows
-    int tid, wave;
-};
-
-__device__ __forceinline__ int ring_start_chunk(int p, int V, int l0_units) {
-    const int per_view = l0_units + kHiddenUnits;
-    if (p < per_view * V) {
-        const int q = p % per_view;
-        return q < l0_units ? q * kSegChunks : kW16Hidden + (q - l0_units) * kSegChunks;
+// first chunk of the segment.
+struct FwdStream {
+    static __device__ __forceinline__ int start_chunk(const Ring& r, int p) {
+        const int per_view = r.l0_units + kHiddenUnits;
+        if (p < per_view * r.V) {
+            const int q = p % per_view;
+            return q < r.l0_units ? q * kSegChunks : kW16Hidden + (q - r.l0_units) * kSegChunks;
+        }
+        const int q = p - per_view * r.V;
+        return q < kHiddenUnits ? kW16Hidden + 192 + q * kSegChunks : kW16Readout;
     }
-    const int q = p - per_view * V;
-    return q < kHiddenUnits ? kW16Hidden + 192 + q * kSegChunks : kW16Readout;
-}
-
-// issue the LDS-DMA of position p + ahead into slot (c + ahead) % kRing: 2 x 16 B per thread, 1 KiB per wave-instruction
-__device__ __forceinline__ void ring_issue(const Ring& r, int ahead) {
-    int pp = r.p + ahead;
-    if (pp >= r.P) pp -= r.P;
-    const f32x4* src = r.w16 + (long)ring_start_chunk(pp, r.V, r.l0_units) * 64 + r.tid;
-    f32x4* dst = r.base + ((r.c + ahead) % kRing) * kSegF4 + 64 * r.wave;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 64 * kWgWaves),
-                                     (__attribute__((address_space(3))) void*)(dst + 64 * kWgWaves), 16, 0, 0);
-}
-
-__device__ __forceinline__ const f32x4* ring_cur(const Ring& r) { return r.base + r.c * kSegF4; }
-
-// end of a segment: the next segment's DMA (issued kAhead - 1 segments ago) must have landed for every wave.
-// kDrain = false leaves the two younger segments (4 DMA instructions of this thread) in flight; segments that also
-// issue ordinary loads or stores drain everything (their own waits are in-order with the DMA anyway).
-template <bool kDrain>
-__device__ __forceinline__ void ring_next(Ring& r) {
-    if (kDrain) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-    r.c = r.c + 1 == kRing ? 0 : r.c + 1;
-    r.p = r.p + 1 == r.P ? 0 : r.p + 1;
-    ring_issue(r, kAhead);                             // slot (c + 3) % 5 was last read two segments ago; everyone is past that barrier
-}
-
-__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
+};
 
 // ---- texel table on the bf16 MFMA (see field_eval.hip, project_texels_kernel, for the fp32 form) --------------
 // T[texel] = W0[123:379]^T features[texel] with bf16 inputs and fp32 accumulation - the same rounding the direct bf16
@@ -259,37 +212,9 @@ __device__ __forceinline__ bf16x8 relu_to_bf16(const f32x16& v, int s) {
     return __builtin_bit_cast(bf16x8, r);
 }
 
-// acc += W^T relu(in) for one hidden layer = two 16-chunk segments (input blocks 0,1 then 2,3)
-// The A operands of k-step ks+1 are requested from LDS before the MFMAs of k-step ks are issued (pinned with a
-// sched_barrier: left alone the compiler keeps two A register sets and waits for an LDS round trip per MFMA pair),
-// and the relu / bf16 conversion of the next B operand runs in the shadow of those MFMAs.
-// bfn(ks) -> B operand (bf16x8) of k-step ks of the segment.
-template <typename BFn>
-__device__ __forceinline__ void segment_mfma(Ring& ring, int lane, BFn bfn, f32x16 (&acc)[4]) {
-    const f32x4* wb = ring_cur(ring) + lane;
-    f32x4 a[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) a[nb] = wb[nb * 64];
-    bf16x8 b = bfn(0);
-#pragma unroll
-    for (int ks = 0; ks < kKs; ++ks) {
-        f32x4 an[4];
-        if (ks < kKs - 1) {
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb) an[nb] = wb[((ks + 1) * 4 + nb) * 64];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma16(__builtin_bit_cast(bf16x8, a[nb]), b, acc[nb]);
-        if (ks < kKs - 1) {
-            b = bfn(ks + 1);
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb) a[nb] = an[nb];
-        }
-    }
-}
-
 // acc += W^T relu(in) for one hidden layer: 8 k-steps (input block kb = ks / 2, half ks % 2) in 8 / kKs segments
+// kDrainFirst: a store was issued in front of the layer (the relu bits of `in`), so its first segment drains
+template <bool kDrainFirst = false>
 __device__ __forceinline__ void dense128_bf16(Ring& ring, int lane, const f32x16 (&in)[4], f32x16 (&acc)[4]) {
 #pragma unroll
     for (int seg = 0; seg < 8 / kKs; ++seg) {
@@ -297,8 +222,19 @@ __device__ __forceinline__ void dense128_bf16(Ring& ring, int lane, const f32x16
             const int g = seg * kKs + ks;
             return relu_to_bf16(in[g >> 1], g & 1);
         }, acc);
-        ring_next<false>(ring);
+        if (kDrainFirst && seg == 0) ring_next<true, FwdStream>(ring);
+        else ring_next<false, FwdStream>(ring);
     }
+}
+
+// the lane's 64 relu bits of a pre-activation tensor (ReluBits, mvnerf_ring16.h): bit 16 nb + r = [x[nb][r] > 0]
+__device__ __forceinline__ void store_relu_bits(unsigned long long* dst, const f32x16 (&x)[4]) {
+    unsigned int w[2] = {0u, 0u};
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) w[nb >> 1] |= (unsigned int)(x[nb][r] > 0.0f) << (16 * (nb & 1) + r);
+    *dst = (unsigned long long)w[0] | ((unsigned long long)w[1] << 32);
 }
 
 template <bool kAdd>
@@ -332,7 +268,9 @@ constexpr int kStage16Row = 256;      // bytes per staged sample row: 128 channe
 // workgroup share the weight ring, hence gather at the same time, and nothing else hides that latency.
 // kF16 (direct gather only): p.features holds bf16 feature maps (512-byte texel rows); the taps are widened to fp32 (exact), lerped
 // in fp32 and rounded once, as with fp32 maps.
-template <bool kMultiView, bool kProj, bool kF16>
+// kBits (direct gather, S = 1 query points): also writes the relu bits of the 6V + 6 pre-activations the trunk's backward needs
+// (trunk_vjp_bf16_kernel, query_bf16.hip), each taken from the fp32 accumulator relu_to_bf16 is about to consume.
+template <bool kMultiView, bool kProj, bool kF16, bool kBits = false>
 __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(FieldParams p, const f32x4* __restrict__ w16) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem16[];
     constexpr int kRingBytes = kRing * kSegF4 * 16;                       // 80 KiB
@@ -344,6 +282,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
     float* net = reinterpret_cast<float*>(smem16 + kRingBytes + kWgWaves * 32 * kStage16Row) - kPackB0;   // net[kPackB0 + i] -> LDS
     for (int i = tid; i < kPackBr + 8 - kPackB0; i += 64 * kWgWaves) net[kPackB0 + i] = p.net[kPackB0 + i];
 
+    const ReluBits bits = {p.relu_bits, p.n_tiles * p.V * kBitSlots * 64};        // (kBits only)
     Ring ring;
     ring.w16 = w16;
     ring.base = reinterpret_cast<f32x4*>(smem16);
@@ -354,11 +293,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
     ring.P = (ring.l0_units + kHiddenUnits) * p.V + kHiddenUnits + 1;
     ring.tid = tid;
     ring.wave = wave;
-    ring_issue(ring, 0);
-    ring_issue(ring, 1);
-    ring_issue(ring, 2);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    ring_issue(ring, kAhead);
+    ring_prime<FwdStream>(ring);
 
     const long n_groups = (p.n_tiles + kWgWaves - 1) / kWgWaves;
     for (long grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
@@ -390,6 +325,8 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
             const Taps tp = bilinear_taps(pxl, pyl, p.H, p.W);
             const int tl = (bv * p.H + tp.y0) * p.W + tp.x0;
             const long vrow = ((long)bv * p.R + (ray - b * p.R)) * p.S + sidx;
+            // S = 1, whole tiles per scene when V > 1: the view tile of StashLayout, (b V + v) tiles_per_b + k
+            const long view_tile = kMultiView ? tile + ((long)b * (p.V - 1) + v) * (p.n_tiles / p.B) : tile;
             if (valid && h == 0 && p.tap_idx) {
                 int4 t4 = make_int4(tl, tl + 1, tl + p.W, tl + p.W + 1);
                 *reinterpret_cast<int4*>(p.tap_idx + 4 * vrow) = t4;
@@ -435,7 +372,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
                     for (int q = 0; q < 8; ++q) t[q] = pe[8 * (seg * kKs + ks) + q];
                     return __builtin_convertvector(t, bf16x8);
                 }, x);
-                ring_next<true>(ring);
+                ring_next<true, FwdStream>(ring);
             }
 
             if (kProj) {
@@ -551,7 +488,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
                         const int off = j * kStage16Row + (((2 * (kKs * part + ks) + h) ^ (j & 15)) << 4);
                         return *reinterpret_cast<const bf16x8*>(stage + off);
                     }, x);
-                    ring_next<true>(ring);
+                    ring_next<true, FwdStream>(ring);
                 }
             }
 
@@ -560,9 +497,11 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
             for (int bi = 0; bi < 3; ++bi) {
                 const float* bias1 = net + kPackBHidden + 256 * bi;
                 bias_acc<false>(bias1, h, hid);
-                dense128_bf16(ring, lane, x, hid);
+                if (kBits && tile_ok) store_relu_bits(bits.view(view_tile, 2 * bi, lane), x);
+                dense128_bf16<kBits>(ring, lane, x, hid);
                 bias_acc<true>(bias1 + 128, h, x);
-                dense128_bf16(ring, lane, hid, x);
+                if (kBits && tile_ok) store_relu_bits(bits.view(view_tile, 2 * bi + 1, lane), hid);
+                dense128_bf16<kBits>(ring, lane, hid, x);
             }
             if (kMultiView) {
 #pragma unroll
@@ -592,9 +531,11 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
         for (int bi = 3; bi < 6; ++bi) {
             const float* bias1 = net + kPackBHidden + 256 * bi;
             bias_acc<false>(bias1, h, hid);
-            dense128_bf16(ring, lane, x, hid);
+            if (kBits && tile_ok) store_relu_bits(bits.fused(tile, 2 * (bi - 3), lane), x);
+            dense128_bf16<kBits>(ring, lane, x, hid);
             bias_acc<true>(bias1 + 128, h, x);
-            dense128_bf16(ring, lane, hid, x);
+            if (kBits && tile_ok) store_relu_bits(bits.fused(tile, 2 * (bi - 3) + 1, lane), hid);
+            dense128_bf16<kBits>(ring, lane, hid, x);
             if (p.acts_fused && valid) store_row(p.acts_fused + (long)(bi - 2) * p.total * 128);
         }
         if (p.embedding && valid) store_row(p.embedding);
@@ -621,7 +562,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
             out[3] = softplus_f32(o[3]);
             *reinterpret_cast<f32x4*>(p.rgbs + 4 * g) = out;
         }
-        ring_next<true>(ring);                                           // stores above: drain
+        ring_next<true, FwdStream>(ring);                                           // stores above: drain
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                     // DMA still in flight must land before the LDS is released
 }
@@ -652,6 +593,26 @@ hipError_t launch_field_eval_bf16(const FieldParams& p, const void* packed16, hi
         else MV16_GO(false, false, false);
     }
 #undef MV16_GO
+    return hipGetLastError();
+}
+
+// The direct-form kernel on query points (S = 1, no texel table, fp32 maps) with the relu bits as a second output
+hipError_t launch_field_eval_bf16_bits(const FieldParams& p_in, const void* packed16, void* relu_bits, hipStream_t stream) {
+    FieldParams p = p_in;
+    p.relu_bits = static_cast<unsigned long long*>(relu_bits);
+    static DeviceSetup setup;
+    const int lds_bytes = kRing * kSegF4 * 16 + kWgWaves * 32 * kStage16Row + (kPackBr + 8 - kPackB0) * 4;
+    int cus = 0;
+    hipError_t e = device_setup(setup, {{&field_eval_bf16_kernel<false, false, false, true>, lds_bytes},
+                                        {&field_eval_bf16_kernel<true, false, false, true>, lds_bytes}}, &cus);
+    if (e != hipSuccess) return e;
+    if ((e = launch_dir_bias(p, stream)) != hipSuccess) return e;
+    const long n_groups = (p.n_tiles + kWgWaves - 1) / kWgWaves;
+    const long resident = (long)cus * (8 / kWgWaves);
+    const unsigned wgs = (unsigned)(n_groups < resident ? n_groups : resident);
+    const f32x4* w16 = static_cast<const f32x4*>(packed16);
+    if (p.V > 1) hipLaunchKernelGGL((field_eval_bf16_kernel<true, false, false, true>), dim3(wgs), dim3(64 * kWgWaves), lds_bytes, stream, p, w16);
+    else hipLaunchKernelGGL((field_eval_bf16_kernel<false, false, false, true>), dim3(wgs), dim3(64 * kWgWaves), lds_bytes, stream, p, w16);
     return hipGetLastError();
 }
 

@@ -31,7 +31,8 @@ struct FieldParams {
     int B, V, R, S, H, W;
     long total;            // B*R*S samples
     long n_tiles;          // ceil(total / 32)
-    unsigned int* tile_counter;   // unused (was the ticket of a persistent field_eval_kernel form); kept: removing it shifts every kernel's arguments
+    unsigned long long* relu_bits;   // bf16 query forward only (ReluBits, mvnerf_ring16.h); the slot of a former tile ticket: removing or adding
+                                     // a field shifts every kernel's arguments
     // forward-mode tangent kernel (query_ops.hip)
     const float* t_o;      // (B,R,3) tangent of rays_o
     const float* t_d;      // (B,R,3) tangent of rays_d
@@ -58,6 +59,13 @@ hipError_t launch_field_eval_bf16x(const FieldParams& p, const void* packed16x, 
 hipError_t launch_project_texels_bf16(const float* features, const void* packed16, const void* packed16b, long n_texels, float* table,
                                       float* table1, hipStream_t stream);
 hipError_t launch_field_eval_bf16(const FieldParams& p, const void* packed16, hipStream_t stream, bool maps_bf16 = false);   // maps_bf16: p.features holds bf16
+// the direct-form kernel on query points (S = 1, fp32 maps, no texel table) that also writes the relu bits (ReluBits, mvnerf_ring16.h)
+hipError_t launch_field_eval_bf16_bits(const FieldParams& p, const void* packed16, void* relu_bits, hipStream_t stream);
+// query_bf16.hip: the frozen trunk's input gradient on the bf16 MFMA, from relu bits and the transposed bf16 weight stream
+size_t bwd_streams_bf16_bytes();
+hipError_t launch_pack_bwd_streams_bf16(const float* net_keras, void* bwd16, hipStream_t st);
+hipError_t launch_trunk_vjp_bf16(const void* bwd16, const void* relu_bits, const float* g_acts, int B, int V, long total, long n_tiles,
+                                 float* g0_tl, hipStream_t stream);
 hipError_t launch_project_texels_bf16maps(const void* features_bf16, const void* packed16, const void* packed16b, long n_texels, float* table,
                                           float* table1, hipStream_t stream);
 size_t packed_net_split_bytes();

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .lmvnerf import N_FUSED, TrunkState, rotation_from_6d, rotation_from_quaternion, t_m_to_h_matrix
+from .lmvnerf import COMPUTE_DTYPES, N_FUSED, TrunkState, rotation_from_6d, rotation_from_quaternion, t_m_to_h_matrix
 
 DEFAULT_WORKSPACE_BOUNDS = ((0.35, 0.85), (-0.25, 0.25), (0.0, 0.2))      # configs/generator_grasp/default.yaml
 
@@ -68,9 +68,12 @@ class DNGFOptimizer:
     `n_images` input images are regrouped into B = n_images / n_views scenes."""
 
     def __init__(self, nerf_grasper, workspace_bounds=DEFAULT_WORKSPACE_BOUNDS, n_initial_guesses=32, n_images=3, fixed_orientation=None,
-                 clip_translation=False, rotation_representation='quaternion'):
+                 clip_translation=False, rotation_representation='quaternion', compute_dtype='f32'):
         if rotation_representation not in ('quaternion', '6d'):
             raise ValueError('Unknown rotation representation: ' + rotation_representation)
+        if compute_dtype not in COMPUTE_DTYPES:
+            raise ValueError(f"compute_dtype must be 'f32' or 'bf16', got {compute_dtype!r}")
+        self.compute_dtype = compute_dtype          # 'bf16': stages 2 and 6 on the bf16 MFMA (query_stash_bf16, query_vjp_bf16; DESIGN.md 12.2)
         self.workspace_bounds = np.array(workspace_bounds, dtype=np.float64)
         if self.workspace_bounds.shape != (3, 2):
             raise ValueError(f'workspace_bounds: shape {self.workspace_bounds.shape}, expected (3, 2)')
@@ -226,13 +229,17 @@ class DNGFOptimizer:
         w4 = torch.stack([lin.weight.detach() for lin in ro.activation_downscale]).contiguous()
         b4 = torch.stack([lin.bias.detach() for lin in ro.activation_downscale]).contiguous()
         wc, bc = ro.combined_activation_downscale.weight.detach().contiguous(), ro.combined_activation_downscale.bias.detach().contiguous()
-        state = TrunkState(images, feats, k, einv, g.trunk_net)
+        bf16 = self.compute_dtype == 'bf16'
+        state = TrunkState(images, feats, k, einv, g.trunk_net, self.compute_dtype)
         head = ops.grasp_head_pack(w4, wc)
         if self._bound is not None and self._bound['key'] == key:
             bd = self._bound
             for old, new in ((bd['state'].packed, state.packed), (bd['state'].packed_split, state.packed_split),
                              (bd['state'].bwd_streams, state.bwd_streams), (bd['head'], head), (bd['b4'], b4), (bd['bc'], bc)):
                 old.copy_(new)
+            if bf16:
+                bd['state'].packed16.copy_(state.packed16)
+                bd['state'].bwd16.copy_(state.bwd16)
             if 'fused' in bd:
                 self._pack_tail(out=bd['fused']['tail'])
             return bd
@@ -244,7 +251,7 @@ class DNGFOptimizer:
         self._bound = dict(key=key, state=state, head=head, b4=b4, bc=bc, n=n, ld=ld, n5=n5,
                            points=torch.zeros((b, ld, 3), dtype=torch.float32, device=dev),
                            dirs=torch.zeros((b, ld, 3), dtype=torch.float32, device=dev),
-                           stash=torch.empty(ops.stash_bytes(b, v, ld, 1), dtype=torch.uint8, device=dev),
+                           stash=torch.empty(ops.relu_bits_bytes(b, v, ld) if bf16 else ops.stash_bytes(b, v, ld, 1), dtype=torch.uint8, device=dev),
                            g_pad=torch.zeros((N_FUSED, b, ld, 128), dtype=torch.float32, device=dev) if ld > n else None,
                            tail={name: {k_: p.detach() for k_, p in getattr(ro, name).named_parameters()}
                                  for name in ('block_0', 'block_1', 'output_layer')})
@@ -268,12 +275,13 @@ class DNGFOptimizer:
             st, b, p = bd['state'], self.batch_size, self.n_initial_guesses
             dev = self.device_
             tail = self._pack_tail()
-            ws = torch.empty(ops.grasp_workspace_bytes(b, g.n_views, p, bd['n5']), dtype=torch.uint8, device=dev)
+            ws = torch.empty(ops.grasp_workspace_bytes(b, g.n_views, p, bd['n5'], bf16=self.compute_dtype == 'bf16'), dtype=torch.uint8, device=dev)
             success = torch.zeros((b, p), dtype=torch.float32, device=dev)
             offsets = g.transforms_to_check.contiguous()
             call = ops.grasp_call(*st.geo, st.packed, st.packed_split, st.bwd_streams, bd['head'], bd['b4'], bd['bc'], tail, offsets,
                                   self.translations, self.rotations, success, self._g_t, self._g_r, ws)
-            bd['fused'] = dict(tail=tail, ws=ws, success=success, offsets=offsets, call=call)
+            nets16 = (st.packed16, st.bwd16) if self.compute_dtype == 'bf16' else None       # -> the _bf16 entry points
+            bd['fused'] = dict(tail=tail, ws=ws, success=success, offsets=offsets, call=call, nets16=nets16)
         return bd['fused']
 
     def _readout_tail(self, x):
@@ -291,8 +299,11 @@ class DNGFOptimizer:
         if ld > n:
             points[:, n:] = points[:, n - 1:n]
             dirs[:, n:] = dirs[:, n - 1:n]
-        ops.query_stash(points, dirs, *st.geo, st.packed, stash=bd['stash'], packed_split=st.packed_split)
-        acts = ops.stash_fused_acts(bd['stash'], b, g.n_views, ld)
+        if self.compute_dtype == 'bf16':
+            acts, _ = ops.query_stash_bf16(points, dirs, *st.geo, st.packed, st.packed16, relu_bits=bd['stash'])
+        else:
+            ops.query_stash(points, dirs, *st.geo, st.packed, stash=bd['stash'], packed_split=st.packed_split)
+            acts = ops.stash_fused_acts(bd['stash'], b, g.n_views, ld)
         if ld > n:
             acts = acts[:, :, :n].contiguous()
         return ops.grasp_head_fwd(acts.reshape(N_FUSED, -1, 128), bd['head'], bd['b4'], bd['bc'])
@@ -301,7 +312,7 @@ class DNGFOptimizer:
         """Steps 1-7 on the bound inputs: -> success (B, P), and d(-sum success)/d(t, rot) in the step's gradient buffers (P, 3), (P, 4|6)."""
         if self._fused:
             fs = self._fused_state()
-            ops.grasp_success_and_gradients(fs['call'], self.translations)
+            ops.grasp_success_and_gradients(fs['call'], self.translations, nets16=fs['nets16'])
             return fs['success'].clone(), self._g_t, self._g_r
         bd, g = self._bound, self.nerf_grasper
         st, n, ld, b, n5 = bd['state'], bd['n'], bd['ld'], self.batch_size, bd['n5']
@@ -315,7 +326,10 @@ class DNGFOptimizer:
         if ld > n:
             bd['g_pad'][:, :, :n] = g_acts
             g_acts = bd['g_pad']
-        d_points, d_dirs = ops.query_vjp(bd['points'], bd['dirs'], *st.geo, st.bwd_streams, bd['stash'], g_acts)
+        if self.compute_dtype == 'bf16':
+            d_points, d_dirs = ops.query_vjp_bf16(bd['points'], bd['dirs'], *st.geo, st.bwd_streams, st.bwd16, bd['stash'], g_acts)
+        else:
+            d_points, d_dirs = ops.query_vjp(bd['points'], bd['dirs'], *st.geo, st.bwd_streams, bd['stash'], g_acts)
         ops.pose_query_vjp(self.rotations, g.transforms_to_check, d_points, d_dirs, scale=-1.0, out=(self._g_t, self._g_r))
         return success.detach(), self._g_t, self._g_r
 
@@ -323,7 +337,7 @@ class DNGFOptimizer:
         if self._fused:
             fs = self._fused_state()
             ops.grasp_opt_step(fs['call'], self._adam_cfg, self._flags, self._counters, self._m_t, self._v_t, self._m_r, self._v_r,
-                               self.translations)
+                               self.translations, nets16=fs['nets16'])
             return fs['success']
         success, g_t, g_r = self.success_and_gradients()
         ops.pose_adam_step(self._adam_cfg, self._flags, self._counters, g_t, g_r, self._m_t, self._v_t, self._m_r, self._v_r,
@@ -377,7 +391,7 @@ class DNGFOptimizer:
         b, n5 = self.batch_size, self._bound['n5']
         if self._fused:
             fs = self._fused_state()
-            ops.grasp_success(fs['call'], self.translations)
+            ops.grasp_success(fs['call'], self.translations, nets16=fs['nets16'])
             return fs['success'].sum(0)[:, None]
         with torch.no_grad():
             _, y = self._forward()

@@ -27,18 +27,25 @@ from torch import nn
 from . import ops, range_policy
 
 N_FUSED = 4
+COMPUTE_DTYPES = ('f32', 'bf16')
 
 
 # ---- the trunk as an autograd function ----------------------------------------------------------------------
 class TrunkState:
     """Everything the trunk needs besides the query points: source views, cameras, packed weights."""
 
-    def __init__(self, images, features, intrinsics, extrinsics_inv, net_keras):
+    def __init__(self, images, features, intrinsics, extrinsics_inv, net_keras, compute_dtype='f32'):
+        if compute_dtype not in COMPUTE_DTYPES:
+            raise ValueError(f"compute_dtype must be 'f32' or 'bf16', got {compute_dtype!r}")
+        self.compute_dtype = compute_dtype
         self.geo = (images.contiguous(), features.contiguous(), intrinsics.contiguous(), extrinsics_inv.contiguous())
         self.packed = ops.pack_net(net_keras)
         self.packed_split = ops.pack_net_split(net_keras)          # value pass on the split-bf16 kernel (fp32-grade, DESIGN.md 4.0)
         self.bwd_streams = ops.pack_bwd_streams(net_keras)
         self.n_views = images.shape[1]
+        if compute_dtype == 'bf16':                                # the hidden layers on the bf16 MFMA, forward and VJP (DESIGN.md 12.2)
+            self.packed16 = ops.pack_net_bf16(net_keras)
+            self.bwd16 = ops.pack_bwd_streams_bf16(net_keras)
 
 
 def _pad32(t, n_pad):
@@ -51,11 +58,16 @@ class _TrunkVJP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g_acts, points, dirs, state, stash):
         ctx.state, ctx.points, ctx.dirs = state, points, dirs
+        if state.compute_dtype == 'bf16':               # stash: the relu bits of query_stash_bf16
+            return ops.query_vjp_bf16(points, dirs, *state.geo, state.bwd_streams, state.bwd16, stash, g_acts.contiguous())
         return ops.query_vjp(points, dirs, *state.geo, state.bwd_streams, stash, g_acts.contiguous())
 
     @staticmethod
     def backward(ctx, c_points, c_dirs):
         st = ctx.state
+        if st.compute_dtype == 'bf16':
+            raise RuntimeError("the trunk's second derivative (the JVP behind the gradient of a gradient) has no bf16 form: "
+                               "build the TrunkState with compute_dtype='f32' for losses on d prediction / d pose")
         zero = torch.zeros_like(ctx.points)
         c_points = zero if c_points is None else c_points.contiguous()
         c_dirs = zero if c_dirs is None else c_dirs.contiguous()
@@ -71,8 +83,11 @@ class TrunkField(torch.autograd.Function):
         b, n, _ = points.shape
         pad = (-n) % 32 if state.n_views > 1 else 0     # the multi-view training kernels want whole 32-point tiles per scene
         p, d = _pad32(points.detach().contiguous(), pad), _pad32(dirs.detach().contiguous(), pad)
-        stash = ops.query_stash(p, d, *state.geo, state.packed, packed_split=state.packed_split)
-        acts = ops.stash_fused_acts(stash, b, state.n_views, n + pad)       # tile layout -> (4, b, n + pad, 128) rows
+        if state.compute_dtype == 'bf16':
+            acts, stash = ops.query_stash_bf16(p, d, *state.geo, state.packed, state.packed16)          # rows, and relu bits for the VJP
+        else:
+            stash = ops.query_stash(p, d, *state.geo, state.packed, packed_split=state.packed_split)
+            acts = ops.stash_fused_acts(stash, b, state.n_views, n + pad)   # tile layout -> (4, b, n + pad, 128) rows
         ctx.state, ctx.stash, ctx.pad, ctx.n = state, stash, pad, n
         ctx.save_for_backward(p, d)
         return acts[:, :, :n].contiguous() if pad else acts
@@ -663,11 +678,11 @@ class LanguageNeRF(nn.Module):
                else rotation_from_6d(self.rotations))
         return t_m_to_h_matrix(self.translations, rot)
 
-    def trunk_state(self, inputs, batched_features):
+    def trunk_state(self, inputs, batched_features, compute_dtype='f32'):
         """inputs[4:7] = src_images (B,V,H,W,3), src_intrinsics (B,V,4,4), src_extrinsics_inv (B,V,4,4) (model_v4.py:209-213)."""
         dev = self.device_
         f32 = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev)
-        return TrunkState(f32(inputs[4]), f32(batched_features), f32(inputs[5]), f32(inputs[6]), self.trunk_net)
+        return TrunkState(f32(inputs[4]), f32(batched_features), f32(inputs[5]), f32(inputs[6]), self.trunk_net, compute_dtype)
 
     def _query_points(self, transforms):
         """poses = transforms @ offsets (model_v4.py:222-226) reduced to what is used of them: points = the poses' translations, dirs =
@@ -707,21 +722,31 @@ class LanguageNeRF(nn.Module):
         return self.grasp_readout(acts)
 
     def infer(self, inputs, transforms, n_points_infer, batched_features, compute_dtype='f32'):
-        """model_v4.py:208-209.  compute_dtype='bf16' evaluates the trunk on the bf16 MFMA kernel (no gradients there)."""
+        """model_v4.py:208-209.  compute_dtype='bf16' evaluates the trunk on the bf16 MFMA kernel (gradients in bf16: TrunkState(compute_dtype='bf16'))."""
         transforms = torch.as_tensor(transforms, dtype=torch.float32).to(self.device_)
         with torch.no_grad():
             if compute_dtype == 'f32':
                 return self._call(inputs, transforms, n_points_infer, batched_features)
             if compute_dtype != 'bf16':
                 raise ValueError("compute_dtype must be 'f32' or 'bf16'")
-            state = self.trunk_state(inputs, batched_features)
+            f32 = lambda t: torch.as_tensor(t, dtype=torch.float32).to(self.device_).contiguous()
+            geo = (f32(inputs[4]), f32(batched_features), f32(inputs[5]), f32(inputs[6]))
+            packed, packed16 = self._infer_nets16()
             b = transforms.shape[0]
             points, dirs = (t.contiguous() for t in self._query_points(transforms))
             z = torch.zeros(b, points.shape[1], 1, dtype=torch.float32, device=self.device_)
-            _, acts = ops.field_eval_bf16(points, dirs, z, *state.geo, state.packed, ops.pack_net_bf16(self.trunk_net),
-                                          return_fused_acts=True)
+            _, acts = ops.field_eval_bf16(points, dirs, z, *geo, packed, packed16, return_fused_acts=True)
             acts = acts.reshape(N_FUSED, b, n_points_infer, self.n_transforms_to_check, 128)
             return self.grasp_readout(list(acts.unbind(0)))
+
+    def _infer_nets16(self):
+        """The two weight images infer(compute_dtype='bf16') reads, packed once per value of trunk_net (its storage and version counter)."""
+        key = (self.trunk_net.data_ptr(), self.trunk_net._version)
+        cached = getattr(self, '_nets16_cache', None)
+        if cached is None or cached[0] != key:
+            cached = (key, ops.pack_net(self.trunk_net), ops.pack_net_bf16(self.trunk_net))
+            object.__setattr__(self, '_nets16_cache', cached)
+        return cached[1], cached[2]
 
     def loss_and_grads(self, data, combined_features):
         """The body of train_step (model_v4.py:277-318) up to the optimizer: returns (dict of losses, prediction)."""

@@ -794,8 +794,17 @@ def grasp_tail_vjp_bwd(x, t_x, stash, cot, packed, g_s=None, want_x=True, out=No
 
 
 # ---- one grasp-pose optimisation step behind the C ABI (csrc/grasp_api.hip; lmvnerf/grasp_optimizer.py:158-184) ------------------------------
-def grasp_workspace_bytes(b, v, p, n5):
-    return int(_lib.lib().mvnerf_grasp_workspace_bytes(int(b), int(v), int(p), int(n5)))
+def grasp_workspace_bytes(b, v, p, n5, bf16=False):
+    fn = _lib.lib().mvnerf_grasp_workspace_bytes_bf16 if bf16 else _lib.lib().mvnerf_grasp_workspace_bytes
+    return int(fn(int(b), int(v), int(p), int(n5)))
+
+
+def _nets16(nets16):
+    """(packed16, bwd16) of the _bf16 grasp entry points -> their two pointer arguments."""
+    packed16, bwd16 = nets16
+    _chk(packed16, 'packed16', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_packed_net_bf16_bytes()),))
+    _chk(bwd16, 'bwd16', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_bwd_streams_bf16_bytes()),))
+    return _p(packed16), _p(bwd16)
 
 
 def grasp_call(images, features, intrinsics, extrinsics_inv, packed_net, split, bwd_streams, head_packed, head_b4, head_bc, tail_packed, offsets,
@@ -828,19 +837,28 @@ def grasp_call(images, features, intrinsics, extrinsics_inv, packed_net, split, 
     return c
 
 
-def grasp_success(call, stream_of):
-    """mvnerf_grasp_success: stages 1-4 on a filled grasp_call -> its success (B, P)."""
+def grasp_success(call, stream_of, nets16=None):
+    """mvnerf_grasp_success: stages 1-4 on a filled grasp_call -> its success (B, P).  nets16 = (packed16, bwd16): mvnerf_grasp_success_bf16,
+    the trunk on the bf16 MFMA (workspace: grasp_workspace_bytes(..., bf16=True)); likewise for the two functions below."""
     with torch.cuda.device(stream_of.device):
-        _lib.check(_lib.lib().mvnerf_grasp_success(ctypes.byref(call), _stream(stream_of)), 'grasp_success')
+        if nets16 is None:
+            rc = _lib.lib().mvnerf_grasp_success(ctypes.byref(call), _stream(stream_of))
+        else:
+            rc = _lib.lib().mvnerf_grasp_success_bf16(ctypes.byref(call), *_nets16(nets16), _stream(stream_of))
+    _lib.check(rc, 'grasp_success')
 
 
-def grasp_success_and_gradients(call, stream_of):
+def grasp_success_and_gradients(call, stream_of, nets16=None):
     """mvnerf_grasp_success_and_gradients: stages 1-7 -> success, g_t, g_rot of the call."""
     with torch.cuda.device(stream_of.device):
-        _lib.check(_lib.lib().mvnerf_grasp_success_and_gradients(ctypes.byref(call), _stream(stream_of)), 'grasp_success_and_gradients')
+        if nets16 is None:
+            rc = _lib.lib().mvnerf_grasp_success_and_gradients(ctypes.byref(call), _stream(stream_of))
+        else:
+            rc = _lib.lib().mvnerf_grasp_success_and_gradients_bf16(ctypes.byref(call), *_nets16(nets16), _stream(stream_of))
+    _lib.check(rc, 'grasp_success_and_gradients')
 
 
-def grasp_opt_step(call, cfg, train_flags, counters, m_t, v_t, m_r, v_r, stream_of):
+def grasp_opt_step(call, cfg, train_flags, counters, m_t, v_t, m_r, v_r, stream_of, nets16=None):
     """mvnerf_grasp_opt_step: stages 1-8, in place on the call's t, rot and on the Adam state (arguments as pose_adam_step)."""
     p, rd = call.P, (4, 6)[call.rep]
     _chk(train_flags, 'train_flags', dtype=torch.int32, shape=(2,))
@@ -850,8 +868,11 @@ def grasp_opt_step(call, cfg, train_flags, counters, m_t, v_t, m_r, v_r, stream_
         if x.numel() != width * p:
             raise ValueError(f'{n}: {x.numel()} floats, expected {width * p}')
     with torch.cuda.device(stream_of.device):
-        rc = _lib.lib().mvnerf_grasp_opt_step(ctypes.byref(call), ctypes.byref(cfg), _p(train_flags), _p(counters), _p(m_t), _p(v_t), _p(m_r),
-                                              _p(v_r), _stream(stream_of))
+        moments = (_p(train_flags), _p(counters), _p(m_t), _p(v_t), _p(m_r), _p(v_r), _stream(stream_of))
+        if nets16 is None:
+            rc = _lib.lib().mvnerf_grasp_opt_step(ctypes.byref(call), ctypes.byref(cfg), *moments)
+        else:
+            rc = _lib.lib().mvnerf_grasp_opt_step_bf16(ctypes.byref(call), *_nets16(nets16), ctypes.byref(cfg), *moments)
     _lib.check(rc, 'grasp_opt_step')
 
 
@@ -1245,6 +1266,103 @@ def query_vjp(points, dirs, images, features, intrinsics, extrinsics_inv, bwd_st
                                          _p(bwd_streams), _p(stash), _p(g_acts), b, v, n, h, w, _p(scratch), _p(d_points),
                                          _p(d_dirs), _stream(points))
     _lib.check(rc, 'query_vjp')
+    return d_points, d_dirs
+
+
+# ---- the same field on the bf16 matrix pipe: relu bits instead of a stash, one backward launch (csrc/query_bf16.hip) ----
+def relu_bits_bytes(b, v, n):
+    return int(_lib.lib().mvnerf_relu_bits_bytes(b, v, n))
+
+
+def pack_bwd_streams_bf16(net_keras):
+    """mvnerf_pack_bwd_streams_bf16: the twelve hidden kernels transposed and rounded to bf16, in the order the backward walk reads them
+    (uint8 tensor of mvnerf_bwd_streams_bf16_bytes())."""
+    _chk(net_keras, 'net_keras', shape=(NET_PARAMS,))
+    out = torch.empty(int(_lib.lib().mvnerf_bwd_streams_bf16_bytes()), dtype=torch.uint8, device=net_keras.device)
+    with torch.cuda.device(net_keras.device):
+        _lib.check(_lib.lib().mvnerf_pack_bwd_streams_bf16(_p(net_keras), _p(out), _stream(net_keras)), 'pack_bwd_streams_bf16')
+    return out
+
+
+def _chk_bytes(t, name, nbytes):
+    _chk(t, name, dtype=torch.uint8)
+    if t.numel() < nbytes:
+        raise ValueError(f'{name}: {t.numel()} bytes, need {nbytes}')
+    return t
+
+
+def query_stash_bf16(points, dirs, images, features, intrinsics, extrinsics_inv, packed_net, packed16, relu_bits=None):
+    """mvnerf_query_stash_bf16: the trunk on query points with its hidden layers on the bf16 MFMA -> (acts (4,B,N,128) = view mean, u1, u2,
+    u3; relu_bits: one bit per pre-activation, what trunk_vjp_bf16 / query_vjp_bf16 need of this forward)."""
+    b, v, n, h, w = _query_shapes(points, dirs, images, features, intrinsics, extrinsics_inv)
+    _chk(packed_net, 'packed_net', shape=(packed_net_floats(),))
+    _chk(packed16, 'packed16', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_packed_net_bf16_bytes()),))
+    dev = points.device
+    if relu_bits is None:
+        relu_bits = torch.empty(relu_bits_bytes(b, v, n), dtype=torch.uint8, device=dev)
+    else:
+        _chk_bytes(relu_bits, 'relu_bits', relu_bits_bytes(b, v, n))
+    acts = torch.empty((4, b, n, 128), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(_lib.lib().mvnerf_query_workspace_bytes(b, v, n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().mvnerf_query_stash_bf16(_p(points), _p(dirs), _p(images), _p(features), _p(intrinsics), _p(extrinsics_inv),
+                                                _p(packed_net), _p(packed16), b, v, n, h, w, _p(acts), _p(relu_bits), _p(ws), _stream(points))
+    _lib.check(rc, 'query_stash_bf16')
+    return acts, relu_bits
+
+
+def unpack_relu_bits(bits, b, v, n):
+    """relu_bits of query_stash_bf16 on (b, n) points, v views -> bool (b, 6 v + 6, n, 128) in feature order: per view x0, h1, x1, h2, x2,
+    h3, then mean, h4, x4, h5, x5, h6 (the layout: include/mvnerf_hip.h).  For tests; any device."""
+    if bits.dtype != torch.uint8 or bits.numel() < (-(-b * n // 32)) * (v + 1) * 6 * 512:
+        raise ValueError('bits: expected the uint8 tensor of query_stash_bf16 for these sizes')
+    if v > 1 and n % 32:
+        raise ValueError(f'n = {n} must be a multiple of 32 when v > 1')
+    n_tiles = -(-b * n // 32)
+    words = bits[:n_tiles * (v + 1) * 6 * 512].view(torch.int64).reshape(-1, 6, 2, 32)              # [tile][slot][h][j]
+    k = torch.arange(64, device=bits.device)
+    on = ((words[..., None] >> k) & 1).bool().reshape(-1, 6, 2, 32, 4, 4, 4)                          # ... [nb][q][c]: bit 16 nb + 4 q + c
+    rows = on.permute(0, 1, 3, 4, 5, 2, 6).reshape(-1, 6, 32, 128)                                    # feature 32 nb + 8 q + 4 h + c
+    view, fused = rows[:n_tiles * v], rows[n_tiles * v:]
+    if v == 1:                                             # tiles run over the flat b * n points
+        flat = lambda t: t.permute(1, 0, 2, 3).reshape(6, -1, 128)[:, :b * n].reshape(6, b, n, 128).permute(1, 0, 2, 3)
+        return torch.cat([flat(view), flat(fused)], 1).contiguous()
+    view = view.reshape(b, v, n // 32, 6, 32, 128).permute(0, 1, 3, 2, 4, 5).reshape(b, v * 6, n, 128)
+    fused = fused.reshape(b, n // 32, 6, 32, 128).permute(0, 2, 1, 3, 4).reshape(b, 6, n, 128)
+    return torch.cat([view, fused], 1).contiguous()
+
+
+def trunk_vjp_bf16(bwd16, relu_bits, g_acts, v):
+    """mvnerf_trunk_vjp_bf16: cotangents (4,B,N,128) -> g0 (view tiles, 128, 32) = dL/d(layer-0 output) in tile layout: the twelve
+    hidden layers' backward as one launch on the bf16 MFMA."""
+    _chk(g_acts, 'g_acts', shape=(4, None, None, 128))
+    _, b, n, _ = g_acts.shape
+    _chk(bwd16, 'bwd16', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_bwd_streams_bf16_bytes()),))
+    _chk_bytes(relu_bits, 'relu_bits', relu_bits_bytes(b, v, n))
+    g0 = torch.empty((-(-b * n // 32) * v, 128, 32), dtype=torch.float32, device=g_acts.device)
+    with torch.cuda.device(g_acts.device):
+        rc = _lib.lib().mvnerf_trunk_vjp_bf16(_p(bwd16), _p(relu_bits), _p(g_acts), b, v, n, _p(g0), _stream(g_acts))
+    _lib.check(rc, 'trunk_vjp_bf16')
+    return g0
+
+
+def query_vjp_bf16(points, dirs, images, features, intrinsics, extrinsics_inv, bwd_streams, bwd16, relu_bits, g_acts):
+    """mvnerf_query_vjp_bf16: cotangents (4,B,N,128) -> (d_points, d_dirs), each (B,N,3): trunk_vjp_bf16, then the fp32 layer-0 pass of
+    query_vjp (bwd_streams: pack_bwd_streams, its layer-0 slabs)."""
+    b, v, n, h, w = _query_shapes(points, dirs, images, features, intrinsics, extrinsics_inv)
+    _chk(g_acts, 'g_acts', shape=(4, b, n, 128))
+    _chk(bwd_streams, 'bwd_streams', shape=(15 * 16384,))
+    _chk(bwd16, 'bwd16', dtype=torch.uint8, shape=(int(_lib.lib().mvnerf_bwd_streams_bf16_bytes()),))
+    _chk_bytes(relu_bits, 'relu_bits', relu_bits_bytes(b, v, n))
+    dev = points.device
+    d_points = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+    d_dirs = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+    scratch = torch.empty(int(_lib.lib().mvnerf_query_vjp_bf16_scratch_bytes(b, v, n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().mvnerf_query_vjp_bf16(_p(points), _p(dirs), _p(images), _p(features), _p(intrinsics), _p(extrinsics_inv),
+                                              _p(bwd_streams), _p(bwd16), _p(relu_bits), _p(g_acts), b, v, n, h, w, _p(scratch),
+                                              _p(d_points), _p(d_dirs), _stream(points))
+    _lib.check(rc, 'query_vjp_bf16')
     return d_points, d_dirs
 
 
