@@ -1,5 +1,6 @@
 """Bit identity of two builds of libmvnerf_hip.so on the calls whose host side orchestrates several launches: the training step, the
-field backward alone, the query JVP / VJP / fused activations, the grasp-pose optimisation step and the LanguageNeRF training step.
+field backward alone, the query JVP / VJP / fused activations, the grasp-pose optimisation step and the LanguageNeRF training step;
+and on the forward field kernels that share the sample front end of mvnerf_field_common.h (forward_legs), with every optional output.
 Each library runs in a fresh process (MVNERF_LIB) on the same seeded inputs and prints one SHA-256 per output array; the first library
 runs --repeat times, which shows the arrays that are not reproducible from run to run at all (mvnerf_query_vjp sums over the views with
 unordered atomics when V > 1, and so does the texel scatter of d_features; with few points a sum has only a few outcomes, hence several
@@ -42,6 +43,9 @@ def child(path, only):
         if a.nbytes > (8 << 20):                                             # a stash: its digest stands for it
             a = np.frombuffer(hashlib.sha256(a.tobytes()).digest(), dtype=np.uint8).copy()
         out[name] = a
+
+    if only != 'steps':
+        forward_legs(keep, dev)
 
     # ---- mvnerf_loss_and_grads / mvnerf_train_step, and mvnerf_field_backward alone on the same scenes ----
     for b, v, full in ((1, 1, False), (2, 2, True)):
@@ -178,6 +182,50 @@ def child(path, only):
     np.savez(path, **out)
     for k, a in out.items():
         print(f'{hashlib.sha256(a.tobytes()).hexdigest()[:16]}  {k} {a.shape}')
+
+
+def forward_legs(keep, dev):
+    """field_eval, field_eval_split on the 32x32x16 kernel (both direct and through a texel table), field_eval_bf16 (direct) and query_jvp
+    on 16x16 maps, B = 2, R = 5, S = 40: 400 samples = 12 whole tiles and one of 16 samples, tiles that straddle rays and the two scenes.
+    The stash form with V = 2 needs whole tiles per scene (R * S % 32 == 0): it runs on the first four rays; its stash is zeroed first,
+    since a pass leaves the slots nothing reads unwritten."""
+    import torch
+
+    from thesis_clip_nerf_amd import ops
+    from thesis_clip_nerf_amd.synthetic import make_scene
+    k32 = 'split_bf16_32x32x16'
+    for v in (1, 2):
+        sc = make_scene(seed=70 + v, batch=2, n_views=v, height=16, width=16, n_rays=5, n_samples=40, bias_scale=0.05)
+        d = {k: dev(sc[k]) for k in ('rays_o', 'rays_d', 'images', 'features', 'intrinsics', 'extrinsics_inv', 'fine', 'u_coarse')}
+        z = ops.stratified_depths(d['u_coarse'], sc['near'], sc['far'])
+        scene = (d['images'], d['features'], d['intrinsics'], d['extrinsics_inv'])
+        geo = (d['rays_o'], d['rays_d'], z) + scene
+        packed, split, packed16 = ops.pack_net(d['fine']), ops.pack_net_split(d['fine']), ops.pack_net_bf16(d['fine'])
+        table = ops.project_texels(d['features'], packed)
+        wide = dict(return_taps=True, return_pix=True, return_embedding=True, complete_output=True)
+
+        def keep_all(leg, res, names):
+            for name, t in zip(names, res):
+                for i, x in enumerate(t if isinstance(t, list) else [t]):
+                    keep(f'forward V{v} {leg} {name}{i if isinstance(t, list) else ""}', x)
+
+        for form, tab in (('direct', None), ('table', table)):
+            keep_all(f'field_eval {form}', ops.field_eval(*geo, packed, texel_table=tab, **wide), ('rgbs', 'tap_idx', 'pix', 'embedding', 'acts'))
+            keep_all(f'field_eval_split {form}', ops.field_eval_split(*geo, packed, split, texel_table=tab, kernel=k32, **wide),
+                     ('rgbs', 'tap_idx', 'pix', 'embedding', 'acts'))
+            r = 5 if v == 1 else 4
+            sgeo = (d['rays_o'][:, :r].contiguous(), d['rays_d'][:, :r].contiguous(), z[:, :r].contiguous()) + scene
+            zeroed = lambda: torch.zeros(ops.stash_bytes(2, v, r, 40), dtype=torch.uint8, device=DEV)
+            keep_all(f'field_eval_stash {form}', ops.field_eval_stash(*sgeo, packed, stash=zeroed(), texel_table=tab), ('rgbs', 'stash'))
+            keep_all(f'field_eval_stash split {form}', ops.field_eval_stash(*sgeo, packed, stash=zeroed(), texel_table=tab, packed_split=split,
+                                                                            kernel=k32), ('rgbs', 'stash'))
+        keep_all('field_eval_bf16 direct', ops.field_eval_bf16(*geo, packed, packed16, return_taps=True, return_embedding=True, return_fused_acts=True),
+                 ('rgbs', 'tap_idx', 'embedding', 'fused_acts'))
+        rng = np.random.default_rng(31 + v)
+        points = ops.points_on_rays(d['rays_o'], d['rays_d'], z).reshape(2, 200, 3).contiguous()
+        dirs = d['rays_d'].repeat_interleave(40, dim=1).contiguous()
+        tp, td = (dev(rng.standard_normal((2, 200, 3)).astype(np.float32) * 1e-2) for _ in range(2))
+        keep_all('query_jvp', ops.query_jvp(points, dirs, tp, td, *scene, packed, return_primal=True), ('t_acts', 'acts'))
 
 
 def run(lib_path, out_path):

@@ -69,17 +69,10 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * kWaves, kMultiView ? kMvOcc
     const long tile = (long)blockIdx.x * (blockDim.x >> 6) + wave;   // one 32-sample tile per wave
     if (tile >= p.n_tiles) return;                       // whole wave leaves; there are no barriers
 
-    long g = tile * kTile + j;
-    const bool valid = g < p.total;
-    if (!valid) g = p.total - 1;
-    const int ray = (int)(g / p.S);                      // global ray index in [0, B*R)
-    const int sidx = (int)(g - (long)ray * p.S);
-    const int b = ray / p.R;
-
-    const float ox = p.rays_o[3 * ray + 0], oy = p.rays_o[3 * ray + 1], oz = p.rays_o[3 * ray + 2];
-    const float dx = p.rays_d[3 * ray + 0], dy = p.rays_d[3 * ray + 1], dz = p.rays_d[3 * ray + 2];
-    const float zz = p.z[g];
-    const float wx = ox + zz * dx, wy = oy + zz * dy, wz = oz + zz * dz;     // mul, then add (no FMA)
+    const LaneSample sm = lane_sample(p, tile, true, j);
+    const long g = sm.g;
+    const bool valid = sm.valid;
+    const int b = sm.b;
 
     const float* __restrict__ net = p.net;
 
@@ -90,63 +83,18 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * kWaves, kMultiView ? kMvOcc
     for (int v = 0; v < p.V; ++v) {
         ws_begin(ws, net, kPackTotal * 4, lane);                         // layer-0 group 0 (re-read per view)
         const int bv = b * p.V + v;
-        const float* E = p.einv + 16 * bv;
-        const float* K = p.k4 + 16 * bv;
-        float cam[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) cam[r] = row_dot4(E, r, wx, wy, wz, 1.0f);
-        float pxl, pyl;
-        pixel_from_cam(K, cam, &pxl, &pyl);
-        const Taps tp = bilinear_taps(pxl, pyl, p.H, p.W);
-        const int tl = (bv * p.H + tp.y0) * p.W + tp.x0;
-        const long vrow = ((long)bv * p.R + (ray - b * p.R)) * p.S + sidx;       // row in a (B*V,R,S,..) tensor
+        const ViewSample vs = view_sample(p, sm, bv);
         if (valid && h == 0) {
-            if (p.tap_idx) {
-                int4 t4 = make_int4(tl, tl + 1, tl + p.W, tl + p.W + 1);
-                *reinterpret_cast<int4*>(p.tap_idx + 4 * vrow) = t4;
-            }
-            if (p.pix) {
-                p.pix[2 * vrow + 0] = pxl;
-                p.pix[2 * vrow + 1] = pyl;
-            }
+            store_tap_idx(p, vs);
+            store_pix(p, vs);
         }
 
         // ---- layer 0: Dense 379 -> 128 on [PE(cam xyz) | PE(cam dir) | 2*rgb-1 | features] ----
         // accumulator seed = b0 + W0_dir^T PE(cam dir) of this lane's (view, ray), from dir_bias_kernel
-        bias_to_acc<false>(p.dir_bias + 128 * ((long)bv * p.R + (ray - b * p.R)), h, x);
+        bias_to_acc<false>(p.dir_bias + 128 * vs.vray, h, x);
         float pe[32];                                     // B operands of k-steps 0..31 (lower half sin, upper cos)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float a0 = cam[d] * 3.14159274101257324f;
-            float sk = 0.0f, ck = 0.0f;
-#pragma unroll
-            for (int k = 0; k < kNFreq; ++k) {
-                // fl32(x * fl32(pi*2^k)) == 2^k * fl32(x * fl32(pi)) exactly, so octave k is the k-fold double
-                // angle of octave 0.  Accurate sin/cos at k = 0 and k = 5, double-angle steps in between (error
-                // x16 at most: ~2e-6 absolute against the 1e-4 bar; the op-level position_encoding is exact).
-                if (k == 0 || k == 5) {
-                    sincos_f32(a0 * (float)(1 << k), &sk, &ck);
-                } else {
-                    const float s2 = sk + sk;
-                    const float cn = fmaf(-s2, sk, 1.0f);              // cos 2t = 1 - 2 sin^2 t
-                    sk = s2 * ck;                                      // sin 2t = 2 sin t cos t
-                    ck = cn;
-                }
-                pe[d * 10 + k] = h ? ck : sk;
-            }
-        }
-        {   // rgb taps of this lane's own sample, normalised 2*img-1 before the lerp (model_v0.py:120)
-            const float* img = p.images + 3 * (long)tl;
-            float rgbv[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float a = img[c] * 2.0f - 1.0f, bq = img[3 + c] * 2.0f - 1.0f;
-                const float cq = img[3 * p.W + c] * 2.0f - 1.0f, dq = img[3 * p.W + 3 + c] * 2.0f - 1.0f;
-                rgbv[c] = bilerp(a, bq, cq, dq, tp.ax, tp.ay);
-            }
-            pe[30] = h ? rgbv[1] : rgbv[0];
-            pe[31] = h ? 0.0f : rgbv[2];
-        }
+        pe_cam_xyz(vs.cam, h, pe);
+        rgb_inputs(p.images, vs.tl, p.W, vs.tp, h, pe);
 #pragma unroll
         for (int gq = 0; gq < 8; ++gq) {
             const float bb[4] = {pe[4 * gq], pe[4 * gq + 1], pe[4 * gq + 2], pe[4 * gq + 3]};
@@ -159,18 +107,11 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * kWaves, kMultiView ? kMvOcc
 #pragma unroll 4
             for (int it = 0; it < 16; ++it) {
                 const int src = 2 * it + h;                           // sample whose 4 table rows this half-wave loads
-                const int tls = __shfl(tl, src);
-                const float axs = __shfl(tp.ax, src), ays = __shfl(tp.ay, src);
+                const int tls = __shfl(vs.tl, src);
+                const float axs = __shfl(vs.tp.ax, src), ays = __shfl(vs.tp.ay, src);
                 const f32x4* f = tbase + (long)tls * 32;
                 const f32x4 vtl = f[0], vtr = f[32], vbl = f[(long)p.W * 32], vbr = f[(long)p.W * 32 + 32];
-                f32x4 o;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float top = fmaf(axs, vtr[c] - vtl[c], vtl[c]);
-                    const float bot = fmaf(axs, vbr[c] - vbl[c], vbl[c]);
-                    o[c] = fmaf(ays, bot - top, top);
-                }
-                *reinterpret_cast<f32x4*>(stage + stage_offset(src, j)) = o;
+                *reinterpret_cast<f32x4*>(stage + stage_offset(src, j)) = lerp_taps(vtl, vtr, vbl, vbr, axs, ays);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // table rows are in accumulator order [h][nb][r]: chunk 16h + 4nb + q of row j = registers 4q..4q+3 of block nb
@@ -190,20 +131,11 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * kWaves, kMultiView ? kMvOcc
 #pragma unroll 4
             for (int it = 0; it < 16; ++it) {
                 const int src = 2 * it + h;                           // sample whose row this half-wave loads
-                const int tls = __shfl(tl, src);
-                const float axs = __shfl(tp.ax, src), ays = __shfl(tp.ay, src);
+                const int tls = __shfl(vs.tl, src);
+                const float axs = __shfl(vs.tp.ax, src), ays = __shfl(vs.tp.ay, src);
                 const f32x4* f = fbase + (long)tls * 64;
                 const f32x4 vtl = f[0], vtr = f[64], vbl = f[(long)p.W * 64], vbr = f[(long)p.W * 64 + 64];
-                f32x4 o;
-                // same bilinear form as tfa (lerp x, then y), each lerp as one FMA after the difference (6 instead of 9 vector
-                // instructions per channel)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float top = fmaf(axs, vtr[c] - vtl[c], vtl[c]);
-                    const float bot = fmaf(axs, vbr[c] - vbl[c], vbl[c]);
-                    o[c] = fmaf(ays, bot - top, top);
-                }
-                *reinterpret_cast<f32x4*>(stage + stage_offset(src, j)) = o;
+                *reinterpret_cast<f32x4*>(stage + stage_offset(src, j)) = lerp_taps(vtl, vtr, vbl, vbr, axs, ays);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // writes landed (same-wave DS order)
 #pragma unroll
@@ -214,18 +146,17 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * kWaves, kMultiView ? kMvOcc
             }
         }
 
-        // training mode: view tile index (all 32 samples of a tile share b because R*S % 32 == 0 when V > 1)
-        const long vtile = kMultiView ? ((long)bv * (p.n_tiles / p.B) + (tile - (long)b * (p.n_tiles / p.B))) : tile;
+        const long vtile = kMultiView ? view_tile(p, tile, b, bv) : tile;              // training mode
         if (kStash) store_tl(p.stash, vtile, j, h, x);       // per-view slot 0: layer-0 output
         // ---- per-view feature blocks (layers.py:365-366); optional complete_output taps (:376-377) ----
         const long vslot = (long)p.B * p.V * p.R * p.S * 128;
-        if (p.acts_view && valid) store_acc(p.acts_view + 128 * vrow, h, x);
+        if (p.acts_view && valid) store_acc(p.acts_view + 128 * vs.vrow, h, x);
 #pragma unroll 1
         for (int bi = 0; bi < 3; ++bi) {
             resnet_block<kStash>(ws, net + kPackBHidden + 256 * bi, h, x, hid,
                                  kStash ? p.stash + (1 + 2 * bi) * p.stash_stride : nullptr, p.stash_stride, vtile, j,
                                  bi < 2);                               // per-view slot 6 = x3 is not written: nothing reads it
-            if (p.acts_view && valid) store_acc(p.acts_view + (bi + 1) * vslot + 128 * vrow, h, x);
+            if (p.acts_view && valid) store_acc(p.acts_view + (bi + 1) * vslot + 128 * vs.vrow, h, x);
         }
 
         if (kMultiView) {                                             // reduce_mean over views (layers.py:368-370)
@@ -272,14 +203,7 @@ __global__ __launch_bounds__(kMultiView ? 256 : 64 * kWaves, kMultiView ? kMvOcc
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = (o[k] + __shfl_xor(o[k], 32)) + net[kPackBr + k];
     }
-    if (valid && h == 0) {
-        f32x4 out;
-        out[0] = sigmoid_f32(o[0]);
-        out[1] = sigmoid_f32(o[1]);
-        out[2] = sigmoid_f32(o[2]);
-        out[3] = softplus_f32(o[3]);
-        *reinterpret_cast<f32x4*>(p.rgbs + 4 * g) = out;
-    }
+    if (valid && h == 0) store_readout(p.rgbs, g, o[0], o[1], o[2], o[3]);
 }
 
 // ---- per-(view, ray) layer-0 seed (dir_seed_row, mvnerf_field_common.h): one wavefront per (b*V+v, ray) ----

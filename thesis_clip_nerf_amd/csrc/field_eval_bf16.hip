@@ -20,7 +20,7 @@
 
 #include <cstdlib>
 
-
+#include "mvnerf_field_common.h"
 #include "mvnerf_kernels.h"
 #include "mvnerf_launch.h"
 #include "mvnerf_math.h"
@@ -237,29 +237,6 @@ __device__ __forceinline__ void store_relu_bits(unsigned long long* dst, const f
     *dst = (unsigned long long)w[0] | ((unsigned long long)w[1] << 32);
 }
 
-template <bool kAdd>
-__device__ __forceinline__ void bias_acc(const float* __restrict__ bperm, int h, f32x16 (&acc)[4]) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(bperm + h * 64);
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = p[nb * 4 + q];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (kAdd) {
-                    // scalar adds on purpose: left to the compiler these become v_pk_add_f32, which costs the matrix pipe
-                    // of the partner wave far more than two v_add_f32 (MI355X_MICROARCH.md, price of fillers beside MFMAs)
-                    float r = acc[nb][4 * q + c];
-                    asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(r), "v"(v[c]));
-                    acc[nb][4 * q + c] = r;
-                } else {
-                    acc[nb][4 * q + c] = v[c];
-                }
-            }
-        }
-}
-
 constexpr int kStage16Row = 256;      // bytes per staged sample row: 128 channels x bf16
 
 // kProj: layer 0's feature rows come from the fp32 texel table (field_eval.hip, project_texels_kernel): a 128-channel
@@ -300,70 +277,25 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
         long tile = grp * kWgWaves + wave;
         const bool tile_ok = tile < p.n_tiles;
         if (!tile_ok) tile = p.n_tiles - 1;                               // idle waves shadow the last tile, no stores
-        long g = tile * 32 + j;
-        const bool valid = tile_ok && g < p.total;
-        if (g >= p.total) g = p.total - 1;
-        const int ray = (int)(g / p.S);
-        const int sidx = (int)(g - (long)ray * p.S);
-        const int b = ray / p.R;
-        const float ox = p.rays_o[3 * ray + 0], oy = p.rays_o[3 * ray + 1], oz = p.rays_o[3 * ray + 2];
-        const float dx = p.rays_d[3 * ray + 0], dy = p.rays_d[3 * ray + 1], dz = p.rays_d[3 * ray + 2];
-        const float zz = p.z[g];
-        const float wx = ox + zz * dx, wy = oy + zz * dy, wz = oz + zz * dz;
+        const LaneSample sm = lane_sample(p, tile, tile_ok, j);
+        const long g = sm.g;
+        const bool valid = sm.valid;
+        const int b = sm.b;
 
         f32x16 x[4], hid[4];
         f32x16 xsum[kMultiView ? 4 : 1];
 
         for (int v = 0; v < p.V; ++v) {
             const int bv = b * p.V + v;
-            const float* E = p.einv + 16 * bv;
-            float cam[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) cam[r] = row_dot4(E, r, wx, wy, wz, 1.0f);
-            float pxl, pyl;
-            pixel_from_cam(p.k4 + 16 * bv, cam, &pxl, &pyl);
-            const Taps tp = bilinear_taps(pxl, pyl, p.H, p.W);
-            const int tl = (bv * p.H + tp.y0) * p.W + tp.x0;
-            const long vrow = ((long)bv * p.R + (ray - b * p.R)) * p.S + sidx;
-            // S = 1, whole tiles per scene when V > 1: the view tile of StashLayout, (b V + v) tiles_per_b + k
-            const long view_tile = kMultiView ? tile + ((long)b * (p.V - 1) + v) * (p.n_tiles / p.B) : tile;
-            if (valid && h == 0 && p.tap_idx) {
-                int4 t4 = make_int4(tl, tl + 1, tl + p.W, tl + p.W + 1);
-                *reinterpret_cast<int4*>(p.tap_idx + 4 * vrow) = t4;
-            }
+            const ViewSample vs = view_sample(p, sm, bv);
+            const long vtile = kMultiView ? view_tile(p, tile, b, bv) : tile;      // (S = 1, whole tiles per scene when V > 1)
+            if (valid && h == 0) store_tap_idx(p, vs);
 
             // ---- segment: PE(cam xyz) + rgb k-steps ----
-            bias_acc<false>(p.dir_bias + 128 * ((long)bv * p.R + (ray - b * p.R)), h, x);
+            bias_acc<false>(p.dir_bias + 128 * vs.vray, h, x);
             float pe[32];
-            {
-                const float* img = p.images + 3 * (long)tl;
-                float rgbv[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float a = img[c] * 2.0f - 1.0f, bq = img[3 + c] * 2.0f - 1.0f;
-                    const float cq = img[3 * p.W + c] * 2.0f - 1.0f, dq = img[3 * p.W + 3 + c] * 2.0f - 1.0f;
-                    rgbv[c] = bilerp(a, bq, cq, dq, tp.ax, tp.ay);
-                }
-                pe[30] = h ? rgbv[1] : rgbv[0];
-                pe[31] = h ? 0.0f : rgbv[2];
-            }
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const float a0 = cam[d] * 3.14159274101257324f;
-                float sk = 0.0f, ck = 0.0f;
-#pragma unroll
-                for (int k = 0; k < kNFreq; ++k) {
-                    if (k == 0 || k == 5) {
-                        sincos_f32(a0 * (float)(1 << k), &sk, &ck);
-                    } else {
-                        const float s2 = sk + sk;
-                        const float cn = fmaf(-s2, sk, 1.0f);
-                        sk = s2 * ck;
-                        ck = cn;
-                    }
-                    pe[d * 10 + k] = h ? ck : sk;
-                }
-            }
+            rgb_inputs(p.images, vs.tl, p.W, vs.tp, h, pe);
+            pe_cam_xyz(vs.cam, h, pe);
 #pragma unroll
             for (int seg = 0; seg < 4 / kKs; ++seg) {
                 segment_mfma(ring, lane, [&](int ks) {
@@ -391,9 +323,9 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int src = 4 * (it0 + u) + sub;
-                            const int tls = __shfl(tl, src);
-                            axs[u] = __shfl(tp.ax, src);
-                            ays[u] = __shfl(tp.ay, src);
+                            const int tls = __shfl(vs.tl, src);
+                            axs[u] = __shfl(vs.tp.ax, src);
+                            ays[u] = __shfl(vs.tp.ay, src);
                             const f32x4* f = tbase + (long)tls * 32 + P * 8;
                             tv[u][0] = f[0];
                             tv[u][1] = f[32];
@@ -404,14 +336,8 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int src = 4 * (it0 + u) + sub;
-                            f32x4 o;
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) {
-                                const float top = fmaf(axs[u], tv[u][1][c] - tv[u][0][c], tv[u][0][c]);
-                                const float bot = fmaf(axs[u], tv[u][3][c] - tv[u][2][c], tv[u][2][c]);
-                                o[c] = fmaf(ays[u], bot - top, top);
-                            }
-                            *reinterpret_cast<f32x4*>(stage + src * kStage16Row + ((l16 ^ (src & 15)) << 4)) = o;
+                            *reinterpret_cast<f32x4*>(stage + src * kStage16Row + ((l16 ^ (src & 15)) << 4)) =
+                                lerp_taps(tv[u][0], tv[u][1], tv[u][2], tv[u][3], axs[u], ays[u]);
                         }
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -448,9 +374,9 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int src = 2 * (it0 + u) + h;
-                        const int tls = __shfl(tl, src);
-                        axs[u] = __shfl(tp.ax, src);
-                        ays[u] = __shfl(tp.ay, src);
+                        const int tls = __shfl(vs.tl, src);
+                        axs[u] = __shfl(vs.tp.ax, src);
+                        ays[u] = __shfl(vs.tp.ay, src);
                         if (kF16) {
                             const u32x2* f = fbase16 + (long)tls * 64;
                             tv[u][0] = widen(f[0]);
@@ -469,13 +395,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int src = 2 * (it0 + u) + h;
-                        f32x4 o;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            const float top = fmaf(axs[u], tv[u][1][c] - tv[u][0][c], tv[u][0][c]);
-                            const float bot = fmaf(axs[u], tv[u][3][c] - tv[u][2][c], tv[u][2][c]);
-                            o[c] = fmaf(ays[u], bot - top, top);
-                        }
+                        const f32x4 o = lerp_taps(tv[u][0], tv[u][1], tv[u][2], tv[u][3], axs[u], ays[u]);
                         // row `src`, channels 4j..4j+3 (8 bytes); 16-byte chunks XOR-swizzled by the row
                         const int off = src * kStage16Row + (((j >> 1) ^ (src & 15)) << 4) + ((j & 1) << 3);
                         *reinterpret_cast<bf16x4*>(stage + off) = __builtin_convertvector(o, bf16x4);
@@ -497,10 +417,10 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
             for (int bi = 0; bi < 3; ++bi) {
                 const float* bias1 = net + kPackBHidden + 256 * bi;
                 bias_acc<false>(bias1, h, hid);
-                if (kBits && tile_ok) store_relu_bits(bits.view(view_tile, 2 * bi, lane), x);
+                if (kBits && tile_ok) store_relu_bits(bits.view(vtile, 2 * bi, lane), x);
                 dense128_bf16<kBits>(ring, lane, x, hid);
                 bias_acc<true>(bias1 + 128, h, x);
-                if (kBits && tile_ok) store_relu_bits(bits.view(view_tile, 2 * bi + 1, lane), hid);
+                if (kBits && tile_ok) store_relu_bits(bits.view(vtile, 2 * bi + 1, lane), hid);
                 dense128_bf16<kBits>(ring, lane, hid, x);
             }
             if (kMultiView) {
@@ -514,18 +434,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
             for (int nb = 0; nb < 4; ++nb) x[nb] = xsum[nb] / nv;
         }
 
-        // one sample row (128 floats) from the accumulators: lane (j,h) holds features 32nb + 8q + 4h + {0..3}
-        auto store_row = [&](float* base) {
-            float* e = base + 128 * g + 4 * h;
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x4 v4 = {x[nb][4 * q], x[nb][4 * q + 1], x[nb][4 * q + 2], x[nb][4 * q + 3]};
-                    *reinterpret_cast<f32x4*>(e + 32 * nb + 8 * q) = v4;
-                }
-        };
-        if (p.acts_fused && valid) store_row(p.acts_fused);                // complete_output: the view mean
+        if (p.acts_fused && valid) store_acc(p.acts_fused + 128 * g, h, x);                // complete_output: the view mean
         // ---- 12 segments: fusion blocks ----
 #pragma unroll 1
         for (int bi = 3; bi < 6; ++bi) {
@@ -536,9 +445,9 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
             bias_acc<true>(bias1 + 128, h, x);
             if (kBits && tile_ok) store_relu_bits(bits.fused(tile, 2 * (bi - 3) + 1, lane), hid);
             dense128_bf16<kBits>(ring, lane, hid, x);
-            if (p.acts_fused && valid) store_row(p.acts_fused + (long)(bi - 2) * p.total * 128);
+            if (p.acts_fused && valid) store_acc(p.acts_fused + (long)(bi - 2) * p.total * 128 + 128 * g, h, x);
         }
-        if (p.embedding && valid) store_row(p.embedding);
+        if (p.embedding && valid) store_acc(p.embedding + 128 * g, h, x);
 
         // ---- segment: read-out ----
         f32x16 o;
@@ -554,14 +463,7 @@ __global__ __launch_bounds__(64 * kWgWaves, 2) void field_eval_bf16_kernel(Field
                     o = mfma16(a, relu_to_bf16(x[kb], s), o);
                 }
         }
-        if (valid && h == 0) {
-            f32x4 out;
-            out[0] = sigmoid_f32(o[0]);
-            out[1] = sigmoid_f32(o[1]);
-            out[2] = sigmoid_f32(o[2]);
-            out[3] = softplus_f32(o[3]);
-            *reinterpret_cast<f32x4*>(p.rgbs + 4 * g) = out;
-        }
+        if (valid && h == 0) store_readout(p.rgbs, g, o[0], o[1], o[2], o[3]);
         ring_next<true, FwdStream>(ring);                                           // stores above: drain
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                     // DMA still in flight must land before the LDS is released

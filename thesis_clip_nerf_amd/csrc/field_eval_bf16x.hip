@@ -23,10 +23,6 @@ namespace mvnerf {
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x8 = __attribute__((ext_vector_type(8))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
-
 // ---- weight stream: 13 positions of 32 chunks (1 KiB = [lane][8 bf16]); chunk (t, rb) of a position at index 8 t + rb ------------------
 //   position 0      : layer 0, PE(cam xyz) + rgb: t = 0, 1 (slot e = 8 t + jj of lane group g: field_eval_split16.hip, s16_pe_row); t = 2, 3 zero
 //   position 1 + l  : hidden layer l: input 32 t + 4 g + jj (jj < 4) | 32 t + 16 + 4 g + jj - 4

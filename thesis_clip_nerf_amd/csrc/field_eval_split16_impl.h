@@ -75,11 +75,7 @@ namespace mvnerf {
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
 // ---- weight stream: 1 KiB chunks [lane][8 bf16]; chunk = 24 * kstep + 3 * rb + piece ------------------------------------
 //   k-steps 0..1  : layer 0, PE(cam xyz) + rgb: lane group g, slot e = 8 t + jj (16 slots per group)

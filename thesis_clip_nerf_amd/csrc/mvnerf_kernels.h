@@ -138,7 +138,7 @@ hipError_t launch_readout(const float* emb, const float* wr, const float* br, lo
 hipError_t launch_finish_view(const float* rgb, const float* depth, long n, float* minmax, uint8_t* rgb8, uint8_t* depth8,
                               hipStream_t st);
 
-// train_ops.hip
+// gemm_ops.hip
 hipError_t launch_gemm_nt_f32(const float* A, const float* Bt, const float* bias, float* C, int M, int N, int K, float* scratch,
                               hipStream_t st);   // bias: N floats added to every row, or nullptr
 int gemm_nt_splits(int M, int N, int K);
@@ -153,6 +153,8 @@ struct TnBatchArgs {
 size_t gemm_tn_batched_scratch_floats(int M, int N, int K, int batch, bool colsum);
 hipError_t launch_gemm_tn_batched(const TnBatchArgs& a, float* C, float* colsum, int M, int N, int K, int batch, float* scratch, hipStream_t st);
 int gemm_tn_splits(int M, int N, int K);
+
+// train_ops.hip
 hipError_t launch_pack_bwd_streams(const float* net_keras, float* dst, hipStream_t st);
 hipError_t launch_field_dz(const FieldParams& p, const float* g0_tl, const float* w0t_streams, float* d_z, float* d_o,
                            float* d_d, float* d_features, hipStream_t st);

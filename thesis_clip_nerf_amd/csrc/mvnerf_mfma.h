@@ -10,7 +10,12 @@
 namespace mvnerf {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+using f32x8 = __attribute__((ext_vector_type(8))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -43,7 +48,6 @@ struct WStream {
 // scalar offset and the chunk index in the immediate, so a step costs no VALU address arithmetic.
 template <int kImm>
 __device__ __forceinline__ f32x4 ws_load(const WStream& ws, int pos) {
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
     const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(ws.rsrc, ws.voff + kImm, pos, 0);
     return __builtin_bit_cast(f32x4, r);
 }
@@ -84,6 +88,12 @@ __device__ __forceinline__ void mfma_step(WStream& ws, const float (&b)[4], f32x
     ws_advance(ws, n0, n1, n2, n3);
 }
 
+__device__ __forceinline__ void zero_acc(f32x16 (&a)[4]) {
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a[nb][r] = 0.0f;
+}
 
 // ---- tile layout (TL): a (rows, F) activation matrix stored as [tile = row/32][feature][row%32], so that
 // "lane = sample" accesses are 128-B contiguous per feature and "lane = feature" accesses read 4 samples as

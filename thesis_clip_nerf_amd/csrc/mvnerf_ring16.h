@@ -10,9 +10,6 @@
 
 namespace mvnerf {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x8 = __attribute__((ext_vector_type(8))) float;
-
 // ---- the segment ring ----------------------------------------------------------------------------------------
 // A workgroup of kWgWaves waves shares the weight stream through a ring of kRing LDS slots of kSegChunks chunks
 // (kKs k-steps x 4 output blocks), filled by LDS-DMA, 2 wave-instructions (2 KiB) per wave and segment.

@@ -67,13 +67,6 @@ __device__ __forceinline__ float masked(float v, unsigned long long w, int nb, i
     return __builtin_bit_cast(float, __builtin_bit_cast(int, v) & bit_mask(half, 16 * (nb & 1) + r));
 }
 
-__device__ __forceinline__ void zero_acc(f32x16 (&a)[4]) {
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a[nb][r] = 0.0f;
-}
-
 // acc += A(layer) x B over the layer's 8 k-steps = 2 segments; drain_first: stores were issued since the last segment
 template <typename BFn>
 __device__ __forceinline__ void dense128_bwd(Ring& ring, int lane, BFn bfn, f32x16 (&acc)[4], bool drain_first) {

@@ -56,13 +56,6 @@ __device__ __forceinline__ void dense128_jvp(WStream& ws, const f32x16 (&in)[4],
         }
 }
 
-__device__ __forceinline__ void zero_acc(f32x16 (&a)[4]) {
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a[nb][r] = 0.0f;
-}
-
 // x <- x + W2^T relu(W1^T relu(x) + b1) + b2 and its tangent (biases have no tangent)
 __device__ __forceinline__ void resnet_block_jvp(WStream& ws, const float* __restrict__ bias1, int h, f32x16 (&x)[4],
                                                  f32x16 (&tx)[4], f32x16 (&hid)[4], f32x16 (&thid)[4]) {
@@ -179,14 +172,12 @@ __global__ __launch_bounds__(256, 1) void field_jvp_kernel(FieldParams p) {
                 const float taxs = __shfl(tax, src), tays = __shfl(tay, src);
                 const f32x4* f = fbase + (long)tls * 64;
                 const f32x4 vtl = f[0], vtr = f[64], vbl = f[(long)p.W * 64], vbr = f[(long)p.W * 64 + 64];
-                f32x4 o, ot;
+                const f32x4 o = lerp_taps(vtl, vtr, vbl, vbr, axs, ays);
+                f32x4 ot;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float dt = vtr[c] - vtl[c], db = vbr[c] - vbl[c];
-                    const float top = fmaf(axs, dt, vtl[c]);
-                    const float bot = fmaf(axs, db, vbl[c]);
-                    o[c] = fmaf(ays, bot - top, top);
-                    ot[c] = taxs * fmaf(ays, db - dt, dt) + tays * (bot - top);
+                    ot[c] = taxs * fmaf(ays, db - dt, dt) + tays * (fmaf(axs, db, vbl[c]) - fmaf(axs, dt, vtl[c]));
                 }
                 *reinterpret_cast<f32x4*>(stage + stage_offset(src, j)) = o;
                 *reinterpret_cast<f32x4*>(tstage + stage_offset(src, j)) = ot;
