@@ -599,32 +599,37 @@ def grasp_head_pack(w4, wc):
     return out
 
 
-def grasp_head_fwd(acts, packed, b4, bc):
-    """acts (4,N,128) -> c (N,256) = [elu(W_k a_k + b_k)], y (N,64) = elu(W_c c + b_c)."""
+def _head_out(out, specs, dev):
+    """The output tensors of a head pass: fresh ones, or the caller's `out` tuple checked against specs = ((name, shape), ...) in order."""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=torch.float32, device=dev) for _, shape in specs)
+    if len(out) != len(specs):
+        raise ValueError(f'out: {len(out)} tensors, expected {len(specs)} ({", ".join(nm for nm, _ in specs)})')
+    return tuple(_chk(t, 'out ' + nm, shape=shape) for t, (nm, shape) in zip(out, specs))
+
+
+def grasp_head_fwd(acts, packed, b4, bc, out=None):
+    """acts (4,N,128) -> c (N,256) = [elu(W_k a_k + b_k)], y (N,64) = elu(W_c c + b_c).  out: (c, y) to write into."""
     _chk(acts, 'acts', shape=(4, None, 128))
     n = acts.shape[1]
     _chk(packed, 'packed', shape=(int(_lib.lib().mvnerf_grasp_head_packed_floats()),))
     _chk(b4, 'b4', shape=(4, 64))
     _chk(bc, 'bc', shape=(64,))
-    c = torch.empty((n, 256), dtype=torch.float32, device=acts.device)
-    y = torch.empty((n, 64), dtype=torch.float32, device=acts.device)
+    c, y = _head_out(out, (('c', (n, 256)), ('y', (n, 64))), acts.device)
     with torch.cuda.device(acts.device):
         _lib.check(_lib.lib().mvnerf_grasp_head_fwd(_p(acts), _p(packed), _p(b4), _p(bc), n, _p(c), _p(y), _stream(acts)), 'grasp_head_fwd')
     return c, y
 
 
-def grasp_head_vjp(g_y, c, y, packed):
-    """g_y (N,64) -> g_v (N,64), q (N,256), g_u (N,256), g_acts (4,N,128)."""
+def grasp_head_vjp(g_y, c, y, packed, out=None):
+    """g_y (N,64) -> g_v (N,64), q (N,256), g_u (N,256), g_acts (4,N,128).  out: the four tensors to write into."""
     _chk(g_y, 'g_y', shape=(None, 64))
     n = g_y.shape[0]
     _chk(c, 'c', shape=(n, 256))
     _chk(y, 'y', shape=(n, 64))
     _chk(packed, 'packed', shape=(int(_lib.lib().mvnerf_grasp_head_packed_floats()),))
     dev = g_y.device
-    g_v = torch.empty((n, 64), dtype=torch.float32, device=dev)
-    q = torch.empty((n, 256), dtype=torch.float32, device=dev)
-    g_u = torch.empty((n, 256), dtype=torch.float32, device=dev)
-    g_acts = torch.empty((4, n, 128), dtype=torch.float32, device=dev)
+    g_v, q, g_u, g_acts = _head_out(out, (('g_v', (n, 64)), ('q', (n, 256)), ('g_u', (n, 256)), ('g_acts', (4, n, 128))), dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().mvnerf_grasp_head_vjp(_p(g_y), _p(c), _p(y), _p(packed), n, _p(g_v), _p(q), _p(g_u), _p(g_acts), _stream(g_y)),
                    'grasp_head_vjp')
@@ -644,8 +649,9 @@ def grasp_head_vjp_acts(g_y, c, y, packed, out=None):
     return g_acts
 
 
-def grasp_head_vjp_bwd(t_acts, g_y, c, y, q, packed):
-    """t_acts (4,N,128) = dL/d(g_acts) -> out_gy (N,64) = dL/d(g_y), r (N,256), m (N,64), p (N,256) (see include/mvnerf_hip.h)."""
+def grasp_head_vjp_bwd(t_acts, g_y, c, y, q, packed, out=None):
+    """t_acts (4,N,128) = dL/d(g_acts) -> out_gy (N,64) = dL/d(g_y), r (N,256), m (N,64), p (N,256) (see include/mvnerf_hip.h).
+    out: the four tensors to write into."""
     _chk(t_acts, 't_acts', shape=(4, None, 128))
     n = t_acts.shape[1]
     _chk(g_y, 'g_y', shape=(n, 64))
@@ -654,10 +660,7 @@ def grasp_head_vjp_bwd(t_acts, g_y, c, y, q, packed):
     _chk(q, 'q', shape=(n, 256))
     _chk(packed, 'packed', shape=(int(_lib.lib().mvnerf_grasp_head_packed_floats()),))
     dev = t_acts.device
-    out_gy = torch.empty((n, 64), dtype=torch.float32, device=dev)
-    r = torch.empty((n, 256), dtype=torch.float32, device=dev)
-    m = torch.empty((n, 64), dtype=torch.float32, device=dev)
-    p_ = torch.empty((n, 256), dtype=torch.float32, device=dev)
+    out_gy, r, m, p_ = _head_out(out, (('out_gy', (n, 64)), ('r', (n, 256)), ('m', (n, 64)), ('p', (n, 256))), dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().mvnerf_grasp_head_vjp_bwd(_p(t_acts), _p(g_y), _p(c), _p(y), _p(q), _p(packed), n, _p(out_gy), _p(r), _p(m),
                                                         _p(p_), _stream(t_acts)), 'grasp_head_vjp_bwd')
@@ -961,18 +964,28 @@ def gemm_nt_ok(m, n, k):
     return m > 0 and n > 0 and k > 0 and m % 32 == 0 and n % 64 == 0 and k % 8 == 0
 
 
-def gemm_nt(a, bt, bias=None):
+def _gemm_scratch(scratch, need, dev):
+    """The split-K partial buffer of a GEMM call: a fresh one of `need` bytes (None for 0), or the caller's, which must hold that many."""
+    if scratch is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    if not isinstance(scratch, torch.Tensor) or not scratch.is_cuda or not scratch.is_contiguous():
+        raise ValueError('scratch: needs a contiguous device tensor')
+    if scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f'scratch: {scratch.numel() * scratch.element_size()} bytes, this shape needs {need}')
+    return scratch
+
+
+def gemm_nt(a, bt, bias=None, out=None, scratch=None):
     """mvnerf_gemm_nt / mvnerf_gemm_nt_bias: a (M,K) @ bt (N,K)^T [+ bias (N,)] -> (M,N), fp32, deterministic (K split into ranges whose
-    partials are added in order)."""
+    partials are added in order).  out: the (M,N) tensor to write into; scratch: at least mvnerf_gemm_nt_scratch_bytes(M,N,K) bytes."""
     m, k = a.shape
     n = bt.shape[0]
     _chk(a, 'a', shape=(m, k))
     _chk(bt, 'bt', shape=(n, k))
     if bias is not None:
         _chk(bias, 'bias', shape=(n,))
-    out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    need = int(_lib.lib().mvnerf_gemm_nt_scratch_bytes(m, n, k))
-    scratch = torch.empty(need, dtype=torch.uint8, device=a.device) if need else None
+    out = torch.empty((m, n), dtype=torch.float32, device=a.device) if out is None else _chk(out, 'out', shape=(m, n))
+    scratch = _gemm_scratch(scratch, int(_lib.lib().mvnerf_gemm_nt_scratch_bytes(m, n, k)), a.device)
     with torch.cuda.device(a.device):
         if bias is None:
             rc = _lib.lib().mvnerf_gemm_nt(_p(a), _p(bt), _p(out), m, n, k, _p(scratch), _stream(a))
@@ -987,26 +1000,27 @@ def gemm_tn_ok(m, n, k):
     return m > 0 and n > 0 and k > 0 and m % 8 == 0 and n % 32 == 0 and k % 64 == 0
 
 
-def gemm_tn(g, a):
-    """mvnerf_gemm_tn: g (M,N)^T @ a (M,K) -> (N,K), fp32, deterministic; no transposed copies."""
+def gemm_tn(g, a, out=None, scratch=None):
+    """mvnerf_gemm_tn: g (M,N)^T @ a (M,K) -> (N,K), fp32, deterministic; no transposed copies.  out: the (N,K) tensor to write into;
+    scratch: at least mvnerf_gemm_tn_scratch_bytes(M,N,K) bytes."""
     m, n = g.shape
     k = a.shape[1]
     _chk(g, 'g', shape=(m, n))
     _chk(a, 'a', shape=(m, k))
-    out = torch.empty((n, k), dtype=torch.float32, device=a.device)
-    need = int(_lib.lib().mvnerf_gemm_tn_scratch_bytes(m, n, k))
-    scratch = torch.empty(need, dtype=torch.uint8, device=a.device) if need else None
+    out = torch.empty((n, k), dtype=torch.float32, device=a.device) if out is None else _chk(out, 'out', shape=(n, k))
+    scratch = _gemm_scratch(scratch, int(_lib.lib().mvnerf_gemm_tn_scratch_bytes(m, n, k)), a.device)
     with torch.cuda.device(a.device):
         rc = _lib.lib().mvnerf_gemm_tn(_p(g), _p(a), _p(out), m, n, k, _p(scratch), _stream(a))
     _lib.check(rc, 'gemm_tn')
     return out
 
 
-def gemm_tn_batched(g, a, g2=None, a2=None, colsum_of=0):
+def gemm_tn_batched(g, a, g2=None, a2=None, colsum_of=0, out=None, scratch=None):
     """mvnerf_gemm_tn_batched: out[b] = g[b]^T @ a[b] (+ g2[b]^T @ a2[b]) for a batch of weight gradients that share their M rows, and the
     column sums of g (colsum_of=1) or g2 (=2) from the same pass.  g, g2: (batch, M, N) views whose last dimension is contiguous - e.g.
     `x.view(M, batch, N).permute(1, 0, 2)` for the column blocks of one (M, batch * N) matrix: no copies are made; a, a2: (batch, M, K).
-    -> (batch, N, K) [, (batch, N)]."""
+    -> (batch, N, K) [, (batch, N)].  out: the (batch, N, K) tensor to write into, with column sums the pair (out, colsum); scratch: at
+    least mvnerf_gemm_tn_batched_scratch_bytes(M, N, K, batch, colsum_of != 0) bytes."""
     def strides(t, name):
         if t.dim() != 3 or t.stride(2) != 1 or t.dtype != torch.float32 or not t.is_cuda:
             raise ValueError(f'{name}: needs a float32 device tensor (batch, M, cols) with contiguous rows')
@@ -1024,10 +1038,15 @@ def gemm_tn_batched(g, a, g2=None, a2=None, colsum_of=0):
         q.g2, q.a2 = _p(g2), _p(a2)
         (q.g2_batch_stride, q.ldg2), (q.a2_batch_stride, q.lda2) = strides(g2, 'g2'), strides(a2, 'a2')
     q.colsum_of = int(colsum_of)
-    out = torch.empty((batch, n, k), dtype=torch.float32, device=a.device)
-    colsum = torch.empty((batch, n), dtype=torch.float32, device=a.device) if colsum_of else None
-    need = int(_lib.lib().mvnerf_gemm_tn_batched_scratch_bytes(m, n, k, batch, int(bool(colsum_of))))
-    scratch = torch.empty(need, dtype=torch.uint8, device=a.device) if need else None
+    if out is None:
+        out = torch.empty((batch, n, k), dtype=torch.float32, device=a.device)
+        colsum = torch.empty((batch, n), dtype=torch.float32, device=a.device) if colsum_of else None
+    else:
+        out, colsum = out if colsum_of else (out, None)
+        _chk(out, 'out', shape=(batch, n, k))
+        if colsum_of:
+            _chk(colsum, 'out colsum', shape=(batch, n))
+    scratch = _gemm_scratch(scratch, int(_lib.lib().mvnerf_gemm_tn_batched_scratch_bytes(m, n, k, batch, int(bool(colsum_of)))), a.device)
     with torch.cuda.device(a.device):
         rc = _lib.lib().mvnerf_gemm_tn_batched(ctypes.byref(q), _p(out), _p(colsum), m, n, k, batch, _p(scratch), _stream(a))
     _lib.check(rc, 'gemm_tn_batched')
