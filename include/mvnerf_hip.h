@@ -817,6 +817,35 @@ int mvnerf_render_fwd_split_ex(const float* rays_o, const float* rays_d, const f
 int mvnerf_fuse_upsample2x(const float* a, const float* b, const float* weight, int N, int h, int w, int Ca, int Cb, int act,
                            void* out, int out_bf16, mvnerf_stream_t stream);
 
+/* ---- 3x3 convolutions of the language fusion (layers.py:414-456 DoubleConv / Up, :593-660 CombineCLIPVisualV4) as one launch each:
+ *   out[n,i,j,co] = mul[n,co] * act( sum_{dy,dx in 0..2} sum_c X[n, i+dy-1, j+dx-1, c] * W[dy,dx,c,co] ),   X = [a | b] along c
+ * Conv2D(3, padding='same', use_bias=False), stride 1; taps outside the image are 0; images of a batch do not see each other.
+ * Products at fp32 grade on the fp16 matrix pipe: both operands as two fp16 pieces under a per-tensor power-of-two scale, three
+ * v_mfma_f32_16x16x32_f16 per product block, fp32 accumulation in a fixed order.  No atomics on out, no workspace:
+ * bit-identical from run to run. */
+
+/* Bytes of the packed weight stream of a (3,3,cin,cout) kernel; 0 when the channel counts are not accepted (cin % 32, cout % 64). */
+size_t mvnerf_conv3x3_packed_bytes(int cin, int cout);
+
+/* w_hwio (3,3,cin,cout) fp32, the Keras kernel as stored -> `packed` (16-byte aligned, mvnerf_conv3x3_packed_bytes): a 256-byte header
+ * (max |w| found on the device, the scale exponent derived from it) and the fp16 pieces in the order the kernel consumes them.
+ * Stream-ordered, no host read.  Call once per weight update. */
+int mvnerf_conv3x3_pack(const float* w_hwio, int cin, int cout, void* packed, mvnerf_stream_t stream);
+
+/* *amax = max |x| over n floats (the word is overwritten).  A NaN in x gives a NaN; for maps that another library produced. */
+int mvnerf_absmax_f32(const float* x, long n, float* amax, mvnerf_stream_t stream);
+
+/* a (N,h,w,Ca), b (N,h,w,Cb) or NULL with Cb = 0: fp32 NHWC, concatenated in that order without a copy.  amax_a, amax_b: one device
+ * float each, an UPPER BOUND of |a|, |b| (mvnerf_absmax_f32, or the amax_out of the launch that wrote the map): the kernel derives the
+ * operand scales from them.  A bound of 0 means an all-zero source; a non-finite bound fills out with NaN.  packed: mvnerf_conv3x3_pack
+ * of the (3,3,Ca+Cb,Cout) kernel.  act: 0 identity, 1 relu, 2 elu (alpha 1), applied to the sum; mul (N,Cout) or NULL multiplies after
+ * the activation.  out (N,h,w,Cout) fp32 NHWC.  amax_out (optional): one device word the CALLER ZEROES; on return max |out| (a NaN
+ * written anywhere makes it a NaN).
+ * Ca, Cb multiples of 32 (Ca >= 32), Cout a multiple of 64, act in 0..2: else MVNERF_E_SHAPE, before any launch.  a, b, packed, mul, out
+ * 16-byte aligned. */
+int mvnerf_conv3x3_nhwc(const float* a, int Ca, const float* amax_a, const float* b, int Cb, const float* amax_b, const void* packed,
+                        int N, int h, int w, int Cout, int act, const float* mul, float* out, float* amax_out, mvnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,108 @@
+// Scalar arithmetic of the 3x3 convolution on two fp16 pieces per operand (conv3x3.hip): the power-of-two scale chooser and
+// the cuts of a weight and of an activation.  Plain scalar code for host and device: tests/cpu_conv builds this file with the host
+// compiler and compares it bit for bit with the NumPy restatement of tests/conv3x3_ref.py.
+//
+//   scale       e = conv_scale_exp(amax): amax * 2^e lies in [2^8, 2^9) (e = 0 for amax == 0); scaling is ldexpf, exact
+//   weight      tw = w * 2^ew:  A0 = rn16(tw), A1 = rn16(tw - A0), A0s = A0 / 64
+//   activation  tx = x * 2^ex:  B0 = rn16(tx), B1 = rn16(64 (tx - B0))
+//   product     acc += A0s B1 + A1 B0 + A0 B0   ( = A0 (tx - B0) + (tw - A0) B0 + A0 B0: the cross term of the two remainders is dropped)
+//
+// Both remainders are exact in fp32 before they are rounded.  With both operands normalised to [2^8, 2^9) at their maximum nothing
+// finite overflows fp16, and the pieces of an element 2^-22 below the maximum still are normal fp16 numbers.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define MVC_HD __host__ __device__ inline
+#else
+#define MVC_HD inline
+#endif
+
+namespace mvnerf {
+
+constexpr int kConvScaleTarget = 8;           // the scaled maximum lies in [2^8, 2^9)
+constexpr float kConvRemScale = 64.0f;        // the activation's remainder is stored times 64 and meets A0 / 64
+
+MVC_HD uint32_t conv_f32_bits(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    return u;
+}
+
+MVC_HD float conv_bits_f32(uint32_t u) {
+    float x;
+    memcpy(&x, &u, 4);
+    return x;
+}
+
+// amax: a non-negative finite float (an upper bound of |x|).  Returns e with amax * 2^e in [2^8, 2^9); 0 for amax == 0.
+// Subnormal bounds are counted from their leading bit, so e reaches 8 + 149 and is applied with ldexpf, never as a float factor.
+MVC_HD int conv_scale_exp(float amax) {
+    const uint32_t bits = conv_f32_bits(amax) & 0x7fffffffu;
+    if (bits == 0) return 0;
+    const int field = (int)(bits >> 23);
+    const int exponent = field ? field - 127 : (31 - __builtin_clz(bits)) - 149;
+    return kConvScaleTarget - exponent;
+}
+
+MVC_HD bool conv_amax_finite(float amax) { return (conv_f32_bits(amax) & 0x7fffffffu) < 0x7f800000u; }
+
+// fp32 -> fp16 bits, round to nearest even (overflow to infinity, subnormals kept), and back
+#if defined(__FLT16_MANT_DIG__)
+MVC_HD uint16_t conv_rn16(float x) {
+    const _Float16 h = (_Float16)x;
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+MVC_HD float conv_f16_f32(uint16_t u) {
+    _Float16 h;
+    memcpy(&h, &u, 2);
+    return (float)h;
+}
+#else
+MVC_HD uint16_t conv_rn16(float x) {
+    const uint32_t u = conv_f32_bits(x), sign = (u >> 16) & 0x8000u, mag = u & 0x7fffffffu;
+    if (mag >= 0x7f800000u) return (uint16_t)(sign | (mag > 0x7f800000u ? 0x7e00u : 0x7c00u));
+    if (mag >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                       // rounds to 2^16 or more
+    if (mag < 0x33000000u) return (uint16_t)sign;                                    // below 2^-25: rounds to zero
+    int exponent = (int)(mag >> 23) - 127;
+    uint32_t mant = (mag & 0x7fffffu) | 0x800000u;                                   // 24 bits
+    int shift = exponent >= -14 ? 13 : 13 + (-14 - exponent);                        // bits dropped
+    uint32_t kept = mant >> shift, rest = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    if (rest > half || (rest == half && (kept & 1u))) ++kept;
+    // normal: kept has the implicit bit at 2^10 (or carried to 2^11); subnormal: kept is the fraction field (a carry makes it normal)
+    const uint32_t out = exponent >= -14 ? ((uint32_t)(exponent + 14) << 10) + kept : kept;
+    return (uint16_t)(sign | out);
+}
+MVC_HD float conv_f16_f32(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, field = (h >> 10) & 31u, frac = h & 0x3ffu;
+    if (field == 31) return conv_bits_f32(sign | 0x7f800000u | (frac << 13));
+    if (field == 0) {
+        const float v = ldexpf((float)frac, -24);
+        return sign ? -v : v;
+    }
+    return conv_bits_f32(sign | ((field + 112u) << 23) | (frac << 13));
+}
+#endif
+
+// A0, A1, A0s of a weight under the scale exponent ew (fp16 bit patterns)
+MVC_HD void conv_cut_weight(float w, int ew, uint16_t& a0, uint16_t& a1, uint16_t& a0s) {
+    const float tw = ldexpf(w, ew);
+    a0 = conv_rn16(tw);
+    const float f0 = conv_f16_f32(a0);
+    a1 = conv_rn16(tw - f0);
+    a0s = conv_rn16(f0 * (1.0f / kConvRemScale));
+}
+
+// B0, B1 of an activation under the scale exponent ex
+MVC_HD void conv_cut_act(float x, int ex, uint16_t& b0, uint16_t& b1) {
+    const float tx = ldexpf(x, ex);
+    b0 = conv_rn16(tx);
+    b1 = conv_rn16(kConvRemScale * (tx - conv_f16_f32(b0)));
+}
+
+}  // namespace mvnerf

@@ -213,18 +213,20 @@ _ACT_CODES = {None: 0, 'relu': 1, 'elu': 2}
 _ACT_FNS = {None: lambda x: x, 'relu': F.relu, 'elu': F.elu}
 
 
-def _wants_fused(fused_tail, *tensors):
-    """The fused-tail switch: True | False | 'auto' = on the GPU and nothing in the call needs a gradient (the fused pass has no backward)."""
+def _wants_fused(fused_tail, *tensors, name='fused_tail'):
+    """The switch of a fused pass (`fused_tail`, `fused_conv`): True | False | 'auto' = on the GPU and nothing in the call needs a gradient
+    (the fused passes have no backward)."""
     if fused_tail not in (True, False, 'auto'):
-        raise ValueError(f"fused_tail: {fused_tail!r}, expected True, False or 'auto'")
+        raise ValueError(f"{name}: {fused_tail!r}, expected True, False or 'auto'")
     if fused_tail is False:
         return False
+    tensors = [t for t in tensors if t is not None]
     needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
     on_gpu = all(t.is_cuda for t in tensors)
     if fused_tail is True:
         if needs_grad:
-            raise RuntimeError('fused_tail=True: the fused tail has no backward pass; run under torch.no_grad(), freeze the inputs, '
-                               "or use fused_tail='auto'")
+            raise RuntimeError(f'{name}=True: the fused {name[6:]} has no backward pass; run under torch.no_grad(), freeze the inputs, '
+                               f"or use {name}='auto'")
         return True                                                  # (a CPU tensor fails in ops: there is no CPU path)
     return on_gpu and not needs_grad
 
@@ -309,29 +311,98 @@ def _activation(name):
     return _ACT_FNS[name]
 
 
-class DoubleConv(nn.Module):
-    """layers.py:414-434: two bias-free 3x3 convolutions, the activation after each."""
+def conv3x3_fusable(conv, c_a, c_b=0):
+    """Whether ops.conv3x3 takes this convolution over [a | b]: 3x3, stride 1, no bias, channel counts in multiples of 32 / 32 / 64."""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and conv.bias is None and c_a + c_b == conv.in_channels
+            and c_a >= 32 and c_a % 32 == 0 and c_b % 32 == 0 and conv.out_channels % 64 == 0)
 
-    def __init__(self, c_in, filters, activation='relu'):
+
+def _packed_conv3x3(conv):
+    """The packed fp16-piece stream of `conv.weight` (ops.conv3x3_pack), cached on the module per parameter version: an in-place
+    update (optimizer step, `copy_`, load_combine_clip_visual_v4) re-packs on the next call.  `load_conv` drops the cache itself."""
+    from . import ops
+    weight = conv.weight
+    key = (weight._version, weight.data_ptr(), weight.device)
+    cached = conv.__dict__.get('_mvnerf_packed')
+    if cached is None or cached[0] != key:
+        cached = (key, ops.conv3x3_pack(weight.detach().permute(2, 3, 1, 0).contiguous()))      # HWIO, the Keras kernel as stored
+        conv.__dict__['_mvnerf_packed'] = cached
+    return cached[1]
+
+
+def conv3x3_act(conv, a, b, activation, fused_conv=False, mul=None, amax_a=None, amax_b=None):
+    """`act(conv([a | b])) * mul` of NCHW a, b (b may be None) with a bias-free 3x3 `conv`; mul (N, C, 1, 1) or None.  Returns (out, amax):
+    through torch (amax None) unless `fused_conv` (True | False | 'auto', :func:`_wants_fused`) selects ops.conv3x3, which reads the two
+    sources without a concat or a padded copy and returns max |out| as a device float - the next convolution's `amax_a`.  A convolution
+    the kernel does not take (:func:`conv3x3_fusable`) runs through torch under 'auto' and raises under True."""
+    fused = _wants_fused(fused_conv, a, b, conv.weight, mul, name='fused_conv')
+    if fused and not conv3x3_fusable(conv, a.shape[1], 0 if b is None else b.shape[1]):
+        if fused_conv is True:
+            raise ValueError(f'fused_conv=True: a {tuple(conv.kernel_size)} convolution over {a.shape[1]} + {0 if b is None else b.shape[1]} -> '
+                             f"{conv.out_channels} channels is not one the HIP pass takes (3x3, no bias, multiples of 32 + 32 -> 64); use 'auto'")
+        fused = False
+    if not fused:
+        out = _ACT_FNS[activation](conv(a if b is None else torch.cat([a, b], 1)))
+        return (out if mul is None else out * mul), None
+    from . import ops
+    nhwc = lambda t: None if t is None else t.detach().permute(0, 2, 3, 1).contiguous()      # free when the storage is channels-last already
+    n, c_out = a.shape[0], conv.out_channels
+    if mul is not None:
+        mul = mul.detach().reshape(mul.shape[0], c_out).expand(n, c_out).contiguous()
+    amax = torch.empty(1, dtype=torch.float32, device=a.device)
+    out = ops.conv3x3(nhwc(a), nhwc(b), _packed_conv3x3(conv), c_out, _ACT_CODES[activation], mul=mul, amax_a=amax_a, amax_b=amax_b,
+                      amax_out=amax)
+    return out.permute(0, 3, 1, 2), amax
+
+
+class DoubleConv(nn.Module):
+    """layers.py:414-434: two bias-free 3x3 convolutions, the activation after each.
+    fused_conv (default False: torch): both as ops.conv3x3 launches, see :func:`conv3x3_act`."""
+
+    def __init__(self, c_in, filters, activation='relu', fused_conv=False):
         super().__init__()
         self.conv_1 = SameConv2d(c_in, filters, 3, bias=False)
         self.conv_2 = SameConv2d(filters, filters, 3, bias=False)
+        self.activation = activation
         self.act = _activation(activation)
+        self.fused_conv = fused_conv
+
+    def convs(self, a, b=None, mul=None, amax_a=None, amax_b=None):
+        """act(conv_2(act(conv_1([a | b])))) * mul -> (out, amax | None); the first convolution's amax_out is the second one's amax."""
+        x, amax = conv3x3_act(self.conv_1, a, b, self.activation, self.fused_conv, None, amax_a, amax_b)
+        return conv3x3_act(self.conv_2, x, None, self.activation, self.fused_conv, mul, amax)
 
     def forward(self, x):
-        return self.act(self.conv_2(self.act(self.conv_1(x))))
+        if self.fused_conv is False:
+            return self.act(self.conv_2(self.act(self.conv_1(x))))
+        return self.convs(x)[0]
 
 
 class Up(nn.Module):
-    """layers.py:437-456: [x2 bilinear of x | CLIP stage map resized to `shape`] -> DoubleConv."""
+    """layers.py:437-456: [x2 bilinear of x | CLIP stage map resized to `shape`] -> DoubleConv.
+    fused_conv (default False: torch): the DoubleConv reads the two maps from where they lie, no concat."""
 
-    def __init__(self, shape, c_in, c_clip, filters, activation='relu'):
+    def __init__(self, shape, c_in, c_clip, filters, activation='relu', fused_conv=False):
         super().__init__()
         self.shape = tuple(shape)
-        self.double_conv = DoubleConv(c_in + c_clip, filters, activation)
+        self.double_conv = DoubleConv(c_in + c_clip, filters, activation, fused_conv)
+
+    @property
+    def fused_conv(self):
+        return self.double_conv.fused_conv
+
+    @fused_conv.setter
+    def fused_conv(self, value):
+        self.double_conv.fused_conv = value
+
+    def convs(self, x, clip_x, mul=None, amax_x=None):
+        """-> (out * mul, amax | None).  amax_x bounds |x|: a bilinear x2 of a map cannot exceed the map's maximum, so it bounds _up(x) too."""
+        return self.double_conv.convs(_up(x, 2), _resize(clip_x, self.shape), mul, amax_x)
 
     def forward(self, x, clip_x):
-        return self.double_conv(torch.cat([_up(x, 2), _resize(clip_x, self.shape)], 1))
+        if self.fused_conv is False:
+            return self.double_conv(torch.cat([_up(x, 2), _resize(clip_x, self.shape)], 1))
+        return self.convs(x, clip_x)[0]
 
 
 class ConvFusion(nn.Module):
@@ -382,10 +453,12 @@ class CombineCLIPVisualV4(nn.Module):
     tail of :class:`CombineCLIPVisualV0` (`conv_fusion_3` + `up_sample`).  up3_filters=128 is V4, 256 is V3 (:523-590), which differs
     in nothing else.  Inputs are NCHW (channels-last storage); the pooled CLIP vector is carried and not used, as in the reference.
     fused_tail: 'auto' | True | False - the tail as one HIP pass (:func:`conv_fusion_tail`) when on the GPU and nothing needs a gradient.
+    fused_conv: False (default) | True | 'auto' - the seven 3x3 convolutions as ops.conv3x3 launches under the same rule
+    (:func:`conv3x3_act`), `multiply_fusion_1..3` in the epilogue of the convolution in front of them, every amax_out the next amax.
     Parity unpinned, like the rest of this file."""
 
     def __init__(self, use_dense=False, activation='relu', half_size=(240, 320), clip_channels=(256, 512, 1024, 2048), text_dim=1024,
-                 widths=(1024, 512, 256), up3_filters=128, visual_channels=256, filters=256, fused_tail='auto'):
+                 widths=(1024, 512, 256), up3_filters=128, visual_channels=256, filters=256, fused_tail='auto', fused_conv=False):
         super().__init__()
         hh, hw = half_size
         if hh % 8 or hw % 8:
@@ -407,20 +480,42 @@ class CombineCLIPVisualV4(nn.Module):
         self.up_3 = Up(self.half_size, w3, c1, up3_filters, activation)
         self.conv_fusion_3 = ConvFusion(up3_filters + visual_channels, filters, activation)
         self.fused_tail = fused_tail
+        self.fused_conv = fused_conv
+
+    @property
+    def fused_conv(self):
+        return self._fused_conv
+
+    @fused_conv.setter
+    def fused_conv(self, value):
+        if value not in (True, False, 'auto'):
+            raise ValueError(f"fused_conv: {value!r}, expected True, False or 'auto'")
+        self._fused_conv = value
+        for up in (self.up_1, self.up_2, self.up_3):
+            up.fused_conv = value
 
     def forward(self, clip_outputs, visual_features, clip_textuals, out_dtype=None):
         _clip_visuals, clip_l1, clip_l2, clip_l3, clip_l4 = clip_outputs
         vis_1 = _resize(visual_features, self.size_1)
         vis_2 = _resize(visual_features, self.size_2)
-        x = self.act(self.conv(_resize(clip_l4, self.size_3)))
-        x = self.multiply_fusion_1(x, clip_textuals)
-        x = self.up_1(x, clip_l3)
-        x = self.multiply_fusion_2(x, clip_textuals)
-        x = self.conv_fusion_1(x, vis_2)
-        x = self.up_2(x, clip_l2)
-        x = self.multiply_fusion_3(x, clip_textuals)
-        x = self.conv_fusion_2(x, vis_1)
-        x = self.up_3(x, clip_l1)
+        if self.fused_conv is False:
+            x = self.act(self.conv(_resize(clip_l4, self.size_3)))
+            x = self.multiply_fusion_1(x, clip_textuals)
+            x = self.up_1(x, clip_l3)
+            x = self.multiply_fusion_2(x, clip_textuals)
+            x = self.conv_fusion_1(x, vis_2)
+            x = self.up_2(x, clip_l2)
+            x = self.multiply_fusion_3(x, clip_textuals)
+            x = self.conv_fusion_2(x, vis_1)
+            x = self.up_3(x, clip_l1)
+        else:               # the same chain; each MultiplyFusion is the `mul` of the convolution in front of it
+            tile = lambda fusion: fusion.tile(clip_textuals)
+            x, amax = conv3x3_act(self.conv, _resize(clip_l4, self.size_3), None, self.activation, self.fused_conv, tile(self.multiply_fusion_1))
+            x, _ = self.up_1.convs(x, clip_l3, tile(self.multiply_fusion_2), amax)
+            x = self.conv_fusion_1(x, vis_2)
+            x, _ = self.up_2.convs(x, clip_l2, tile(self.multiply_fusion_3))
+            x = self.conv_fusion_2(x, vis_1)
+            x, _ = self.up_3.convs(x, clip_l1)
         fused = _wants_fused(self.fused_tail, x, visual_features, self.conv_fusion_3.conv.weight)
         return conv_fusion_tail(x, visual_features, self.conv_fusion_3.conv, self.activation, fused, out_dtype)
 
@@ -492,10 +587,11 @@ class LanguageFeatureProducer(nn.Module):
     instruction - `tokens` (N | 1, 77) int32 through the text stand-in, or a ready `text_embedding` (N | 1, text_dim) - ->
     combined_features (N, H, W, 256), NHWC-contiguous in `out_dtype`.  VisualFeatures + the CLIP pyramid + the text embedding +
     CombineCLIPVisualV4(use_dense=True, activation='elu').  Nothing in it trains (the reference's tape watches `grasp_readout` only),
-    so with fused_tail='auto' the tail is the fused HIP pass whenever the producer is on the GPU."""
+    so with fused_tail='auto' the tail is the fused HIP pass whenever the producer is on the GPU; fused_conv (default False) is handed
+    to the fusion: its 3x3 convolutions as ops.conv3x3 launches."""
 
     def __init__(self, original_image_size=(480, 640), out_dtype=torch.float32, fused_tail='auto', n_features=256, clip_pyramid=None,
-                 clip_text=None, combine_kw=None, **visual_kw):
+                 clip_text=None, combine_kw=None, fused_conv=False, **visual_kw):
         super().__init__()
         h, w = original_image_size
         if h % 16 or w % 16:
@@ -503,7 +599,8 @@ class LanguageFeatureProducer(nn.Module):
         self.visual_features = VisualFeatures(n_features, original_image_size, **visual_kw)
         self.clip_pyramid = clip_pyramid if clip_pyramid is not None else SyntheticCLIPPyramid()
         self.clip_text = clip_text if clip_text is not None else SyntheticCLIPText()
-        kw = dict(use_dense=True, activation='elu', half_size=(h // 2, w // 2), visual_channels=n_features, fused_tail=fused_tail)
+        kw = dict(use_dense=True, activation='elu', half_size=(h // 2, w // 2), visual_channels=n_features, fused_tail=fused_tail,
+                  fused_conv=fused_conv)
         kw.update(combine_kw or {})
         self.combine_clip_visual = CombineCLIPVisualV4(**kw)
         self.out_dtype = out_dtype
@@ -601,6 +698,7 @@ def _t(a):
 def load_conv(conv, kernel_hwio, bias=None):
     """Keras Conv2D kernel (kh, kw, in, out) -> torch (out, in, kh, kw)."""
     conv.weight.data.copy_(_t(kernel_hwio).permute(3, 2, 0, 1))
+    conv.__dict__.pop('_mvnerf_packed', None)            # (`.data` does not bump the parameter version the packed-stream cache keys on)
     if bias is not None:
         conv.bias.data.copy_(_t(bias))
 
@@ -808,7 +906,7 @@ def count_parameters(module):
 
 
 __all__ = ['FeatureProducer', 'LanguageFeatureProducer', 'CombineCLIPVisualV4', 'DoubleConv', 'Up', 'ConvFusion', 'Tile',
-           'MultiplyFusion', 'SyntheticCLIPPyramid', 'SyntheticCLIPText', 'tokenize', 'conv_fusion_tail', 'load_combine_clip_visual_v4',
+           'MultiplyFusion', 'conv3x3_act', 'conv3x3_fusable', 'SyntheticCLIPPyramid', 'SyntheticCLIPText', 'tokenize', 'conv_fusion_tail', 'load_combine_clip_visual_v4',
            'COMBINE_CLIP_VISUAL_V4_VARIABLES', 'VisualFeatures', 'CombineCLIPVisualV0', 'ConvolutionalEncoder', 'VisionTransformerEncoder',
            'VisionTransformer', 'TransformerBlock', 'SyntheticCLIPStage1', 'flat_net_from_keras', 'keras_from_flat_net',
            'make_encoder_optimizer', 'KerasAdam', 'convolutional_encoder_weights', 'warmup_lr_lambda', 'load_conv', 'load_conv_transpose', 'load_dense', 'load_batchnorm', 'load_mha',

@@ -1637,3 +1637,85 @@ def fuse_upsample2x(a, b, weight, act, out_dtype=torch.float32, out=None):
                                                int(out_dtype == torch.bfloat16), _stream(a))
     _lib.check(rc, 'fuse_upsample2x')
     return out
+
+
+def absmax(x, out=None):
+    """mvnerf_absmax_f32: max |x| of a contiguous fp32 tensor as one device float (shape (1,)); a NaN in x gives a NaN.  No host read."""
+    _chk(x, 'x')
+    if x.numel() == 0:
+        raise ValueError('x: empty tensor')
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=x.device)
+    else:
+        _chk(out, 'out', shape=(1,))
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().mvnerf_absmax_f32(_p(x), x.numel(), _p(out), _stream(x))
+    _lib.check(rc, 'absmax')
+    return out
+
+
+def conv3x3_packed_bytes(cin, cout):
+    """Bytes of the packed stream of a (3,3,cin,cout) kernel (cin a multiple of 32, cout a multiple of 64; ValueError otherwise)."""
+    n = _lib.lib().mvnerf_conv3x3_packed_bytes(int(cin), int(cout))
+    if n == 0:
+        raise ValueError(f'conv3x3: cin={cin} cout={cout} (cin a multiple of 32, cout a multiple of 64)')
+    return n
+
+
+def conv3x3_pack(w_hwio, out=None):
+    """mvnerf_conv3x3_pack: w_hwio (3,3,cin,cout) fp32, the Keras kernel as stored -> the packed fp16-piece stream (uint8 tensor) that
+    :func:`conv3x3` reads; max |w| and the scale are found on the device."""
+    _chk(w_hwio, 'w_hwio', shape=(3, 3, None, None))
+    cin, cout = w_hwio.shape[2:]
+    nbytes = conv3x3_packed_bytes(cin, cout)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=w_hwio.device)
+    else:
+        _chk(out, 'out', dtype=torch.uint8, shape=(nbytes,))
+    with torch.cuda.device(w_hwio.device):
+        rc = _lib.lib().mvnerf_conv3x3_pack(_p(w_hwio), cin, cout, _p(out), _stream(w_hwio))
+    _lib.check(rc, 'conv3x3_pack')
+    return out
+
+
+def conv3x3(a, b, packed, cout, act, mul=None, amax_a=None, amax_b=None, out=None, amax_out=None):
+    """mvnerf_conv3x3_nhwc: out (N,h,w,cout) = mul[n,co] * act(conv3x3_same([a | b], W)), bias-free, stride 1, zero padding.
+    a (N,h,w,Ca), b (N,h,w,Cb) or None: fp32 NHWC; packed: :func:`conv3x3_pack` of the (3,3,Ca+Cb,cout) kernel; act: 0 | 'identity',
+    1 | 'relu', 2 | 'elu'; mul (N,cout) or None.  amax_a / amax_b: device floats (1,) bounding |a| / |b| (computed with :func:`absmax`
+    when missing); amax_out: a (1,) device float that receives max |out| (zeroed here)."""
+    _chk(a, 'a', shape=(None, None, None, None))
+    n, h, w, ca = a.shape
+    cb = 0
+    if b is not None:
+        _chk(b, 'b', shape=(n, h, w, None))
+        cb = b.shape[3]
+    if not isinstance(act, int):
+        if act not in FUSE_ACTIVATIONS:
+            raise ValueError(f'act: {act!r}, expected one of {list(FUSE_ACTIVATIONS)} or 0, 1, 2')
+        act = FUSE_ACTIVATIONS[act]
+    _chk(packed, 'packed', dtype=torch.uint8, shape=(conv3x3_packed_bytes(ca + cb, cout),))
+    if mul is not None:
+        _chk(mul, 'mul', shape=(n, cout))
+    if amax_a is None:
+        amax_a = absmax(a)
+    else:
+        _chk(amax_a, 'amax_a', shape=(1,))
+    if b is not None:
+        if amax_b is None:
+            amax_b = absmax(b)
+        else:
+            _chk(amax_b, 'amax_b', shape=(1,))
+    elif amax_b is not None:
+        raise ValueError('amax_b given without b')
+    if out is None:
+        out = torch.empty((n, h, w, cout), dtype=torch.float32, device=a.device)
+    else:
+        _chk(out, 'out', shape=(n, h, w, cout))
+    if amax_out is not None:
+        _chk(amax_out, 'amax_out', shape=(1,))
+        amax_out.zero_()
+    with torch.cuda.device(a.device):
+        rc = _lib.lib().mvnerf_conv3x3_nhwc(_p(a), ca, _p(amax_a), _p(b), cb, _p(amax_b), _p(packed), n, h, w, int(cout), int(act), _p(mul),
+                                            _p(out), _p(amax_out), _stream(a))
+    _lib.check(rc, 'conv3x3')
+    return out
