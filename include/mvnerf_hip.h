@@ -846,6 +846,38 @@ int mvnerf_absmax_f32(const float* x, long n, float* amax, mvnerf_stream_t strea
 int mvnerf_conv3x3_nhwc(const float* a, int Ca, const float* amax_a, const float* b, int Cb, const float* amax_b, const void* packed,
                         int N, int h, int w, int Cout, int act, const float* mul, float* out, float* amax_out, mvnerf_stream_t stream);
 
+/* ---- the 3x3 convolutions of VisualFeatures (layers.py:7-34 Block, :37-57 ConvolutionalEncoder, :150-229 VisionTransformerEncoder):
+ * Conv2D(3, padding='same') WITH a bias, a relu in front of a convolution (output_conv, layers.py:206-212), and
+ * BatchNormalization(training=True) behind it (Block, layers.py:22-27).  Inference only. */
+
+/* mvnerf_conv3x3_nhwc with three more arguments (everything else as above; with bias = NULL, act_in = 0, stats = NULL it IS that call):
+ *   bias    (Cout) fp32 or NULL: out = mul * act(sum + bias[co]) - added to the un-scaled sum, before act.  amax_out covers what is
+ *           written.  16-byte aligned.
+ *   act_in  0 identity, 1 relu, 2 elu: applied to every element of a and b as it is read, before the fp16 cut.  |relu(x)| <= |x| and
+ *           |elu(x)| <= |x|, so amax_a / amax_b computed on the un-activated sources stay valid bounds.  Taps outside the image are
+ *           zero AFTER the activation (Keras pads the activated map).
+ *   stats   NULL, or mvnerf_conv3x3_stats_bytes bytes (16-byte aligned): for every workgroup - channel tile ct of 64, image n, tile row
+ *           ty, tile column tx of 16 x 16 pixels, in that order - 64 means and then 64 M2 (sums of squared deviations from that mean) of
+ *           the values written to the tile's real pixels, per channel.  The mean is reduced first, then the deviations about it; no raw
+ *           sum of squares is formed.  Pixel counts follow from (h, w) and are not stored.  Every workgroup owns its slots (plain stores,
+ *           no atomics): two runs give the same bits.  A non-finite amax fills them with NaN. */
+size_t mvnerf_conv3x3_stats_bytes(int N, int h, int w, int Cout);
+int mvnerf_conv3x3_nhwc_ex(const float* a, int Ca, const float* amax_a, const float* b, int Cb, const float* amax_b, const void* packed,
+                           int N, int h, int w, int Cout, int act, const float* mul, float* out, float* amax_out, const float* bias,
+                           int act_in, float* stats, mvnerf_stream_t stream);
+
+/* Batch statistics of a convolution output from its tile partials (layers.py:23, 27: tf.keras BatchNormalization, training=True):
+ * mean[c] and rstd[c] = 1 / sqrt(var[c] + eps) with the BIASED variance over all N h w pixels, c < Cout.  The tiles are combined with
+ * Chan's pairwise update in double, in a fixed order.  Stream-ordered, no host read (the chain can be captured in a graph). */
+int mvnerf_bn_finalize(const float* stats, int N, int h, int w, int Cout, double eps, float* mean, float* rstd, mvnerf_stream_t stream);
+
+/* out = act(((y - mean[c]) * rstd[c]) * gamma[c] + beta[c] (+ skip)) over `pixels` x C fp32 NHWC elements (layers.py:23-33: the
+ * normalisation, `out += skip`, relu).  skip: like y, or NULL.  act: 0 identity, 1 relu.  out may be y (in place).  amax_out (optional):
+ * one device word the CALLER ZEROES; on return max |out|.  One rounding per written operation, the subtraction first.
+ * C a multiple of 4; all arrays 16-byte aligned. */
+int mvnerf_bn_apply_nhwc(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* skip,
+                         long pixels, int C, int act, float* out, float* amax_out, mvnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

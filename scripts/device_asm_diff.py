@@ -22,7 +22,8 @@ def functions(path):
                 name, body = m[1], []
             elif name is not None:
                 if line.startswith('.Lfunc_end'):
-                    out[name] = re.sub(r'\.LBB\d+_', '.LBB_', ''.join(body))
+                    # (labels and the "in Loop: Header=BB2_31" comments that name them)
+                    out[name] = re.sub(r'\bBB\d+_', 'BB_', re.sub(r'\.LBB\d+_', '.LBB_', ''.join(body)))
                     name = None
                 else:
                     body.append(line)

@@ -24,6 +24,10 @@
 // epilogue multiplies by 2^-(ew + e_last).  A non-finite amax (or weight maximum) fills the tile with NaN instead.
 //
 // No atomics on out, no workspace, a fixed summation order: two runs give the same bits.
+//
+// mvnerf_conv3x3_nhwc_ex (the convolutions of VisualFeatures, layers.py:7-34, 206-212) adds, as compile-time variants that
+// leave the plain instantiation's code as it was: a bias in front of the activation, an activation of the source elements as the halo
+// is read (before the cut; the padding stays zero), and per-workgroup (mean, M2) partials of what the tile writes, for batchnorm.hip.
 #include <hip/hip_runtime.h>
 
 #include "mvnerf_api.h"
@@ -53,6 +57,7 @@ constexpr int kCvTapBytes = 12 * kCvFragBytes;                // 4 channel block
 static_assert(kCvGroupBytes % 256 == 0, "the k groups of a B fragment must fall on the same banks");
 static_assert(kCvHaloPix <= kCvPixPad, "halo fits its LDS row");
 
+// (the plain instantiation's epilogue; the variants of mvnerf_conv3x3_nhwc_ex use mvnerf_conv.h's conv_act_f, the same function for host and device)
 __device__ __forceinline__ float conv_act(float x, int act) {
     if (act == 1) return x > 0.0f ? x : 0.0f;
     if (act == 2) return x > 0.0f ? x : expm1f(x);
@@ -63,11 +68,24 @@ __device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
+// What mvnerf_conv3x3_nhwc_ex adds to a launch: the trailing argument of the kernels behind it.  The plain instantiation has no such
+// argument (an empty pack), so its code and its argument block are what they were.
+struct ConvEx {
+    const float* bias;          // (Cout) or null
+    float* stats;               // [workgroup][mean | M2][64] or null
+};
+__device__ __forceinline__ ConvEx conv_ex() { return ConvEx{nullptr, nullptr}; }
+__device__ __forceinline__ ConvEx conv_ex(ConvEx ex) { return ex; }
+
+// kActIn: the activation of the source elements as the halo is read (0 identity, 1 relu, 2 elu); Ex: nothing, or one ConvEx.
+template <int kActIn, class... Ex>
 __global__ __launch_bounds__(kCvThreads, 2) void conv3x3_kernel(const float* __restrict__ a, const float* __restrict__ b, int Ca, int Cb,
                                                              const float* __restrict__ amax_a, const float* __restrict__ amax_b,
                                                              const unsigned char* __restrict__ packed, int N, int h, int w, int Cout, int act,
                                                              const float* __restrict__ mul, float* __restrict__ out,
-                                                             unsigned* __restrict__ amax_out, int tiles_x, int tiles_y) {
+                                                             unsigned* __restrict__ amax_out, int tiles_x, int tiles_y, Ex... extra) {
+    constexpr bool kEx = sizeof...(Ex) != 0;
+    [[maybe_unused]] const ConvEx ex = conv_ex(extra...);
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 15, grp = lane >> 4;
@@ -97,6 +115,9 @@ __global__ __launch_bounds__(kCvThreads, 2) void conv3x3_kernel(const float* __r
                     *reinterpret_cast<f32x4*>(out + (((size_t)n * h + py) * w + px) * Cout + ch0 + 16 * m) = nan4;
         }
         if (amax_out && tid == 0) atomicMax(amax_out, 0x7fc00000u);
+        if constexpr (kEx) {
+            if (ex.stats && tid < 2 * kCvCout) ex.stats[(size_t)blockIdx.x * 2 * kCvCout + tid] = nan;
+        }
         return;
     }
     const int ea = conv_scale_exp(max_a), eb = conv_scale_exp(max_b);
@@ -110,7 +131,7 @@ __global__ __launch_bounds__(kCvThreads, 2) void conv3x3_kernel(const float* __r
         const int iy = y0 - 1 + hp / kCvHalo, ix = x0 - 1 + hp % kCvHalo;
         src_pix[s] = (item < kCvStageItems && iy >= 0 && iy < h && ix >= 0 && ix < w) ? (n * h + iy) * w + ix : -1;
     }
-    auto stage = [&](const float* __restrict__ src, int C, int c0, int e) {
+    auto stage = [&](const float* __restrict__ src, int C, int c0, int e) __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < kCvStageSlots; ++s) {
             const int item = tid + kCvThreads * s;
@@ -122,7 +143,11 @@ __global__ __launch_bounds__(kCvThreads, 2) void conv3x3_kernel(const float* __r
                 lo = q[0];
                 hi = q[1];
             }
-            const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            if constexpr (kActIn != 0) {                            // act_in(0) == 0: the taps outside the image stay zero
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = conv_act_f(v[k], kActIn);
+            }
             u32x4 p0, p1;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -189,23 +214,106 @@ __global__ __launch_bounds__(kCvThreads, 2) void conv3x3_kernel(const float* __r
     // epilogue: un-scale, activation, mul, store; register r of acc[m][nb] is channel ch0 + 16 m + r of pixel (4 wave + nb, col)
     const int undo = -(ew + (Cb ? eb : ea));
     unsigned top = 0;
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-        const int py = y0 + 4 * wave + nb;
-        if (py >= h || px >= w) continue;
-        float* o = out + (((size_t)n * h + py) * w + px) * Cout + ch0;
+    if constexpr (kEx) {
+        // the same epilogue with the bias in front of the activation; the written values stay in the accumulators for the statistics
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            f32x4 v;
+            f32x4 bias4 = {0.0f, 0.0f, 0.0f, 0.0f}, mul4 = {1.0f, 1.0f, 1.0f, 1.0f};
+            if (ex.bias) bias4 = *reinterpret_cast<const f32x4*>(ex.bias + ch0 + 16 * m);
+            if (mul) mul4 = *reinterpret_cast<const f32x4*>(mul + (size_t)n * Cout + ch0 + 16 * m);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = conv_act(ldexpf(acc[m][nb][r], undo), act);
-            if (mul) v = v * *reinterpret_cast<const f32x4*>(mul + (size_t)n * Cout + ch0 + 16 * m);
+            for (int nb = 0; nb < 4; ++nb) {
+                const int py = y0 + 4 * wave + nb;
+                f32x4 v;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const unsigned bits = __builtin_bit_cast(unsigned, (float)v[r]) & 0x7fffffffu;
-                top = bits > top ? bits : top;
+                for (int r = 0; r < 4; ++r) {
+                    const float sum = ldexpf(acc[m][nb][r], undo);
+                    v[r] = ex.bias ? conv_bias_act(sum, bias4[r], act) : conv_act_f(sum, act);
+                    if (mul) v[r] = v[r] * mul4[r];
+                }
+                acc[m][nb] = v;
+                if (py >= h || px >= w) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const unsigned bits = __builtin_bit_cast(unsigned, (float)v[r]) & 0x7fffffffu;
+                    top = bits > top ? bits : top;
+                }
+                *reinterpret_cast<f32x4*>(out + (((size_t)n * h + py) * w + px) * Cout + ch0 + 16 * m) = v;
             }
-            *reinterpret_cast<f32x4*>(o + 16 * m) = v;
+        }
+        if (ex.stats) {                                          // (the same in every thread)
+            // Per channel over the tile's real pixels: mean = ref + sum(y - ref) / k with ref the tile's first pixel, then M2 about that
+            // mean (mvnerf_conv.h).  A channel's 256 pixels lie in 4 registers (nb) x 16 lanes (col) x 4 waves: registers, then an
+            // xor butterfly over the 16 lanes, then the four waves in order through LDS.  Every order is fixed.
+            float* red = reinterpret_cast<float*>(lds);          // [0, 64) ref, then mean; [64, 320) one row of 64 per wave
+            const int chl = 4 * grp;                             // this lane's channels of the tile: 16 m + chl + r
+            const int count = conv_tile_pixels(h, w, ty, tx, kCvTile);
+            bool real[4];
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) real[nb] = y0 + 4 * wave + nb < h && px < w;
+            __syncthreads();                                     // the last stage has been read
+            if (wave == 0 && col == 0)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) *reinterpret_cast<f32x4*>(red + 16 * m + chl) = acc[m][0];
+            __syncthreads();
+            f32x4 centre[4];                                     // ref in the first pass, the mean in the second
+#pragma unroll
+            for (int m = 0; m < 4; ++m) centre[m] = *reinterpret_cast<const f32x4*>(red + 16 * m + chl);
+#pragma unroll
+            for (int pass = 0; pass < 2; ++pass) {
+                f32x4 part[4];
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float s = 0.0f;
+#pragma unroll
+                        for (int nb = 0; nb < 4; ++nb) {
+                            const float t = pass == 0 ? acc[m][nb][r] - centre[m][r] : bn_sq_dev(acc[m][nb][r], centre[m][r]);
+                            s = s + (real[nb] ? t : 0.0f);
+                        }
+#pragma unroll
+                        for (int mask = 1; mask < 16; mask <<= 1) s = s + __shfl_xor(s, mask);
+                        part[m][r] = s;
+                    }
+                if (pass) __syncthreads();                       // the means have been read
+                if (col == 0)
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) *reinterpret_cast<f32x4*>(red + 64 + 64 * wave + 16 * m + chl) = part[m];
+                __syncthreads();
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const float* q = red + 64 + 16 * m + chl;
+                    const f32x4 total = ((*reinterpret_cast<const f32x4*>(q) + *reinterpret_cast<const f32x4*>(q + 64)) +
+                                         *reinterpret_cast<const f32x4*>(q + 128)) + *reinterpret_cast<const f32x4*>(q + 192);
+                    if (pass == 0) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) centre[m][r] = bn_tile_mean(centre[m][r], total[r], count);
+                    }
+                    if (wave == 0 && col == 0)                   // this workgroup's own slots: plain stores, no atomics
+                        *reinterpret_cast<f32x4*>(ex.stats + ((size_t)blockIdx.x * 2 + pass) * kCvCout + 16 * m + chl) = pass == 0 ? centre[m] : total;
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+            const int py = y0 + 4 * wave + nb;
+            if (py >= h || px >= w) continue;
+            float* o = out + (((size_t)n * h + py) * w + px) * Cout + ch0;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                f32x4 v;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = conv_act(ldexpf(acc[m][nb][r], undo), act);
+                if (mul) v = v * *reinterpret_cast<const f32x4*>(mul + (size_t)n * Cout + ch0 + 16 * m);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const unsigned bits = __builtin_bit_cast(unsigned, (float)v[r]) & 0x7fffffffu;
+                    top = bits > top ? bits : top;
+                }
+                *reinterpret_cast<f32x4*>(o + 16 * m) = v;
+            }
         }
     }
     if (amax_out) {                                              // (the same in every thread)
@@ -269,6 +377,51 @@ int launch_absmax(const float* x, long n, float* amax, hipStream_t st, const cha
 
 bool conv_channels_ok(int cin, int cout) { return cin >= kCvChunk && cin % kCvChunk == 0 && cout >= kCvCout && cout % kCvCout == 0; }
 
+// mvnerf_conv3x3_nhwc (bias, act_in, stats = null, 0, null: the plain instantiation) and mvnerf_conv3x3_nhwc_ex: the checks, then one launch
+int conv3x3_call(const char* who, const float* a, int Ca, const float* amax_a, const float* b, int Cb, const float* amax_b, const void* packed,
+                 int N, int h, int w, int Cout, int act, const float* mul, float* out, float* amax_out, const float* bias, int act_in,
+                 float* stats, mvnerf_stream_t stream) {
+    if (!a || !amax_a || !packed || !out)
+        return api_fail(MVNERF_E_ARG, "%s: null pointer (%s)", who, !a ? "a" : !amax_a ? "amax_a" : !packed ? "packed" : "out");
+    if ((b != nullptr) != (Cb != 0) || (b != nullptr) != (amax_b != nullptr))
+        return api_fail(MVNERF_E_ARG, "%s: b, Cb=%d and amax_b go together (all given, or NULL, 0, NULL)", who, Cb);
+    if (N <= 0 || h <= 0 || w <= 0) return api_fail(MVNERF_E_ARG, "%s: N=%d h=%d w=%d", who, N, h, w);
+    if (Ca < kCvChunk || Ca % kCvChunk) return api_fail(MVNERF_E_SHAPE, "%s: Ca=%d (a multiple of 32, at least 32)", who, Ca);
+    if (Cb < 0 || Cb % kCvChunk) return api_fail(MVNERF_E_SHAPE, "%s: Cb=%d (a multiple of 32, or 0 without b)", who, Cb);
+    if (Cout < kCvCout || Cout % kCvCout) return api_fail(MVNERF_E_SHAPE, "%s: Cout=%d (a multiple of 64, at least 64)", who, Cout);
+    if (act < 0 || act > 2) return api_fail(MVNERF_E_SHAPE, "%s: act=%d (0 identity, 1 relu, 2 elu)", who, act);
+    if (act_in < 0 || act_in > 2) return api_fail(MVNERF_E_SHAPE, "%s: act_in=%d (0 identity, 1 relu, 2 elu)", who, act_in);
+    const int tiles_x = (w + kCvTile - 1) / kCvTile, tiles_y = (h + kCvTile - 1) / kCvTile;
+    const long pixels = (long)N * h * w, blocks = (long)N * tiles_x * tiles_y * (Cout / kCvCout);
+    if (pixels > 0x7fffffffL || blocks > 0x7fffffffL)
+        return api_fail(MVNERF_E_SHAPE, "%s: N=%d h=%d w=%d Cout=%d is %ld pixels in %ld tiles (each at most 2^31 - 1)", who, N, h, w, Cout, pixels,
+                        blocks);
+    if (!aligned16(a) || !aligned16(b) || !aligned16(packed) || !aligned16(mul) || !aligned16(out))
+        return api_fail(MVNERF_E_ALIGN, "%s: %s must be 16-byte aligned", who,
+                        !aligned16(a) ? "a" : !aligned16(b) ? "b" : !aligned16(packed) ? "packed" : !aligned16(mul) ? "mul" : "out");
+    if (!aligned16(bias) || !aligned16(stats))
+        return api_fail(MVNERF_E_ALIGN, "%s: %s must be 16-byte aligned", who, !aligned16(bias) ? "bias" : "stats");
+    if (!aligned4(amax_a) || !aligned4(amax_b) || !aligned4(amax_out))
+        return api_fail(MVNERF_E_ALIGN, "%s: %s must be 4-byte aligned", who, !aligned4(amax_a) ? "amax_a" : !aligned4(amax_b) ? "amax_b" : "amax_out");
+    static DeviceSetup setup;
+    MV_HIP(device_setup(setup, {{conv3x3_kernel<0>, kCvLdsBytes}, {conv3x3_kernel<0, ConvEx>, kCvLdsBytes},
+                                {conv3x3_kernel<1, ConvEx>, kCvLdsBytes}, {conv3x3_kernel<2, ConvEx>, kCvLdsBytes}}), who);
+    const dim3 grid((unsigned)blocks), block(kCvThreads);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned char* pk = static_cast<const unsigned char*>(packed);
+    unsigned* top = reinterpret_cast<unsigned*>(amax_out);
+    if (!bias && !act_in && !stats) {
+        hipLaunchKernelGGL(conv3x3_kernel<0>, grid, block, kCvLdsBytes, st, a, b, Ca, Cb, amax_a, amax_b, pk, N, h, w, Cout, act, mul, out, top,
+                           tiles_x, tiles_y);
+    } else {
+        const ConvEx ex{bias, stats};
+        auto* kernel = act_in == 0 ? conv3x3_kernel<0, ConvEx> : act_in == 1 ? conv3x3_kernel<1, ConvEx> : conv3x3_kernel<2, ConvEx>;
+        hipLaunchKernelGGL(kernel, grid, block, kCvLdsBytes, st, a, b, Ca, Cb, amax_a, amax_b, pk, N, h, w, Cout, act, mul, out, top, tiles_x,
+                           tiles_y, ex);
+    }
+    return hip_status(hipGetLastError(), who);
+}
+
 }  // namespace
 
 }  // namespace mvnerf
@@ -309,33 +462,22 @@ int mvnerf_absmax_f32(const float* x, long n, float* amax, mvnerf_stream_t strea
 
 int mvnerf_conv3x3_nhwc(const float* a, int Ca, const float* amax_a, const float* b, int Cb, const float* amax_b, const void* packed, int N,
                         int h, int w, int Cout, int act, const float* mul, float* out, float* amax_out, mvnerf_stream_t stream) {
+    return mvnerf::conv3x3_call("mvnerf_conv3x3_nhwc", a, Ca, amax_a, b, Cb, amax_b, packed, N, h, w, Cout, act, mul, out, amax_out, nullptr, 0,
+                                nullptr, stream);
+}
+
+size_t mvnerf_conv3x3_stats_bytes(int N, int h, int w, int Cout) {
     using namespace mvnerf;
-    const char* who = "mvnerf_conv3x3_nhwc";
-    if (!a || !amax_a || !packed || !out)
-        return api_fail(MVNERF_E_ARG, "%s: null pointer (%s)", who, !a ? "a" : !amax_a ? "amax_a" : !packed ? "packed" : "out");
-    if ((b != nullptr) != (Cb != 0) || (b != nullptr) != (amax_b != nullptr))
-        return api_fail(MVNERF_E_ARG, "%s: b, Cb=%d and amax_b go together (all given, or NULL, 0, NULL)", who, Cb);
-    if (N <= 0 || h <= 0 || w <= 0) return api_fail(MVNERF_E_ARG, "%s: N=%d h=%d w=%d", who, N, h, w);
-    if (Ca < kCvChunk || Ca % kCvChunk) return api_fail(MVNERF_E_SHAPE, "%s: Ca=%d (a multiple of 32, at least 32)", who, Ca);
-    if (Cb < 0 || Cb % kCvChunk) return api_fail(MVNERF_E_SHAPE, "%s: Cb=%d (a multiple of 32, or 0 without b)", who, Cb);
-    if (Cout < kCvCout || Cout % kCvCout) return api_fail(MVNERF_E_SHAPE, "%s: Cout=%d (a multiple of 64, at least 64)", who, Cout);
-    if (act < 0 || act > 2) return api_fail(MVNERF_E_SHAPE, "%s: act=%d (0 identity, 1 relu, 2 elu)", who, act);
-    const int tiles_x = (w + kCvTile - 1) / kCvTile, tiles_y = (h + kCvTile - 1) / kCvTile;
-    const long pixels = (long)N * h * w, blocks = (long)N * tiles_x * tiles_y * (Cout / kCvCout);
-    if (pixels > 0x7fffffffL || blocks > 0x7fffffffL)
-        return api_fail(MVNERF_E_SHAPE, "%s: N=%d h=%d w=%d Cout=%d is %ld pixels in %ld tiles (each at most 2^31 - 1)", who, N, h, w, Cout, pixels,
-                        blocks);
-    if (!aligned16(a) || !aligned16(b) || !aligned16(packed) || !aligned16(mul) || !aligned16(out))
-        return api_fail(MVNERF_E_ALIGN, "%s: %s must be 16-byte aligned", who,
-                        !aligned16(a) ? "a" : !aligned16(b) ? "b" : !aligned16(packed) ? "packed" : !aligned16(mul) ? "mul" : "out");
-    if (!aligned4(amax_a) || !aligned4(amax_b) || !aligned4(amax_out))
-        return api_fail(MVNERF_E_ALIGN, "%s: %s must be 4-byte aligned", who, !aligned4(amax_a) ? "amax_a" : !aligned4(amax_b) ? "amax_b" : "amax_out");
-    static DeviceSetup setup;
-    MV_HIP(device_setup(setup, {{conv3x3_kernel, kCvLdsBytes}}), who);
-    hipLaunchKernelGGL(conv3x3_kernel, dim3((unsigned)blocks), dim3(kCvThreads), kCvLdsBytes, static_cast<hipStream_t>(stream), a, b, Ca, Cb,
-                       amax_a, amax_b, static_cast<const unsigned char*>(packed), N, h, w, Cout, act, mul, out,
-                       reinterpret_cast<unsigned*>(amax_out), tiles_x, tiles_y);
-    return hip_status(hipGetLastError(), who);
+    if (N <= 0 || h <= 0 || w <= 0 || Cout < kCvCout || Cout % kCvCout) return 0;
+    const size_t tiles = (size_t)N * ((h + kCvTile - 1) / kCvTile) * ((w + kCvTile - 1) / kCvTile);
+    return tiles * (Cout / kCvCout) * 2 * kCvCout * sizeof(float);
+}
+
+int mvnerf_conv3x3_nhwc_ex(const float* a, int Ca, const float* amax_a, const float* b, int Cb, const float* amax_b, const void* packed, int N,
+                           int h, int w, int Cout, int act, const float* mul, float* out, float* amax_out, const float* bias, int act_in,
+                           float* stats, mvnerf_stream_t stream) {
+    return mvnerf::conv3x3_call("mvnerf_conv3x3_nhwc_ex", a, Ca, amax_a, b, Cb, amax_b, packed, N, h, w, Cout, act, mul, out, amax_out, bias,
+                                act_in, stats, stream);
 }
 
 }  // extern "C"

@@ -105,4 +105,88 @@ MVC_HD void conv_cut_act(float x, int ex, uint16_t& b0, uint16_t& b1) {
     b1 = conv_rn16(kConvRemScale * (tx - conv_f16_f32(b0)));
 }
 
+// ---- bias, source activation and batch statistics (mvnerf_conv3x3_nhwc_ex, batchnorm.hip) ---------------------------------
+// tests/cpu_bn builds this part for the host.
+//
+//   act_in      x' = act_in(x) as the halo is read, before the cut.  |relu(x)| <= |x| and |elu(x)| <= |x| (expm1 of a negative number lies
+//               in (-1, 0) and |expm1(x)| <= |x|), so a bound of |x| stays a bound of |x'|: the caller's amax needs no second pass.  Taps
+//               outside the image are zero AFTER the activation (Keras pads the activated map).
+//   bias        y = act(sum + bias[co]): the bias joins the un-scaled sum, before the activation
+//   tile stats  over the k real pixels of one workgroup's tile, per channel: with ref = the value of the tile's first pixel,
+//               mean = ref + (sum_i (y_i - ref)) / k, then M2 = sum_i (y_i - mean)^2 about that mean.  No raw sum of y or of y^2 is ever
+//               formed: a constant map gives mean == the constant and M2 == 0 exactly, and |mean| >> sigma costs nothing.
+//   combine     Chan's update of (count, mean, M2) pairs, in double, tiles in a fixed order
+//   apply       out = act(((y - mean) * rstd) * gamma + beta (+ skip)), one rounding per written operation
+MVC_HD float conv_act_f(float x, int act) {
+    if (act == 1) return x > 0.0f ? x : 0.0f;
+    if (act == 2) return x > 0.0f ? x : expm1f(x);
+    return x;
+}
+
+MVC_HD float conv_bias_act(float sum, float bias, int act) { return conv_act_f(sum + bias, act); }
+
+MVC_HD float bn_tile_mean(float ref, float dev_sum, int count) { return ref + dev_sum / (float)count; }
+
+MVC_HD float bn_sq_dev(float y, float mean) {
+    const float d = y - mean;
+    return d * d;
+}
+
+struct BnMoments {
+    double count, mean, m2;
+};
+
+// (count, mean, M2) of the union of two disjoint sets (Chan, Golub, LeVeque 1979)
+MVC_HD BnMoments bn_chan_combine(BnMoments a, BnMoments b) {
+    if (b.count == 0.0) return a;
+    if (a.count == 0.0) return b;
+    const double n = a.count + b.count, delta = b.mean - a.mean;
+    BnMoments r;
+    r.count = n;
+    r.mean = a.mean + delta * (b.count / n);
+    r.m2 = a.m2 + b.m2 + delta * delta * (a.count * b.count / n);
+    return r;
+}
+
+// biased variance, as Keras and torch normalise
+MVC_HD float bn_rstd(BnMoments m, double eps) { return (float)(1.0 / sqrt(m.m2 / m.count + eps)); }
+
+MVC_HD float bn_apply_one(float y, float mean, float rstd, float gamma, float beta, bool has_skip, float skip, int act) {
+    float t = y - mean;
+    t = t * rstd;
+    t = t * gamma;
+    t = t + beta;
+    if (has_skip) t = t + skip;
+    return act == 1 ? (t < 0.0f ? 0.0f : t) : t;          // (a NaN stays a NaN: the statistics of a poisoned map must not read as zeros)
+}
+
+// real pixels of tile (ty, tx) of an (h, w) map cut into 16 x 16 tiles
+MVC_HD int conv_tile_pixels(int h, int w, int ty, int tx, int tile) {
+    const int rows = h - ty * tile < tile ? h - ty * tile : tile, cols = w - tx * tile < tile ? w - tx * tile : tile;
+    return rows * cols;
+}
+
+// The finalize pass's order: the tiles of one channel tile - [image][tile row][tile column], each 64 means then 64 M2 - are cut into
+// kBnRuns runs of consecutive tiles; a run is combined tile by tile, then the runs in order.  src points at this channel's mean of tile 0.
+constexpr int kBnTile = 16;                  // conv3x3.hip: kCvTile, kCvCout
+constexpr int kBnCout = 64;
+constexpr int kBnRuns = 16;
+
+MVC_HD BnMoments bn_combine_run(const float* src, int run, int N, int h, int w) {
+    const int tiles_x = (w + kBnTile - 1) / kBnTile, tiles_y = (h + kBnTile - 1) / kBnTile;
+    const int per_image = tiles_x * tiles_y, tiles = N * per_image;
+    const int per_run = (tiles + kBnRuns - 1) / kBnRuns;
+    const int first = run * per_run, last = first + per_run < tiles ? first + per_run : tiles;
+    BnMoments acc = {0.0, 0.0, 0.0};
+    for (int t = first; t < last; ++t) {
+        const int in_image = t % per_image;
+        BnMoments one;
+        one.count = (double)conv_tile_pixels(h, w, in_image / tiles_x, in_image % tiles_x, kBnTile);
+        one.mean = (double)src[(size_t)t * 2 * kBnCout];
+        one.m2 = (double)src[(size_t)t * 2 * kBnCout + kBnCout];
+        acc = bn_chan_combine(acc, one);
+    }
+    return acc;
+}
+
 }  // namespace mvnerf

@@ -50,39 +50,81 @@ def _keras_bn(c):
     return nn.BatchNorm2d(c, eps=1e-3, momentum=0.01)          # Keras momentum 0.99 = torch momentum 0.01
 
 
+def _check_switch(value, name='fused_conv'):
+    if not (value is True or value is False or (isinstance(value, str) and value == 'auto')):      # (1 == True, but the code asks `is True`)
+        raise ValueError(f"{name}: {value!r}, expected True, False or 'auto'")
+    return value
+
+
 class Block(nn.Module):
     """layers.py:7-33.  One BatchNormalization serves both convolutions (the attribute is assigned twice in the reference)
-    and it always normalises with batch statistics (`training=True` is hard-coded there)."""
+    and it always normalises with batch statistics (`training=True` is hard-coded there).
+    fused_conv (default False: torch): each convolution as ops.conv3x3 (bias, tile statistics) -> ops.bn_finalize -> ops.bn_apply
+    (skip, relu) under the rule of :func:`_wants_fused`, see :func:`conv3x3_bn`; the downsample branch stays torch."""
 
-    def __init__(self, c_in, n_features, downsample=None):
+    def __init__(self, c_in, n_features, downsample=None, fused_conv=False):
         super().__init__()
         self.conv_1 = SameConv2d(c_in, n_features, 3)
         self.conv_2 = SameConv2d(n_features, n_features, 3)
         self.norm_1 = _keras_bn(n_features)
         self.downsample = downsample
+        self.fused_conv = fused_conv
+
+    @property
+    def fused_conv(self):
+        return self._fused_conv
+
+    @fused_conv.setter
+    def fused_conv(self, value):
+        self._fused_conv = _check_switch(value)
 
     def _norm(self, x):
         return F.batch_norm(x, None, None, self.norm_1.weight, self.norm_1.bias, True, 0.0, self.norm_1.eps)
 
-    def forward(self, x):
+    def run(self, x, amax=None):
+        """-> (out, amax | None): amax bounds |x| (a device float, or None), the returned one is max |out| when conv_2 ran fused."""
         skip = x if self.downsample is None else self.downsample(x)
-        out = F.relu(self._norm(self.conv_1(x)))
-        out = self._norm(self.conv_2(out))
-        return F.relu(out + skip)
+        out, amax = conv3x3_bn(self.conv_1, self.norm_1, x, None, self.fused_conv, amax)
+        return conv3x3_bn(self.conv_2, self.norm_1, out, skip, self.fused_conv, amax)
+
+    def forward(self, x):
+        if self.fused_conv is False:
+            skip = x if self.downsample is None else self.downsample(x)
+            out = F.relu(self._norm(self.conv_1(x)))
+            out = self._norm(self.conv_2(out))
+            return F.relu(out + skip)
+        return self.run(x)[0]
 
 
 class ConvolutionalEncoder(nn.Module):
-    """layers.py:36-57: 7x7/2 conv -> BN -> ReLU -> 3 residual blocks of n_features / 2 channels; (H, W) -> (H/2, W/2)."""
+    """layers.py:36-57: 7x7/2 conv -> BN -> ReLU -> 3 residual blocks of n_features / 2 channels; (H, W) -> (H/2, W/2).
+    fused_conv (default False): handed to the three blocks, every apply's amax_out the next convolution's amax; the stem stays torch."""
 
-    def __init__(self, n_features=256, stem=64):
+    def __init__(self, n_features=256, stem=64, fused_conv=False):
         super().__init__()
         half = n_features // 2
         downsample = nn.Sequential(SameConv2d(stem, half, 1, bias=False), _keras_bn(half))
         self.conv_features = nn.Sequential(SameConv2d(3, stem, 7, stride=2, bias=False), _keras_bn(stem), nn.ReLU(),
                                            Block(stem, half, downsample), Block(half, half), Block(half, half))
+        self.fused_conv = fused_conv
+
+    @property
+    def fused_conv(self):
+        return self._fused_conv
+
+    @fused_conv.setter
+    def fused_conv(self, value):
+        self._fused_conv = _check_switch(value)
+        for block in self.conv_features[3:]:
+            block.fused_conv = value
 
     def forward(self, x):
-        return self.conv_features(x)
+        if self.fused_conv is False:
+            return self.conv_features(x)
+        x, amax = self.conv_features[:3](x), None
+        for block in self.conv_features[3:]:
+            x, amax = block.run(x, amax)
+        return x
 
 
 class KerasMHA(nn.Module):
@@ -164,11 +206,16 @@ def _resize(x, size):
 
 class VisionTransformerEncoder(nn.Module):
     """layers.py:160-229: four token maps -> post-processing to 4 / 2 / 1 / 0.5 x the patch grid -> 3x3 decode convs to
-    n_features -> bilinear up-sampling to 8 x the grid -> concat -> ReLU, conv, ReLU, conv to n_features / 2."""
+    n_features -> bilinear up-sampling to 8 x the grid -> concat -> ReLU, conv, ReLU, conv to n_features / 2.
+    fused_conv (default False: torch): under the rule of :func:`_wants_fused` both `output_conv` convolutions run as ops.conv3x3 with
+    act_in = relu and their bias, and each `conv_decode` whose channel counts the kernel takes (multiples of 32 -> 64; at the reference's
+    sizes all but the first, 48 -> 256) as a plain ops.conv3x3 - under 'auto' only where the launch is large enough to beat the torch
+    path (:func:`conv3x3_auto_pays`); the others, the post-processing and the ViT stay torch."""
 
     def __init__(self, img_size=(224, 224), patch_size=16, embed_dim=768, n_features=256, mlp_ratio=4, hooks=(3, 6, 9, 12),
-                 features=(48, 96, 192, 384), num_heads=12):
+                 features=(48, 96, 192, 384), num_heads=12, fused_conv=False):
         super().__init__()
+        self.fused_conv = fused_conv
         self.vit = VisionTransformer(img_size, patch_size, embed_dim, mlp_ratio, hooks, num_heads)
         f = features
 
@@ -185,23 +232,55 @@ class VisionTransformerEncoder(nn.Module):
         self.output_conv = nn.Sequential(nn.ReLU(), SameConv2d(4 * n_features, n_features, 3), nn.ReLU(),
                                          SameConv2d(n_features, n_features // 2, 3))
 
+    @property
+    def fused_conv(self):
+        return self._fused_conv
+
+    @fused_conv.setter
+    def fused_conv(self, value):
+        self._fused_conv = _check_switch(value)
+
     def forward(self, x):
         gh, gw = self.vit.grid_size
         feats = [t[:, 1:].transpose(1, 2).reshape(t.shape[0], -1, gh, gw) for t in self.vit(x)]
         post = (self.post_process_1, self.post_process_2, self.post_process_3, self.post_process_4)
-        maps = [_up(dec(pp(t)), s) for t, pp, dec, s in zip(feats, post, self.conv_decode, (2, 4, 8, 16))]
-        return self.output_conv(torch.cat(maps, 1))
+        if self.fused_conv is False:
+            maps = [_up(dec(pp(t)), s) for t, pp, dec, s in zip(feats, post, self.conv_decode, (2, 4, 8, 16))]
+            return self.output_conv(torch.cat(maps, 1))
+        maps = []
+        for t, pp, dec, s in zip(feats, post, self.conv_decode, (2, 4, 8, 16)):
+            t = pp(t)
+            # (True is about gradients and devices, not channel counts; 'auto' also leaves launches too small to pay to torch)
+            takes = conv3x3_fusable(dec, t.shape[1]) and (self.fused_conv is True or conv3x3_auto_pays(t.shape[0], *t.shape[2:], dec.out_channels))
+            switch = self.fused_conv if takes else False
+            maps.append(_up(conv3x3_act(dec, t, None, None, switch)[0], s))
+        conv_a, conv_b = self.output_conv[1], self.output_conv[3]
+        x, amax = conv3x3_bias(conv_a, torch.cat(maps, 1), 'relu', self.fused_conv)
+        return conv3x3_bias(conv_b, x, 'relu', self.fused_conv, amax)[0]
 
 
 class VisualFeatures(nn.Module):
-    """layers.py:232-259: images (N, H, W, 3) in [0, 1] -> (N, H/2, W/2, n_features) = [ViT latents resized | conv features]."""
+    """layers.py:232-259: images (N, H, W, 3) in [0, 1] -> (N, H/2, W/2, n_features) = [ViT latents resized | conv features].
+    fused_conv: False (default) | True | 'auto' - handed to both encoders: their stride-1 3x3 convolutions and the batch-statistics
+    normalisation behind the blocks' as HIP passes when on the GPU and nothing needs a gradient (inference only, no backward)."""
 
-    def __init__(self, n_features=256, original_image_size=(480, 640), transformer_image_size=(224, 224), **vit_kw):
+    def __init__(self, n_features=256, original_image_size=(480, 640), transformer_image_size=(224, 224), fused_conv=False, **vit_kw):
         super().__init__()
         self.conv_features = ConvolutionalEncoder(n_features)
         self.vision_transformer = VisionTransformerEncoder(img_size=transformer_image_size, n_features=n_features, **vit_kw)
         self.transformer_image_size = tuple(transformer_image_size)
         self.half_size = (original_image_size[0] // 2, original_image_size[1] // 2)
+        self.fused_conv = fused_conv
+
+    @property
+    def fused_conv(self):
+        return self._fused_conv
+
+    @fused_conv.setter
+    def fused_conv(self, value):
+        self._fused_conv = _check_switch(value)
+        self.conv_features.fused_conv = value
+        self.vision_transformer.fused_conv = value
 
     def forward(self, images_nhwc):
         x = images_nhwc.permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
@@ -311,9 +390,10 @@ def _activation(name):
     return _ACT_FNS[name]
 
 
-def conv3x3_fusable(conv, c_a, c_b=0):
-    """Whether ops.conv3x3 takes this convolution over [a | b]: 3x3, stride 1, no bias, channel counts in multiples of 32 / 32 / 64."""
-    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and conv.bias is None and c_a + c_b == conv.in_channels
+def conv3x3_fusable(conv, c_a, c_b=0, bias=False):
+    """Whether ops.conv3x3 takes this convolution over [a | b]: 3x3, stride 1, channel counts in multiples of 32 / 32 / 64, and no bias
+    unless the caller hands it over (`bias=True`: the paths of VisualFeatures)."""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and (bias or conv.bias is None) and c_a + c_b == conv.in_channels
             and c_a >= 32 and c_a % 32 == 0 and c_b % 32 == 0 and conv.out_channels % 64 == 0)
 
 
@@ -353,6 +433,65 @@ def conv3x3_act(conv, a, b, activation, fused_conv=False, mul=None, amax_a=None,
     out = ops.conv3x3(nhwc(a), nhwc(b), _packed_conv3x3(conv), c_out, _ACT_CODES[activation], mul=mul, amax_a=amax_a, amax_b=amax_b,
                       amax_out=amax)
     return out.permute(0, 3, 1, 2), amax
+
+
+CONV3X3_AUTO_MIN_WORKGROUPS = 48
+
+
+def conv3x3_auto_pays(n, h, w, c_out):
+    """The 'auto' rule of the `conv_decode` convolutions, the only ones of VisualFeatures on maps of a few pixels: the kernel's launch has
+    n x ceil(h / 16) x ceil(w / 16) x c_out / 64 workgroups, and at the reference's sizes with 3 views it was faster than the torch path in
+    every repeat at 48 of them (28 x 28, 96 -> 256) and slower at 12 (14 x 14 and 7 x 7); the figures are the `convs` entries of
+    profiles/visual_features_bench.json.  Three shapes at one batch size: the workgroup count as the deciding quantity is
+    an extrapolation in n (nothing between 12 and 48 was measured, and with one view the 28 x 28 launch has 16 workgroups and goes to
+    torch too) - conservative, since torch is the path that was there before."""
+    return n * -(-h // 16) * -(-w // 16) * (c_out // 64) >= CONV3X3_AUTO_MIN_WORKGROUPS
+
+
+def _fused_or_torch(fused_conv, conv, c_in, *tensors):
+    """The switch of one biased convolution of VisualFeatures: :func:`_wants_fused` on the tensors, then the channel counts - a
+    convolution the kernel does not take runs through torch under 'auto' and raises under True."""
+    fused = _wants_fused(fused_conv, conv.weight, conv.bias, *tensors, name='fused_conv')
+    if fused and not conv3x3_fusable(conv, c_in, bias=True):
+        if fused_conv is True:
+            raise ValueError(f'fused_conv=True: a {tuple(conv.kernel_size)} convolution over {c_in} -> {conv.out_channels} channels is not one '
+                             f"the HIP pass takes (3x3, stride 1, multiples of 32 -> 64); use 'auto'")
+        fused = False
+    return fused
+
+
+def _nhwc(t):
+    return None if t is None else t.detach().permute(0, 2, 3, 1).contiguous()      # free when the storage is channels-last already
+
+
+def conv3x3_bias(conv, x, act_in=None, fused_conv=False, amax=None):
+    """`conv(act_in(x))` of NCHW x with a biased 3x3 `conv` -> (out, amax | None): through torch unless `fused_conv` selects ops.conv3x3
+    with bias and act_in (zero padding after the activation, as torch pads the activated map).  amax bounds |x|; |act_in(x)| <= |x|."""
+    if not _fused_or_torch(fused_conv, conv, x.shape[1], x):
+        return conv(_ACT_FNS[act_in](x)), None
+    from . import ops
+    top = torch.empty(1, dtype=torch.float32, device=x.device)
+    out = ops.conv3x3(_nhwc(x), None, _packed_conv3x3(conv), conv.out_channels, 0, amax_a=amax, amax_out=top,
+                      bias=None if conv.bias is None else conv.bias.detach(), act_in=_ACT_CODES[act_in])
+    return out.permute(0, 3, 1, 2), top
+
+
+def conv3x3_bn(conv, norm, x, skip=None, fused_conv=False, amax=None):
+    """`relu(batch_norm(conv(x)) (+ skip))` of NCHW x with a biased 3x3 `conv` and the batch statistics of its own output (gamma, beta,
+    eps of `norm`; layers.py:22-33) -> (out, amax | None).  Through torch unless `fused_conv` selects the three HIP passes: ops.conv3x3
+    with the bias and the per-tile statistics, ops.bn_finalize, ops.bn_apply in place with the skip, the relu and max |out|."""
+    if not _fused_or_torch(fused_conv, conv, x.shape[1], x, skip, norm.weight, norm.bias):
+        out = F.batch_norm(conv(x), None, None, norm.weight, norm.bias, True, 0.0, norm.eps)
+        return F.relu(out if skip is None else out + skip), None
+    from . import ops
+    n, _, h, w = x.shape
+    c_out = conv.out_channels
+    y, stats = ops.conv3x3(_nhwc(x), None, _packed_conv3x3(conv), c_out, 0, amax_a=amax,
+                           bias=None if conv.bias is None else conv.bias.detach(), stats=True)
+    mean, rstd = ops.bn_finalize(stats, n, h, w, c_out, norm.eps)
+    top = torch.empty(1, dtype=torch.float32, device=x.device)
+    out = ops.bn_apply(y, mean, rstd, norm.weight.detach(), norm.bias.detach(), skip=_nhwc(skip), act='relu', out=y, amax_out=top)
+    return out.permute(0, 3, 1, 2), top
 
 
 class DoubleConv(nn.Module):
@@ -588,15 +727,15 @@ class LanguageFeatureProducer(nn.Module):
     combined_features (N, H, W, 256), NHWC-contiguous in `out_dtype`.  VisualFeatures + the CLIP pyramid + the text embedding +
     CombineCLIPVisualV4(use_dense=True, activation='elu').  Nothing in it trains (the reference's tape watches `grasp_readout` only),
     so with fused_tail='auto' the tail is the fused HIP pass whenever the producer is on the GPU; fused_conv (default False) is handed
-    to the fusion: its 3x3 convolutions as ops.conv3x3 launches."""
+    to the fusion: its 3x3 convolutions as ops.conv3x3 launches; fused_visual (default False) is the `fused_conv` of VisualFeatures."""
 
     def __init__(self, original_image_size=(480, 640), out_dtype=torch.float32, fused_tail='auto', n_features=256, clip_pyramid=None,
-                 clip_text=None, combine_kw=None, fused_conv=False, **visual_kw):
+                 clip_text=None, combine_kw=None, fused_conv=False, fused_visual=False, **visual_kw):
         super().__init__()
         h, w = original_image_size
         if h % 16 or w % 16:
             raise ValueError('image height and width must be multiples of 16 (the fusion starts at 1/16 resolution)')
-        self.visual_features = VisualFeatures(n_features, original_image_size, **visual_kw)
+        self.visual_features = VisualFeatures(n_features, original_image_size, fused_conv=fused_visual, **visual_kw)
         self.clip_pyramid = clip_pyramid if clip_pyramid is not None else SyntheticCLIPPyramid()
         self.clip_text = clip_text if clip_text is not None else SyntheticCLIPText()
         kw = dict(use_dense=True, activation='elu', half_size=(h // 2, w // 2), visual_channels=n_features, fused_tail=fused_tail,
@@ -906,7 +1045,7 @@ def count_parameters(module):
 
 
 __all__ = ['FeatureProducer', 'LanguageFeatureProducer', 'CombineCLIPVisualV4', 'DoubleConv', 'Up', 'ConvFusion', 'Tile',
-           'MultiplyFusion', 'conv3x3_act', 'conv3x3_fusable', 'SyntheticCLIPPyramid', 'SyntheticCLIPText', 'tokenize', 'conv_fusion_tail', 'load_combine_clip_visual_v4',
+           'MultiplyFusion', 'conv3x3_act', 'conv3x3_bias', 'conv3x3_bn', 'conv3x3_auto_pays', 'conv3x3_fusable', 'Block', 'SyntheticCLIPPyramid', 'SyntheticCLIPText', 'tokenize', 'conv_fusion_tail', 'load_combine_clip_visual_v4',
            'COMBINE_CLIP_VISUAL_V4_VARIABLES', 'VisualFeatures', 'CombineCLIPVisualV0', 'ConvolutionalEncoder', 'VisionTransformerEncoder',
            'VisionTransformer', 'TransformerBlock', 'SyntheticCLIPStage1', 'flat_net_from_keras', 'keras_from_flat_net',
            'make_encoder_optimizer', 'KerasAdam', 'convolutional_encoder_weights', 'warmup_lr_lambda', 'load_conv', 'load_conv_transpose', 'load_dense', 'load_batchnorm', 'load_mha',

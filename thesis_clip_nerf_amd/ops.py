@@ -1678,11 +1678,15 @@ def conv3x3_pack(w_hwio, out=None):
     return out
 
 
-def conv3x3(a, b, packed, cout, act, mul=None, amax_a=None, amax_b=None, out=None, amax_out=None):
+def conv3x3(a, b, packed, cout, act, mul=None, amax_a=None, amax_b=None, out=None, amax_out=None, bias=None, act_in=None, stats=None):
     """mvnerf_conv3x3_nhwc: out (N,h,w,cout) = mul[n,co] * act(conv3x3_same([a | b], W)), bias-free, stride 1, zero padding.
     a (N,h,w,Ca), b (N,h,w,Cb) or None: fp32 NHWC; packed: :func:`conv3x3_pack` of the (3,3,Ca+Cb,cout) kernel; act: 0 | 'identity',
     1 | 'relu', 2 | 'elu'; mul (N,cout) or None.  amax_a / amax_b: device floats (1,) bounding |a| / |b| (computed with :func:`absmax`
-    when missing); amax_out: a (1,) device float that receives max |out| (zeroed here)."""
+    when missing); amax_out: a (1,) device float that receives max |out| (zeroed here).
+    With any of the next three the call is mvnerf_conv3x3_nhwc_ex: bias (cout,) joins the sum before act; act_in (as act) is applied to
+    the elements of a and b as they are read - |act_in(x)| <= |x|, so amax_a / amax_b of the plain maps stay valid, and the padding is
+    zero after it; stats: True, or a float32 tensor of :func:`conv3x3_stats_bytes` / 4 elements, receives the per-tile (mean, M2) of what
+    is written for :func:`bn_finalize` - the return value is then (out, stats)."""
     _chk(a, 'a', shape=(None, None, None, None))
     n, h, w, ca = a.shape
     cb = 0
@@ -1693,9 +1697,24 @@ def conv3x3(a, b, packed, cout, act, mul=None, amax_a=None, amax_b=None, out=Non
         if act not in FUSE_ACTIVATIONS:
             raise ValueError(f'act: {act!r}, expected one of {list(FUSE_ACTIVATIONS)} or 0, 1, 2')
         act = FUSE_ACTIVATIONS[act]
+    if act_in is not None and not isinstance(act_in, int):
+        if act_in not in FUSE_ACTIVATIONS:
+            raise ValueError(f'act_in: {act_in!r}, expected one of {list(FUSE_ACTIVATIONS)} or 0, 1, 2')
+        act_in = FUSE_ACTIVATIONS[act_in]
+    act_in = int(act_in or 0)
+    if not 0 <= act_in <= 2:
+        raise ValueError(f'act_in: {act_in}, expected 0, 1 or 2')
     _chk(packed, 'packed', dtype=torch.uint8, shape=(conv3x3_packed_bytes(ca + cb, cout),))
     if mul is not None:
         _chk(mul, 'mul', shape=(n, cout))
+    if bias is not None:
+        _chk(bias, 'bias', shape=(cout,))
+    if stats is True:
+        stats = torch.empty(conv3x3_stats_bytes(n, h, w, cout) // 4, dtype=torch.float32, device=a.device)
+    elif stats is not None and stats is not False:
+        _chk(stats, 'stats', shape=(conv3x3_stats_bytes(n, h, w, cout) // 4,))
+    else:
+        stats = None
     if amax_a is None:
         amax_a = absmax(a)
     else:
@@ -1715,7 +1734,71 @@ def conv3x3(a, b, packed, cout, act, mul=None, amax_a=None, amax_b=None, out=Non
         _chk(amax_out, 'amax_out', shape=(1,))
         amax_out.zero_()
     with torch.cuda.device(a.device):
-        rc = _lib.lib().mvnerf_conv3x3_nhwc(_p(a), ca, _p(amax_a), _p(b), cb, _p(amax_b), _p(packed), n, h, w, int(cout), int(act), _p(mul),
-                                            _p(out), _p(amax_out), _stream(a))
+        if bias is None and not act_in and stats is None:
+            rc = _lib.lib().mvnerf_conv3x3_nhwc(_p(a), ca, _p(amax_a), _p(b), cb, _p(amax_b), _p(packed), n, h, w, int(cout), int(act), _p(mul),
+                                                _p(out), _p(amax_out), _stream(a))
+        else:
+            rc = _lib.lib().mvnerf_conv3x3_nhwc_ex(_p(a), ca, _p(amax_a), _p(b), cb, _p(amax_b), _p(packed), n, h, w, int(cout), int(act),
+                                                   _p(mul), _p(out), _p(amax_out), _p(bias), act_in, _p(stats), _stream(a))
     _lib.check(rc, 'conv3x3')
+    return out if stats is None else (out, stats)
+
+
+def conv3x3_stats_bytes(n, h, w, cout):
+    """Bytes of the tile-statistics buffer of a (n,h,w,cout) convolution output (mvnerf_conv3x3_stats_bytes; ValueError when cout is not
+    a multiple of 64 or a size is not positive)."""
+    nbytes = _lib.lib().mvnerf_conv3x3_stats_bytes(int(n), int(h), int(w), int(cout))
+    if nbytes == 0:
+        raise ValueError(f'conv3x3 stats: n={n} h={h} w={w} cout={cout} (positive sizes, cout a multiple of 64)')
+    return nbytes
+
+
+def bn_finalize(stats, n, h, w, cout, eps=1e-3, out=None):
+    """mvnerf_bn_finalize: the tile statistics of :func:`conv3x3` over an (n,h,w,cout) output -> (mean, rstd), each (cout,), rstd =
+    1 / sqrt(biased variance + eps) over all n h w pixels.  out: a (2, cout) tensor to write them into.  No host read."""
+    _chk(stats, 'stats', shape=(conv3x3_stats_bytes(n, h, w, cout) // 4,))
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError(f'eps: {eps}, expected a non-negative number')
+    if out is None:
+        out = torch.empty((2, cout), dtype=torch.float32, device=stats.device)
+    else:
+        _chk(out, 'out', shape=(2, cout))
+    with torch.cuda.device(stats.device):
+        rc = _lib.lib().mvnerf_bn_finalize(_p(stats), int(n), int(h), int(w), int(cout), eps, _p(out[0]), _p(out[1]), _stream(stats))
+    _lib.check(rc, 'bn_finalize')
+    return out[0], out[1]
+
+
+def bn_apply(y, mean, rstd, gamma, beta, skip=None, act=None, out=None, amax_out=None):
+    """mvnerf_bn_apply_nhwc: act(((y - mean) * rstd) * gamma + beta (+ skip)) over y (..., C) fp32, channels last; mean, rstd, gamma,
+    beta (C,); skip like y or None; act: 0 | 'identity' | None, 1 | 'relu'.  out may be y (in place).  amax_out: a (1,) device float that
+    receives max |out| (zeroed here)."""
+    _chk(y, 'y')
+    if y.dim() < 2 or y.numel() == 0:
+        raise ValueError(f'y: shape {tuple(y.shape)}, expected (..., C) with at least one pixel')
+    c = y.shape[-1]
+    if c % 4:
+        raise ValueError(f'y: {c} channels, expected a multiple of 4')
+    for t, name in ((mean, 'mean'), (rstd, 'rstd'), (gamma, 'gamma'), (beta, 'beta')):
+        _chk(t, name, shape=(c,))
+    if skip is not None:
+        _chk(skip, 'skip', shape=tuple(y.shape))
+    if not isinstance(act, int):
+        if act not in (None, 'identity', 'relu'):
+            raise ValueError(f"act: {act!r}, expected None, 'identity', 'relu' or 0, 1")
+        act = int(act == 'relu')
+    if act not in (0, 1):
+        raise ValueError(f'act: {act}, expected 0 or 1')
+    if out is None:
+        out = torch.empty_like(y)
+    else:
+        _chk(out, 'out', shape=tuple(y.shape))
+    if amax_out is not None:
+        _chk(amax_out, 'amax_out', shape=(1,))
+        amax_out.zero_()
+    with torch.cuda.device(y.device):
+        rc = _lib.lib().mvnerf_bn_apply_nhwc(_p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(skip), y.numel() // c, c, act, _p(out),
+                                             _p(amax_out), _stream(y))
+    _lib.check(rc, 'bn_apply')
     return out
