@@ -878,6 +878,41 @@ int mvnerf_bn_finalize(const float* stats, int N, int h, int w, int Cout, double
 int mvnerf_bn_apply_nhwc(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* skip,
                          long pixels, int C, int act, float* out, float* amax_out, mvnerf_stream_t stream);
 
+/* ---- the transformer blocks of the ViT (layers.py:72-95 TransformerBlock) over token rows (M, C) fp32, row-major:
+ * Dense layers at fp32 grade on the fp16 matrix pipe (the three-product rule of the 3x3 convolution above with one tap),
+ * LayerNormalization, and self-attention in fp32.  Inference only.  The block's first norm, an eval-mode BatchNormalization over the
+ * embedding axis, is mvnerf_bn_apply_nhwc with mean = the moving mean and rstd = 1 / sqrt(moving variance + eps).  Every pass is
+ * stream-ordered, reads nothing on the host, has no atomics on its output and sums in a fixed order: bit-identical from run to run. */
+
+/* Bytes of the packed stream of an (N, K) Dense weight; 0 when the shape is not accepted (K % 32, N % 64). */
+size_t mvnerf_linear_packed_bytes(int K, int N);
+
+/* weight (N, K) fp32, torch's Linear layout (the transpose of the Keras kernel) -> `packed` (16-byte aligned,
+ * mvnerf_linear_packed_bytes): a 256-byte header (max |w| found on the device, the scale exponent derived from it) and the fp16 pieces
+ * A0, A1, A0 / 64 in the order the kernel's K loop consumes them.  Call once per weight update. */
+int mvnerf_linear_pack(const float* weight, int K, int N, void* packed, mvnerf_stream_t stream);
+
+/* out (M, N) = epi(x (M, K) . W^T + bias).  amax_x: one device float, an UPPER BOUND of |x| (mvnerf_absmax_f32, or the amax_out of the
+ * pass that wrote x); 0 means an all-zero x, a non-finite bound fills out with NaN.  bias (N) or NULL.  epi: 0 nothing more, 1 exact-erf
+ * gelu, 2 `+ residual` with residual (M, N) - NULL unless epi is 2 (else MVNERF_E_ARG).  amax_out (optional): one device word the CALLER
+ * ZEROES; on return max |out|.  Any M >= 1: the last tile of 32 rows is predicated, nothing is read or written past row M.
+ * K a multiple of 32, N a multiple of 64, epi in 0..2: else MVNERF_E_SHAPE.  x, packed, bias, residual, out 16-byte aligned; out must
+ * not overlap x. */
+int mvnerf_linear_tokens(const float* x, const float* amax_x, const void* packed, const float* bias, const float* residual, long M, int K,
+                         int N, int epi, float* out, float* amax_out, mvnerf_stream_t stream);
+
+/* out = ((x - mean) * rstd) * gamma + beta per row of (M, C): mean = ref + sum(x - ref) / C with ref the row's first element, then
+ * rstd = 1 / sqrt(sum((x - mean)^2) / C + eps) (biased variance), both sums in a fixed order; one rounding per written operation.  A
+ * constant row gives out == beta.  out may be x (in place).  amax_out as above.  C a multiple of 4; all arrays 16-byte aligned. */
+int mvnerf_layer_norm_tokens(const float* x, const float* gamma, const float* beta, long M, int C, float eps, float* out, float* amax_out,
+                             mvnerf_stream_t stream);
+
+/* qkv (B, n, 3, heads, d) fp32, the output of the QKV Dense layer as it lies -> out (B, n, heads * d) = softmax_j(q_i . k_j * scale) v_j
+ * per image and head, fp32 throughout (v_mfma_f32_16x16x4_f32, the accurate expf, the row maximum subtracted first).  amax_out as above.
+ * d in {16, 32, 64}, 1 <= n <= 256: else MVNERF_E_SHAPE.  qkv, out 16-byte aligned. */
+int mvnerf_attention_tokens(const float* qkv, int B, int n, int heads, int d, float scale, float* out, float* amax_out,
+                            mvnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

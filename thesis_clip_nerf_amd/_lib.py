@@ -196,6 +196,11 @@ SIGNATURES = {
                                [c_void_p, c_int, c_void_p, c_void_p]),
     'mvnerf_bn_finalize': (c_int, [c_void_p] + [c_int] * 4 + [c_double, c_void_p, c_void_p, c_void_p]),
     'mvnerf_bn_apply_nhwc': (c_int, [c_void_p] * 6 + [c_long, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_linear_packed_bytes': (c_size_t, [c_int, c_int]),
+    'mvnerf_linear_pack': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'mvnerf_linear_tokens': (c_int, [c_void_p] * 5 + [c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_layer_norm_tokens': (c_int, [c_void_p] * 3 + [c_long, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_attention_tokens': (c_int, [c_void_p] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -150,10 +150,14 @@ class KerasMHA(nn.Module):
 
 class TransformerBlock(nn.Module):
     """layers.py:72-95, quirks kept: the first norm is a BatchNormalization over the embedding axis; `x = inputs + attn`,
-    then `inputs + mlp(LayerNorm(x))` - the second residual adds the block input, not x."""
+    then `inputs + mlp(LayerNorm(x))` - the second residual adds the block input, not x.
+    fused_vit (default False: torch): the block as seven HIP launches, see :func:`transformer_block_fused` - under the rule of
+    :func:`_wants_fused` and only in eval mode (the first norm then reads its running statistics) and for sizes the kernels take
+    (:func:`vit_block_unfusable`); otherwise 'auto' runs torch and True raises."""
 
-    def __init__(self, num_heads=12, embed_dim=768, mlp_ratio=4):
+    def __init__(self, num_heads=12, embed_dim=768, mlp_ratio=4, fused_vit=False):
         super().__init__()
+        self.fused_vit = fused_vit
         self.layer_norm_1 = nn.BatchNorm1d(embed_dim, eps=1e-3, momentum=0.01)
         self.attention = KerasMHA(embed_dim, num_heads)
         self.layer_norm_2 = nn.LayerNorm(embed_dim, eps=1e-3)
@@ -163,7 +167,21 @@ class TransformerBlock(nn.Module):
             nn.init.xavier_uniform_(lin.weight)
             nn.init.zeros_(lin.bias)
 
+    @property
+    def fused_vit(self):
+        return self._fused_vit
+
+    @fused_vit.setter
+    def fused_vit(self, value):
+        self._fused_vit = _check_switch(value, 'fused_vit')
+
     def forward(self, inputs):
+        if self.fused_vit is not False and _wants_fused(self.fused_vit, inputs, *self.parameters(), name='fused_vit'):
+            reason = vit_block_unfusable(self, inputs)
+            if reason is None:
+                return transformer_block_fused(self, inputs, self.fused_vit)
+            if self.fused_vit is True:
+                raise ValueError(f"fused_vit=True: {reason}; use 'auto'")
         x = self.layer_norm_1(inputs.transpose(1, 2)).transpose(1, 2)
         x = inputs + self.attention(x)
         x = self.layer_norm_2(x)
@@ -172,9 +190,10 @@ class TransformerBlock(nn.Module):
 
 class VisionTransformer(nn.Module):
     """layers.py:98-157 (skip_classification=True): patch embedding, class token, learned positions, `sum(hooks)`-free grouping of
-    the blocks at the hook depths; returns the token maps after each group."""
+    the blocks at the hook depths; returns the token maps after each group.
+    fused_vit (default False): handed to every block; patch embedding, class token and position add stay torch."""
 
-    def __init__(self, img_size=(224, 224), patch_size=16, embed_dim=768, mlp_ratio=4, hooks=(3, 6, 9, 12), num_heads=12):
+    def __init__(self, img_size=(224, 224), patch_size=16, embed_dim=768, mlp_ratio=4, hooks=(3, 6, 9, 12), num_heads=12, fused_vit=False):
         super().__init__()
         self.grid_size = (img_size[0] // patch_size, img_size[1] // patch_size)
         self.patch_embed = nn.Conv2d(3, embed_dim, patch_size, stride=patch_size)
@@ -185,6 +204,18 @@ class VisionTransformer(nn.Module):
         depth = [hooks[0]] + [hooks[i] - hooks[i - 1] for i in range(1, len(hooks))]
         self.transformer_blocks = nn.ModuleList(
             nn.Sequential(*[TransformerBlock(num_heads, embed_dim, mlp_ratio) for _ in range(d)]) for d in depth)
+        self.fused_vit = fused_vit
+
+    @property
+    def fused_vit(self):
+        return self._fused_vit
+
+    @fused_vit.setter
+    def fused_vit(self, value):
+        self._fused_vit = _check_switch(value, 'fused_vit')
+        for blocks in self.transformer_blocks:
+            for block in blocks:
+                block.fused_vit = value
 
     def forward(self, x):
         x = self.patch_embed(x).flatten(2).transpose(1, 2)                     # b (h w) c
@@ -210,13 +241,14 @@ class VisionTransformerEncoder(nn.Module):
     fused_conv (default False: torch): under the rule of :func:`_wants_fused` both `output_conv` convolutions run as ops.conv3x3 with
     act_in = relu and their bias, and each `conv_decode` whose channel counts the kernel takes (multiples of 32 -> 64; at the reference's
     sizes all but the first, 48 -> 256) as a plain ops.conv3x3 - under 'auto' only where the launch is large enough to beat the torch
-    path (:func:`conv3x3_auto_pays`); the others, the post-processing and the ViT stay torch."""
+    path (:func:`conv3x3_auto_pays`); the others and the post-processing stay torch.
+    fused_vit (default False), a switch of its own: the transformer blocks of the ViT as HIP launches (:class:`TransformerBlock`)."""
 
     def __init__(self, img_size=(224, 224), patch_size=16, embed_dim=768, n_features=256, mlp_ratio=4, hooks=(3, 6, 9, 12),
-                 features=(48, 96, 192, 384), num_heads=12, fused_conv=False):
+                 features=(48, 96, 192, 384), num_heads=12, fused_conv=False, fused_vit=False):
         super().__init__()
         self.fused_conv = fused_conv
-        self.vit = VisionTransformer(img_size, patch_size, embed_dim, mlp_ratio, hooks, num_heads)
+        self.vit = VisionTransformer(img_size, patch_size, embed_dim, mlp_ratio, hooks, num_heads, fused_vit)
         f = features
 
         def convT(c, k):
@@ -240,6 +272,14 @@ class VisionTransformerEncoder(nn.Module):
     def fused_conv(self, value):
         self._fused_conv = _check_switch(value)
 
+    @property
+    def fused_vit(self):
+        return self.vit.fused_vit
+
+    @fused_vit.setter
+    def fused_vit(self, value):
+        self.vit.fused_vit = value
+
     def forward(self, x):
         gh, gw = self.vit.grid_size
         feats = [t[:, 1:].transpose(1, 2).reshape(t.shape[0], -1, gh, gw) for t in self.vit(x)]
@@ -262,12 +302,14 @@ class VisionTransformerEncoder(nn.Module):
 class VisualFeatures(nn.Module):
     """layers.py:232-259: images (N, H, W, 3) in [0, 1] -> (N, H/2, W/2, n_features) = [ViT latents resized | conv features].
     fused_conv: False (default) | True | 'auto' - handed to both encoders: their stride-1 3x3 convolutions and the batch-statistics
-    normalisation behind the blocks' as HIP passes when on the GPU and nothing needs a gradient (inference only, no backward)."""
+    normalisation behind the blocks' as HIP passes when on the GPU and nothing needs a gradient (inference only, no backward).
+    fused_vit: False (default) | True | 'auto' - the ViT's transformer blocks as HIP passes, eval mode only (:class:`TransformerBlock`)."""
 
-    def __init__(self, n_features=256, original_image_size=(480, 640), transformer_image_size=(224, 224), fused_conv=False, **vit_kw):
+    def __init__(self, n_features=256, original_image_size=(480, 640), transformer_image_size=(224, 224), fused_conv=False, fused_vit=False,
+                 **vit_kw):
         super().__init__()
         self.conv_features = ConvolutionalEncoder(n_features)
-        self.vision_transformer = VisionTransformerEncoder(img_size=transformer_image_size, n_features=n_features, **vit_kw)
+        self.vision_transformer = VisionTransformerEncoder(img_size=transformer_image_size, n_features=n_features, fused_vit=fused_vit, **vit_kw)
         self.transformer_image_size = tuple(transformer_image_size)
         self.half_size = (original_image_size[0] // 2, original_image_size[1] // 2)
         self.fused_conv = fused_conv
@@ -282,10 +324,135 @@ class VisualFeatures(nn.Module):
         self.conv_features.fused_conv = value
         self.vision_transformer.fused_conv = value
 
+    @property
+    def fused_vit(self):
+        return self.vision_transformer.fused_vit
+
+    @fused_vit.setter
+    def fused_vit(self, value):
+        self.vision_transformer.fused_vit = value
+
     def forward(self, images_nhwc):
         x = images_nhwc.permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
         latents = _resize(self.vision_transformer(_resize(x, self.transformer_image_size)), self.half_size)
         return torch.cat([latents, self.conv_features(x)], 1)                  # NCHW view, channels-last storage
+
+
+# ---- the transformer block as HIP passes (csrc/token_linear.hip, csrc/attention.hip) --------------------------------------
+VIT_PASSES = ('linear_qkv', 'attention', 'linear_out', 'layer_norm', 'linear_0', 'linear_1')
+# The passes 'auto' leaves to torch inside a fused block: those whose HIP median was above the torch path's at the reference's shape
+# (3 x 197 tokens of 768 channels, `dense` / `layer_norm` entries of profiles/vit_bench.json): the QKV projection 0.95x,
+# dense_0 0.91x, dense_1 0.66x, the LayerNorm 0.61x; the out projection (1.45x) and the attention (1.44x) were faster in every repeat.
+# One shape on one box: other token counts or widths were not measured.  fused_vit=True runs every pass in HIP.
+VIT_AUTO_TORCH_PASSES = frozenset({'linear_qkv', 'layer_norm', 'linear_0', 'linear_1'})
+
+
+def _param_key(*tensors):
+    return tuple((t._version, t.data_ptr(), t.device) for t in tensors)
+
+
+def _loads(*modules):
+    return tuple(m.__dict__.get('_mvnerf_loads', 0) for m in modules)
+
+
+def _mark_loaded(module):
+    """A loader wrote `.data` (which does not bump the parameter version the packed caches key on): count it and drop the module's cache."""
+    module.__dict__['_mvnerf_loads'] = module.__dict__.get('_mvnerf_loads', 0) + 1
+    module.__dict__.pop('_mvnerf_packed', None)
+
+
+def _cached(module, key, make):
+    cached = module.__dict__.get('_mvnerf_packed')
+    if cached is None or cached[0] != key:
+        cached = (key, make())
+        module.__dict__['_mvnerf_packed'] = cached
+    return cached[1]
+
+
+def _packed_linear(lin):
+    """The packed fp16-piece stream of `lin.weight` (ops.linear_pack), cached on the module per parameter version like :func:`_packed_conv3x3`."""
+    from . import ops
+    return _cached(lin, (_param_key(lin.weight), _loads(lin)), lambda: ops.linear_pack(lin.weight.detach().contiguous()))
+
+
+def _packed_qkv(mha):
+    """(packed stream, bias) of the q, k, v projections of a :class:`KerasMHA` as ONE Dense layer to 3 heads d outputs: the three weights
+    and biases concatenated in that order, so the GEMM's output is (tokens, 3, heads, d).  Cached on the module per parameter version."""
+    from . import ops
+    lins = (mha.q, mha.k, mha.v)
+    key = (_param_key(*[t for lin in lins for t in (lin.weight, lin.bias)]), _loads(*lins))
+
+    def make():
+        weight = torch.cat([lin.weight.detach() for lin in lins], 0).contiguous()
+        return ops.linear_pack(weight), torch.cat([lin.bias.detach() for lin in lins], 0).contiguous()
+    return _cached(mha, key, make)
+
+
+def _running_rstd(bn):
+    """1 / sqrt(running_var + eps) of an eval-mode BatchNorm, cached per buffer version."""
+    key = (_param_key(bn.running_var), _loads(bn), bn.eps)
+    return _cached(bn, key, lambda: torch.rsqrt(bn.running_var.detach().double() + bn.eps).float().contiguous())
+
+
+def vit_block_unfusable(blk, inputs):
+    """None when :func:`transformer_block_fused` takes this block on these inputs, else the reason as a phrase."""
+    from . import ops
+    mha = blk.attention
+    if blk.training:
+        return 'the block is in training mode (its first norm would have to update its running statistics; call .eval())'
+    if inputs.dim() != 3 or inputs.dtype != torch.float32:
+        return f'inputs of shape {tuple(inputs.shape)} and dtype {inputs.dtype} are not float32 (batch, tokens, embed)'
+    embed = inputs.shape[2]
+    if embed % 64 or mha.h * mha.d != embed or blk.dense_0.out_features % 64:
+        return f'embed {embed} with {mha.h} heads and {blk.dense_0.out_features} hidden channels is not in multiples of 64'
+    if mha.d not in ops.ATTENTION_HEAD_DIMS:
+        return f'head dimension {mha.d} is not one of {ops.ATTENTION_HEAD_DIMS}'
+    if not 1 <= inputs.shape[1] <= ops.ATTENTION_MAX_TOKENS or inputs.shape[0] < 1:
+        return f'{inputs.shape[1]} tokens are more than the attention pass keeps ({ops.ATTENTION_MAX_TOKENS})'
+    return None
+
+
+def transformer_block_fused(blk, inputs, switch=True):
+    """:class:`TransformerBlock` on (batch, tokens, embed) as seven launches, every amax_out the next GEMM's amax_x:
+    ops.bn_apply (the first norm with its running statistics) -> ops.linear (q, k, v as one Dense layer) -> ops.attention ->
+    ops.linear (out projection + inputs) -> ops.layer_norm (in place) -> ops.linear (dense_0, gelu) -> ops.linear (dense_1 + inputs: the
+    reference adds the block input here, layers.py:94).  switch='auto' leaves the passes of VIT_AUTO_TORCH_PASSES to torch."""
+    from . import ops
+    hip = lambda name: switch is True or name not in VIT_AUTO_TORCH_PASSES
+    b, n, e = inputs.shape
+    x_in = inputs.detach().contiguous()
+    words = torch.zeros(4, dtype=torch.float32, device=x_in.device)            # the four amax words of the block, zeroed in one fill
+    word = lambda i: dict(amax_out=words[i:i + 1], amax_zeroed=True)
+    bn, mha, ln = blk.layer_norm_1, blk.attention, blk.layer_norm_2
+    amax = words[0:1]
+    x = ops.bn_apply(x_in, bn.running_mean, _running_rstd(bn), bn.weight.detach(), bn.bias.detach(), **word(0))
+    if hip('linear_qkv'):
+        packed, bias = _packed_qkv(mha)
+        qkv = ops.linear(x, packed, 3 * e, bias=bias, amax_x=amax)
+    else:
+        qkv = torch.cat([lin(x) for lin in (mha.q, mha.k, mha.v)], -1)
+    qkv = qkv.view(b, n, 3, mha.h, mha.d)
+    if hip('attention'):
+        x, amax = ops.attention(qkv, **word(1)), words[1:2]
+    else:
+        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
+        x, amax = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(b, n, e), None
+    if hip('linear_out'):
+        x = ops.linear(x, _packed_linear(mha.o), e, bias=mha.o.bias.detach(), residual=x_in, amax_x=amax)
+    else:
+        x = x_in + mha.o(x)
+    if hip('layer_norm'):
+        x, amax = ops.layer_norm(x, ln.weight.detach(), ln.bias.detach(), ln.eps, out=x, **word(2)), words[2:3]
+    else:
+        x, amax = ln(x), None
+    if hip('linear_0'):
+        x, amax = ops.linear(x, _packed_linear(blk.dense_0), blk.dense_0.out_features, bias=blk.dense_0.bias.detach(), act='gelu', amax_x=amax,
+                             **word(3)), words[3:4]
+    else:
+        x, amax = F.gelu(blk.dense_0(x)), None
+    if hip('linear_1'):
+        return ops.linear(x, _packed_linear(blk.dense_1), e, bias=blk.dense_1.bias.detach(), residual=x_in, amax_x=amax)
+    return x_in + blk.dense_1(x)
 
 
 _ACT_CODES = {None: 0, 'relu': 1, 'elu': 2}
@@ -727,15 +894,16 @@ class LanguageFeatureProducer(nn.Module):
     combined_features (N, H, W, 256), NHWC-contiguous in `out_dtype`.  VisualFeatures + the CLIP pyramid + the text embedding +
     CombineCLIPVisualV4(use_dense=True, activation='elu').  Nothing in it trains (the reference's tape watches `grasp_readout` only),
     so with fused_tail='auto' the tail is the fused HIP pass whenever the producer is on the GPU; fused_conv (default False) is handed
-    to the fusion: its 3x3 convolutions as ops.conv3x3 launches; fused_visual (default False) is the `fused_conv` of VisualFeatures."""
+    to the fusion: its 3x3 convolutions as ops.conv3x3 launches; fused_visual (default False) is the `fused_conv` of VisualFeatures,
+    fused_vit (default False) its `fused_vit`: the ViT's transformer blocks as HIP launches."""
 
     def __init__(self, original_image_size=(480, 640), out_dtype=torch.float32, fused_tail='auto', n_features=256, clip_pyramid=None,
-                 clip_text=None, combine_kw=None, fused_conv=False, fused_visual=False, **visual_kw):
+                 clip_text=None, combine_kw=None, fused_conv=False, fused_visual=False, fused_vit=False, **visual_kw):
         super().__init__()
         h, w = original_image_size
         if h % 16 or w % 16:
             raise ValueError('image height and width must be multiples of 16 (the fusion starts at 1/16 resolution)')
-        self.visual_features = VisualFeatures(n_features, original_image_size, fused_conv=fused_visual, **visual_kw)
+        self.visual_features = VisualFeatures(n_features, original_image_size, fused_conv=fused_visual, fused_vit=fused_vit, **visual_kw)
         self.clip_pyramid = clip_pyramid if clip_pyramid is not None else SyntheticCLIPPyramid()
         self.clip_text = clip_text if clip_text is not None else SyntheticCLIPText()
         kw = dict(use_dense=True, activation='elu', half_size=(h // 2, w // 2), visual_channels=n_features, fused_tail=fused_tail,
@@ -852,6 +1020,7 @@ def load_dense(lin, kernel_io, bias):
     """Keras Dense kernel (in, out) -> torch Linear (out, in)."""
     lin.weight.data.copy_(_t(kernel_io).T)
     lin.bias.data.copy_(_t(bias))
+    _mark_loaded(lin)                                    # (the packed-stream caches of the fused transformer block)
 
 
 def load_grasp_readout(readout, arrays):
@@ -882,6 +1051,7 @@ def load_batchnorm(bn, gamma, beta, moving_mean, moving_var):
     bn.bias.data.copy_(_t(beta))
     bn.running_mean.data.copy_(_t(moving_mean))
     bn.running_var.data.copy_(_t(moving_var))
+    _mark_loaded(bn)
 
 
 def load_mha(mha, q_k, q_b, k_k, k_b, v_k, v_b, o_k, o_b):
@@ -891,6 +1061,7 @@ def load_mha(mha, q_k, q_b, k_k, k_b, v_k, v_b, o_k, o_b):
         load_dense(lin, k.reshape(k.shape[0], -1), np.asarray(b).reshape(-1))
     o_k = np.asarray(o_k, dtype=np.float32)
     load_dense(mha.o, o_k.reshape(-1, o_k.shape[-1]), o_b)
+    _mark_loaded(mha)
 
 
 def load_combine_clip_visual(module, weights):
@@ -1047,6 +1218,6 @@ def count_parameters(module):
 __all__ = ['FeatureProducer', 'LanguageFeatureProducer', 'CombineCLIPVisualV4', 'DoubleConv', 'Up', 'ConvFusion', 'Tile',
            'MultiplyFusion', 'conv3x3_act', 'conv3x3_bias', 'conv3x3_bn', 'conv3x3_auto_pays', 'conv3x3_fusable', 'Block', 'SyntheticCLIPPyramid', 'SyntheticCLIPText', 'tokenize', 'conv_fusion_tail', 'load_combine_clip_visual_v4',
            'COMBINE_CLIP_VISUAL_V4_VARIABLES', 'VisualFeatures', 'CombineCLIPVisualV0', 'ConvolutionalEncoder', 'VisionTransformerEncoder',
-           'VisionTransformer', 'TransformerBlock', 'SyntheticCLIPStage1', 'flat_net_from_keras', 'keras_from_flat_net',
+           'VisionTransformer', 'TransformerBlock', 'transformer_block_fused', 'vit_block_unfusable', 'SyntheticCLIPStage1', 'flat_net_from_keras', 'keras_from_flat_net',
            'make_encoder_optimizer', 'KerasAdam', 'convolutional_encoder_weights', 'warmup_lr_lambda', 'load_conv', 'load_conv_transpose', 'load_dense', 'load_batchnorm', 'load_mha',
            'load_combine_clip_visual', 'load_grasp_readout', 'load_convolutional_encoder', 'load_transformer_block', 'count_parameters']

@@ -1770,10 +1770,10 @@ def bn_finalize(stats, n, h, w, cout, eps=1e-3, out=None):
     return out[0], out[1]
 
 
-def bn_apply(y, mean, rstd, gamma, beta, skip=None, act=None, out=None, amax_out=None):
+def bn_apply(y, mean, rstd, gamma, beta, skip=None, act=None, out=None, amax_out=None, amax_zeroed=False):
     """mvnerf_bn_apply_nhwc: act(((y - mean) * rstd) * gamma + beta (+ skip)) over y (..., C) fp32, channels last; mean, rstd, gamma,
     beta (C,); skip like y or None; act: 0 | 'identity' | None, 1 | 'relu'.  out may be y (in place).  amax_out: a (1,) device float that
-    receives max |out| (zeroed here)."""
+    receives max |out| (zeroed here, unless amax_zeroed says that the caller has done that: several words in one fill)."""
     _chk(y, 'y')
     if y.dim() < 2 or y.numel() == 0:
         raise ValueError(f'y: shape {tuple(y.shape)}, expected (..., C) with at least one pixel')
@@ -1796,9 +1796,141 @@ def bn_apply(y, mean, rstd, gamma, beta, skip=None, act=None, out=None, amax_out
         _chk(out, 'out', shape=tuple(y.shape))
     if amax_out is not None:
         _chk(amax_out, 'amax_out', shape=(1,))
-        amax_out.zero_()
+        if not amax_zeroed:
+            amax_out.zero_()
     with torch.cuda.device(y.device):
         rc = _lib.lib().mvnerf_bn_apply_nhwc(_p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(skip), y.numel() // c, c, act, _p(out),
                                              _p(amax_out), _stream(y))
     _lib.check(rc, 'bn_apply')
+    return out
+
+
+# ---- the transformer blocks of the ViT (csrc/token_linear.hip, csrc/attention.hip) ----------------------------------------
+LINEAR_EPILOGUES = {None: 0, 'gelu': 1}
+ATTENTION_MAX_TOKENS = 256
+ATTENTION_HEAD_DIMS = (16, 32, 64)
+
+
+def linear_packed_bytes(k, n):
+    """Bytes of the packed stream of an (n, k) Dense weight (k a multiple of 32, n a multiple of 64; ValueError otherwise)."""
+    nbytes = _lib.lib().mvnerf_linear_packed_bytes(int(k), int(n))
+    if nbytes == 0:
+        raise ValueError(f'linear: K={k} N={n} (K a multiple of 32, N a multiple of 64)')
+    return nbytes
+
+
+def linear_pack(weight, out=None):
+    """mvnerf_linear_pack: weight (N, K) fp32, torch's Linear layout -> the packed fp16-piece stream (uint8 tensor) that :func:`linear`
+    reads; max |w| and the scale are found on the device."""
+    _chk(weight, 'weight', shape=(None, None))
+    n, k = weight.shape
+    nbytes = linear_packed_bytes(k, n)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    else:
+        _chk(out, 'out', dtype=torch.uint8, shape=(nbytes,))
+    with torch.cuda.device(weight.device):
+        rc = _lib.lib().mvnerf_linear_pack(_p(weight), k, n, _p(out), _stream(weight))
+    _lib.check(rc, 'linear_pack')
+    return out
+
+
+def linear(x, packed, n, bias=None, act=None, residual=None, amax_x=None, out=None, amax_out=None, amax_zeroed=False):
+    """mvnerf_linear_tokens: out (..., n) = epi(x (..., K) . W^T + bias) over fp32 token rows; packed: :func:`linear_pack` of the (n, K)
+    weight; bias (n,) or None; act: None | 'gelu' (exact erf); residual like out or None, added after the bias (not together with
+    act).  amax_x: a device float (1,) bounding |x| (computed with :func:`absmax` when missing); amax_out: a (1,) device float that
+    receives max |out| (zeroed here; amax_zeroed=True says that the caller has zeroed it, as :func:`bn_apply` takes it).  Any number of
+    rows; K a multiple of 32, n a multiple of 64."""
+    _chk(x, 'x')
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f'x: shape {tuple(x.shape)}, expected (..., K) with at least one row')
+    k = x.shape[-1]
+    m = x.numel() // k
+    n = int(n)
+    _chk(packed, 'packed', dtype=torch.uint8, shape=(linear_packed_bytes(k, n),))
+    if act not in LINEAR_EPILOGUES:
+        raise ValueError(f"act: {act!r}, expected None or 'gelu'")
+    if act is not None and residual is not None:
+        raise ValueError('act and residual do not go together: the epilogue is the bias, then gelu OR the residual')
+    shape = (*x.shape[:-1], n)
+    if bias is not None:
+        _chk(bias, 'bias', shape=(n,))
+    if residual is not None:
+        _chk(residual, 'residual', shape=shape)
+    if amax_x is None:
+        amax_x = absmax(x)
+    else:
+        _chk(amax_x, 'amax_x', shape=(1,))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _chk(out, 'out', shape=shape)
+        if out.data_ptr() == x.data_ptr():
+            raise ValueError('out: must not be x (a tile reads whole rows of x while others write)')
+    if amax_out is not None:
+        _chk(amax_out, 'amax_out', shape=(1,))
+        if not amax_zeroed:
+            amax_out.zero_()
+    epi = 2 if residual is not None else LINEAR_EPILOGUES[act]
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().mvnerf_linear_tokens(_p(x), _p(amax_x), _p(packed), _p(bias), _p(residual), m, k, n, epi, _p(out), _p(amax_out),
+                                             _stream(x))
+    _lib.check(rc, 'linear')
+    return out
+
+
+def layer_norm(x, gamma, beta, eps=1e-3, out=None, amax_out=None, amax_zeroed=False):
+    """mvnerf_layer_norm_tokens: ((x - mean) * rstd) * gamma + beta per row of x (..., C) fp32 with the biased variance; gamma, beta (C,).
+    out may be x (in place).  amax_out: a (1,) device float that receives max |out| (zeroed here).  C a multiple of 4."""
+    _chk(x, 'x')
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f'x: shape {tuple(x.shape)}, expected (..., C) with at least one row')
+    c = x.shape[-1]
+    if c % 4:
+        raise ValueError(f'x: {c} channels, expected a multiple of 4')
+    _chk(gamma, 'gamma', shape=(c,))
+    _chk(beta, 'beta', shape=(c,))
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError(f'eps: {eps}, expected a non-negative number')
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk(out, 'out', shape=tuple(x.shape))
+    if amax_out is not None:
+        _chk(amax_out, 'amax_out', shape=(1,))
+        if not amax_zeroed:
+            amax_out.zero_()
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().mvnerf_layer_norm_tokens(_p(x), _p(gamma), _p(beta), x.numel() // c, c, eps, _p(out), _p(amax_out), _stream(x))
+    _lib.check(rc, 'layer_norm')
+    return out
+
+
+def attention(qkv, scale=None, out=None, amax_out=None, amax_zeroed=False):
+    """mvnerf_attention_tokens: qkv (B, n, 3, heads, d) fp32, the QKV Dense layer's output as it lies -> (B, n, heads * d) =
+    softmax(q k^T * scale) v per image and head, fp32 throughout; scale defaults to 1 / sqrt(d).  d in ATTENTION_HEAD_DIMS and
+    n <= ATTENTION_MAX_TOKENS.  amax_out: a (1,) device float that receives max |out| (zeroed here)."""
+    _chk(qkv, 'qkv', shape=(None, None, 3, None, None))
+    b, n, _, heads, d = qkv.shape
+    if qkv.numel() == 0:
+        raise ValueError(f'qkv: shape {tuple(qkv.shape)}, expected at least one token and one head')
+    if d not in ATTENTION_HEAD_DIMS:
+        raise ValueError(f'qkv: head dimension {d}, expected one of {ATTENTION_HEAD_DIMS}')
+    if n > ATTENTION_MAX_TOKENS:
+        raise ValueError(f'qkv: {n} tokens, at most {ATTENTION_MAX_TOKENS} (the logits of a query stay in registers)')
+    scale = float(d) ** -0.5 if scale is None else float(scale)
+    if not np.isfinite(scale):
+        raise ValueError(f'scale: {scale}, expected a finite number')
+    if out is None:
+        out = torch.empty((b, n, heads * d), dtype=torch.float32, device=qkv.device)
+    else:
+        _chk(out, 'out', shape=(b, n, heads * d))
+    if amax_out is not None:
+        _chk(amax_out, 'amax_out', shape=(1,))
+        if not amax_zeroed:
+            amax_out.zero_()
+    with torch.cuda.device(qkv.device):
+        rc = _lib.lib().mvnerf_attention_tokens(_p(qkv), b, n, heads, d, scale, _p(out), _p(amax_out), _stream(qkv))
+    _lib.check(rc, 'attention')
     return out

@@ -615,12 +615,17 @@ def main(argv=None):
     ap.add_argument('--fused-visual', action='store_true',
                     help="with --encoder v4: the 3x3 convolutions and batch-statistics normalisations of VisualFeatures as HIP passes "
                          "(LanguageFeatureProducer(fused_visual='auto'); csrc/conv3x3.hip, csrc/batchnorm.hip)")
+    ap.add_argument('--fused-vit', action='store_true',
+                    help="with --encoder v4: the transformer blocks of the ViT of VisualFeatures as HIP passes "
+                         "(LanguageFeatureProducer(fused_vit='auto'); csrc/token_linear.hip, csrc/attention.hip)")
     ap.add_argument('--host-batches', action='store_true', help='assemble batches in NumPy on the host (default: on the GPU)')
     args = ap.parse_args(argv)
     if args.fused_conv and args.encoder != 'v4':
         ap.error('--fused-conv needs --encoder v4')
     if args.fused_visual and args.encoder != 'v4':
         ap.error('--fused-visual needs --encoder v4')
+    if args.fused_vit and args.encoder != 'v4':
+        ap.error('--fused-vit needs --encoder v4')
     height, width = _size(args.size)
     bounds = DEFAULT_WORKSPACE_BOUNDS
     dev = 'cuda:0'
@@ -630,7 +635,8 @@ def main(argv=None):
     if with_tokens:
         from .encoders import LanguageFeatureProducer
         producer = LanguageFeatureProducer((height, width), fused_conv='auto' if args.fused_conv else False,
-                                           fused_visual='auto' if args.fused_visual else False).to(dev)
+                                           fused_visual='auto' if args.fused_visual else False,
+                                           fused_vit='auto' if args.fused_vit else False).to(dev)
         train, valid = (EncodedLanguageDataset(d, producer, None if args.host_batches else dev) for d in (train, valid))
     generator = LanguageDataGenerator(train, bounds, n_views=args.n_views, batch_size=args.batch_size,
                                       pose_augmentation_factor=args.pose_augmentation_factor, n_future_poses=args.n_future_poses,
