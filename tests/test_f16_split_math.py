@@ -6,24 +6,9 @@ restated in NumPy and checked on the CPU: an fp32 operand as two fp16 pieces, a 
 The GPU tests (tests/test_gpu_split.py) measure the kernels themselves; this file pins the claims made about the representation."""
 import numpy as np
 
+from oracle.field_f32_ref import split_activation, split_weight           # the restatement itself; emulate_f16x3 builds on it
+
 F32, F16, F64 = np.float32, np.float16, np.float64
-
-
-def split_weight(w):
-    tw = (w * F32(64)).astype(F32)
-    a0 = tw.astype(F16)
-    r = (tw - a0.astype(F32)).astype(F32)
-    a1 = r.astype(F16)
-    a0s = (a0.astype(F32) * F32(1 / 64)).astype(F16)
-    return a0, a0s, a1, r, tw
-
-
-def split_activation(v):
-    tv = (v * F32(1 / 64)).astype(F32)
-    b0 = tv.astype(F16)
-    r64 = (v - F32(64) * b0.astype(F32)).astype(F32)           # what v_fma_mix_f32(B0, -64, v) returns
-    b1 = r64.astype(F16)
-    return b0, b1, r64, tv
 
 
 def test_remainders_are_exact_in_fp32():

@@ -30,7 +30,12 @@
 //                  tests/test_f16_split_math.py); the one dropped cross term (tw - A0)(tv - B0) is <= 2^-22 |w v| (2^-25 typical).  The
 //                  activation's remainder is scaled by 64 (and meets A0 / 64): its pieces keep all 11 bits for |v| >= 1/4, the weights'
 //                  unscaled remainder for |w| >= 2^-8; below that they go subnormal - the MFMA honours fp16 subnormals
-//                  (scripts/f16_mfma_probe.hip) - with absolute errors <= 2^-25 |w| resp. 2^-31 |v| per product.  Measured per ResNet block against float64: at or below the fp32 MFMA kernel's error
+//                  (scripts/f16_mfma_probe.hip) - with absolute errors <= 2^-25 |w| resp. 2^-31 |v| per product.  So the error is RELATIVE
+//                  (fp32 rounding level) only while the operands stay above those thresholds, i.e. down to max |activation| of about
+//                  1/4; below that a Dense output carries an ABSOLUTE floor of at most 2^-25 sum_k |W_kj| + 2^-31 sum_k |v_k|
+//                  (oracle/field_f32_ref.py f16_floor; tests/test_field_f32_ref.py; the scale sweep of DESIGN.md 4.0c), harmless for
+//                  rendering but not a relative bound.  The exact bf16 cut (MVS16_F16 = 0) keeps the relative bound at every scale.
+//                  Measured per ResNet block against float64 at the scale of real scenes: at or below the fp32 MFMA kernel's error
 //                  (tests/test_gpu_split.py).  Same stream size (three 1 KiB weight pieces per row block), two instead of three operand
 //                  pieces in registers, half the MFMAs.  Range: |w| < 1023, |v| < 4.19e6 (fp16 overflow beyond; the bf16 form has the full
 //                  fp32 range).
