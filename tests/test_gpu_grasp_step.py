@@ -196,7 +196,8 @@ def drive_with_ctypes_only(tensors, rep, p, b, v, h, w, n5, lr, decay, bounds, p
     m_t, v_t, m_r, v_r = f32(p, 3), f32(p, 3), f32(p, rd), f32(p, rd)
     counters, flags = torch.zeros((2, p), dtype=torch.int32, device=DEV), torch.zeros(2, dtype=torch.int32, device=DEV)
     need = lib.mvnerf_grasp_workspace_bytes(b, v, p, n5)
-    ws = torch.zeros(need, dtype=torch.uint8, device=DEV)
+    ws = torch.full((need // 4,), float('nan'), dtype=torch.float32, device=DEV).view(torch.uint8)      # any content: production hands in torch.empty
+    assert ws.numel() == need and ws.data_ptr() % 256 == 0
     c = _lib.GraspCall()
     for name, x in (('images', tensors['images']), ('features', tensors['features']), ('intrinsics', tensors['intrinsics']),
                     ('extrinsics_inv', tensors['extrinsics_inv']), ('packed_net', packed_net), ('split', split), ('bwd_streams', bwd),

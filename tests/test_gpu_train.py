@@ -354,7 +354,8 @@ def test_c_abi_train_step_through_ctypes_only():
         assert L.mvnerf_pack_bwd_streams(P(d[name]), P(bwd[k]), None) == 0
     need = L.mvnerf_train_workspace_bytes(batch, views, n, 64, 16, 16, 1, 0)
     assert need > 0
-    ws = u8(need)
+    ws = torch.full((need // 4,), float('nan'), dtype=torch.float32, device=DEV).view(torch.uint8)      # any content: production hands in torch.empty
+    assert ws.numel() == need and ws.data_ptr() % 256 == 0
     loss, grad = f32(1), f32(2 * 247300)
     outs_t = [f32(batch, n, 3), f32(batch, n), f32(batch, n, 3), f32(batch, n)]
     c = _lib.TrainCall()

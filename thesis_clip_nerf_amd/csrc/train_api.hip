@@ -119,14 +119,21 @@ int mvnerf_loss_and_grads(const mvnerf_train_call* c, mvnerf_stream_t stream) {
     if (want_df) MV_HIP(mvnerf::launch_zero(c->d_features, (size_t)B * V * H * W * 256 * sizeof(float), st), who);
     float* gc = c->grad;
     float* gf = c->grad + mvnerf::kNetParams;
-    MV_RC(mvnerf_composite_bwd(w.z_all, w.rgbs_f, w.d_fine, nullptr, nullptr, n_rays, 2 * S, w.d_rgbs_f, c->stop_fine_z ? nullptr : w.d_z_all,
+    // V > 1: the views of a fine sample add their shares of dL/dz with atomics, in no fixed order.  Two shares onto a zeroed word commute
+    // exactly; onto the compositing term they would not ((c + v0) + v1 != (c + v1) + v0), and the coarse gradient would differ from run to
+    // run at V = 2.  So that term waits in d_rgbs_c (4n floats, free until the coarse composite_bwd) and is added once the views are in.
+    const bool dz_apart = !c->stop_fine_z && V > 1;
+    float* const dz_composite = dz_apart ? w.d_rgbs_c : w.d_z_all;
+    MV_RC(mvnerf_composite_bwd(w.z_all, w.rgbs_f, w.d_fine, nullptr, nullptr, n_rays, 2 * S, w.d_rgbs_f, c->stop_fine_z ? nullptr : dz_composite,
                                stream));
+    if (dz_apart) MV_HIP(mvnerf::launch_zero(w.d_z_all, (size_t)n_rays * 2 * S * sizeof(float), st), who);
     MV_RC(mvnerf_field_backward_table(c->rays_o, c->rays_d, w.z_all, c->images, c->features, tab_f, w.texel_grad, c->intrinsics, c->extrinsics_inv,
                                       c->net_fine, c->bwd_streams_fine, w.stash_f, w.rgbs_f, w.d_rgbs_f, B, V, R, 2 * S, H, W, w.bwd_scratch, gf,
                                       c->stop_fine_z ? nullptr : w.d_z_all, c->d_features, stream));
     if (c->fine_grad_event) MV_HIP(hipEventRecord(static_cast<hipEvent_t>(c->fine_grad_event), st), who);
     const float* d_w = nullptr;
     if (!c->stop_fine_z) {                                                  // fine loss -> fine sample depths -> sample_pdf -> coarse weights (F12)
+        if (dz_apart) MV_HIP(mvnerf::launch_add(w.d_z_all, dz_composite, (size_t)n_rays * 2 * S, st), who);
         MV_RC(mvnerf_resample_bwd(w.z, w.weights, c->u_fine, w.rank, w.d_z_all, n_rays, S, c->q7_mode, w.d_w, stream));
         d_w = w.d_w;
     }

@@ -1079,6 +1079,18 @@ hipError_t launch_zero(void* ptr, size_t bytes, hipStream_t st) {
     return hipGetLastError();
 }
 
+__global__ void add_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = dst[i] + src[i];
+}
+
+hipError_t launch_add(float* dst, const float* src, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(add_kernel, dim3(blocks), dim3(256), 0, st, dst, src, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_readout_bwd(const float* x_tl, const float* rgbs, const float* d_rgbs, const float* wr, long n_rows,
                               long n_tiles, float* do_tl, float* g_tl, hipStream_t st, float* amax_out) {
     hipError_t e = launch_zero(do_tl, (size_t)n_tiles * 32 * 32 * sizeof(float), st);
