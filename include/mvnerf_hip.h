@@ -866,6 +866,29 @@ int mvnerf_conv3x3_nhwc_ex(const float* a, int Ca, const float* amax_a, const fl
                            int N, int h, int w, int Cout, int act, const float* mul, float* out, float* amax_out, const float* bias,
                            int act_in, float* stats, mvnerf_stream_t stream);
 
+/* ---- backward of the biased 3x3 convolution (csrc/conv3x3_bwd.hip) -------------------------------------------------------------------
+ * For y = conv3x3_same(act_in(x), W) + bias and g = dL/dy.  The data gradient needs no entry point of its own: it is
+ * mvnerf_conv3x3_nhwc of g with the pack of W'[dy,dx,co,ci] = W[2-dy,2-dx,ci,co] (Cout of the forward a multiple of 32, Cin of 64). */
+
+/* Pixels per slab of the weight gradient's reduction (whole 16 x 16 tiles, in the order [image][tile row][tile column]). */
+int mvnerf_conv3x3_wgrad_slab_pixels(void);
+
+/* Bytes of the workspace of mvnerf_conv3x3_wgrad_nhwc: one fp32 partial of dw and dbias per slab; 0 when the shape is not accepted. */
+size_t mvnerf_conv3x3_wgrad_workspace_bytes(int N, int h, int w, int Cin, int Cout);
+
+/* dw_hwio (3,3,Cin,Cout) fp32, the Keras layout: dw[dy,dx,ci,co] = sum_{n,i,j} act_in(x)[n,i+dy-1,j+dx-1,ci] * g[n,i,j,co], taps outside
+ * the image zero after the activation, images apart; dbias (Cout) or NULL: sum_{n,i,j} g[n,i,j,co].
+ * x (N,h,w,Cin), g (N,h,w,Cout): fp32 NHWC.  amax_x, amax_g: one device float each, an UPPER BOUND of |x|, |g| (as for the forward: a
+ * bound of |x| bounds |act_in(x)|).  A bound of 0 gives zeros (amax_x = 0 leaves dbias the plain sum), a non-finite bound NaN in dw and
+ * dbias.  act_in: 0 identity, 1 relu, 2 elu, applied to x as it is read.
+ * fp32 grade on the fp16 matrix pipe: g cut like a weight, act_in(x) like an activation, three products.  The pixels are summed in
+ * slabs (fp32 inside a slab, a fixed order), the slabs in a second launch in order in double, then one rounding; dbias likewise from
+ * one more small launch.  No atomics, nothing of `workspace` is read that this call did not write: two runs give the same bits.
+ * Stream-ordered, no host read.  Cin a multiple of 32, Cout a multiple of 64, act_in in 0..2: else MVNERF_E_SHAPE, before any launch.
+ * x, g, dw_hwio, dbias, workspace 16-byte aligned. */
+int mvnerf_conv3x3_wgrad_nhwc(const float* x, const float* amax_x, int act_in, const float* g, const float* amax_g, int N, int h, int w,
+                              int Cin, int Cout, float* dw_hwio, float* dbias, void* workspace, mvnerf_stream_t stream);
+
 /* Batch statistics of a convolution output from its tile partials (layers.py:23, 27: tf.keras BatchNormalization, training=True):
  * mean[c] and rstd[c] = 1 / sqrt(var[c] + eps) with the BIASED variance over all N h w pixels, c < Cout.  The tiles are combined with
  * Chan's pairwise update in double, in a fixed order.  Stream-ordered, no host read (the chain can be captured in a graph). */

@@ -189,4 +189,41 @@ MVC_HD BnMoments bn_combine_run(const float* src, int run, int N, int h, int w) 
     return acc;
 }
 
+// ---- weight gradient of the 3x3 convolution (conv3x3_bwd.hip) ---------------------------------------------------------------
+// tests/cpu_conv_bwd builds this part for the host.
+//
+//   dw[dy,dx,ci,co] = sum_{n,i,j} act_in(x)[n,i+dy-1,j+dx-1,ci] * g[n,i,j,co],   dbias[co] = sum g
+//
+//   operands    g takes the weight's cut (A0, A1, A0s under eg), act_in(x) the activation's (B0, B1 under ex): the same three products
+//   slabs       the 16 x 16 tiles - [image][tile row][tile column] - in runs of kWgradSlabTiles; a slab's sum is fp32 (each half tile of
+//               8 x 16 pixels summed by the matrix pipe, the half tiles added in order), the slabs are added in order in double
+//   finish      dw = (float)(sum * 2^-(ex + eg)), one rounding; a zero bound gives zeros, a non-finite one NaN
+constexpr int kWgradTile = 16;               // conv3x3.hip: kCvTile
+constexpr int kWgradSlabTiles = 16;          // tiles per slab
+constexpr int kWgradSlabPixels = kWgradSlabTiles * kWgradTile * kWgradTile;       // 4096: what ops.CONV3X3_WGRAD_SLAB_PIXELS reports
+
+MVC_HD long conv_wgrad_tiles(int N, int h, int w) {
+    return (long)N * ((h + kWgradTile - 1) / kWgradTile) * ((w + kWgradTile - 1) / kWgradTile);
+}
+
+MVC_HD long conv_wgrad_slabs(int N, int h, int w) { return (conv_wgrad_tiles(N, h, w) + kWgradSlabTiles - 1) / kWgradSlabTiles; }
+
+// B0, B1 of act_in(x): the activation first, as the forward stages it
+MVC_HD void conv_wgrad_cut_x(float x, int act_in, int ex, uint16_t& b0, uint16_t& b1) { conv_cut_act(conv_act_f(x, act_in), ex, b0, b1); }
+
+// A0, A1, A0s of an upstream gradient
+MVC_HD void conv_wgrad_cut_g(float g, int eg, uint16_t& a0, uint16_t& a1, uint16_t& a0s) { conv_cut_weight(g, eg, a0, a1, a0s); }
+
+// the slab total of one weight -> the gradient.  amax_x, amax_g as the launch read them.
+MVC_HD float conv_wgrad_finish(double sum, float amax_x, float amax_g) {
+    if (!conv_amax_finite(amax_x) || !conv_amax_finite(amax_g)) return conv_bits_f32(0x7fc00000u);
+    if (amax_x == 0.0f || amax_g == 0.0f) return 0.0f;
+    return (float)ldexp(sum, -(conv_scale_exp(amax_x) + conv_scale_exp(amax_g)));
+}
+
+MVC_HD float conv_dbias_finish(double sum, float amax_x, float amax_g) {
+    if (!conv_amax_finite(amax_x) || !conv_amax_finite(amax_g)) return conv_bits_f32(0x7fc00000u);
+    return amax_g == 0.0f ? 0.0f : (float)sum;
+}
+
 }  // namespace mvnerf

@@ -56,19 +56,29 @@ def _check_switch(value, name='fused_conv'):
     return value
 
 
+def _check_bool(value, name='fused_backward'):
+    if not (value is True or value is False):
+        raise ValueError(f'{name}: {value!r}, expected True or False')
+    return value
+
+
 class Block(nn.Module):
     """layers.py:7-33.  One BatchNormalization serves both convolutions (the attribute is assigned twice in the reference)
     and it always normalises with batch statistics (`training=True` is hard-coded there).
     fused_conv (default False: torch): each convolution as ops.conv3x3 (bias, tile statistics) -> ops.bn_finalize -> ops.bn_apply
-    (skip, relu) under the rule of :func:`_wants_fused`, see :func:`conv3x3_bn`; the downsample branch stays torch."""
+    (skip, relu) under the rule of :func:`_wants_fused`, see :func:`conv3x3_bn`; the downsample branch stays torch.
+    fused_backward (default False): where a call under `fused_conv` needs a gradient, the convolutions run as the differentiable HIP
+    pass (:class:`Conv3x3BiasFunction`) and the normalisation, skip and relu as torch, instead of torch all over ('auto') or the
+    "no backward" error (True)."""
 
-    def __init__(self, c_in, n_features, downsample=None, fused_conv=False):
+    def __init__(self, c_in, n_features, downsample=None, fused_conv=False, fused_backward=False):
         super().__init__()
         self.conv_1 = SameConv2d(c_in, n_features, 3)
         self.conv_2 = SameConv2d(n_features, n_features, 3)
         self.norm_1 = _keras_bn(n_features)
         self.downsample = downsample
         self.fused_conv = fused_conv
+        self.fused_backward = fused_backward
 
     @property
     def fused_conv(self):
@@ -78,14 +88,22 @@ class Block(nn.Module):
     def fused_conv(self, value):
         self._fused_conv = _check_switch(value)
 
+    @property
+    def fused_backward(self):
+        return self._fused_backward
+
+    @fused_backward.setter
+    def fused_backward(self, value):
+        self._fused_backward = _check_bool(value)
+
     def _norm(self, x):
         return F.batch_norm(x, None, None, self.norm_1.weight, self.norm_1.bias, True, 0.0, self.norm_1.eps)
 
     def run(self, x, amax=None):
         """-> (out, amax | None): amax bounds |x| (a device float, or None), the returned one is max |out| when conv_2 ran fused."""
         skip = x if self.downsample is None else self.downsample(x)
-        out, amax = conv3x3_bn(self.conv_1, self.norm_1, x, None, self.fused_conv, amax)
-        return conv3x3_bn(self.conv_2, self.norm_1, out, skip, self.fused_conv, amax)
+        out, amax = conv3x3_bn(self.conv_1, self.norm_1, x, None, self.fused_conv, amax, self.fused_backward)
+        return conv3x3_bn(self.conv_2, self.norm_1, out, skip, self.fused_conv, amax, self.fused_backward)
 
     def forward(self, x):
         if self.fused_conv is False:
@@ -98,15 +116,17 @@ class Block(nn.Module):
 
 class ConvolutionalEncoder(nn.Module):
     """layers.py:36-57: 7x7/2 conv -> BN -> ReLU -> 3 residual blocks of n_features / 2 channels; (H, W) -> (H/2, W/2).
-    fused_conv (default False): handed to the three blocks, every apply's amax_out the next convolution's amax; the stem stays torch."""
+    fused_conv (default False): handed to the three blocks, every apply's amax_out the next convolution's amax; the stem stays torch.
+    fused_backward (default False): handed to the three blocks too."""
 
-    def __init__(self, n_features=256, stem=64, fused_conv=False):
+    def __init__(self, n_features=256, stem=64, fused_conv=False, fused_backward=False):
         super().__init__()
         half = n_features // 2
         downsample = nn.Sequential(SameConv2d(stem, half, 1, bias=False), _keras_bn(half))
         self.conv_features = nn.Sequential(SameConv2d(3, stem, 7, stride=2, bias=False), _keras_bn(stem), nn.ReLU(),
                                            Block(stem, half, downsample), Block(half, half), Block(half, half))
         self.fused_conv = fused_conv
+        self.fused_backward = fused_backward
 
     @property
     def fused_conv(self):
@@ -117,6 +137,16 @@ class ConvolutionalEncoder(nn.Module):
         self._fused_conv = _check_switch(value)
         for block in self.conv_features[3:]:
             block.fused_conv = value
+
+    @property
+    def fused_backward(self):
+        return self._fused_backward
+
+    @fused_backward.setter
+    def fused_backward(self, value):
+        self._fused_backward = _check_bool(value)
+        for block in self.conv_features[3:]:
+            block.fused_backward = value
 
     def forward(self, x):
         if self.fused_conv is False:
@@ -242,12 +272,15 @@ class VisionTransformerEncoder(nn.Module):
     act_in = relu and their bias, and each `conv_decode` whose channel counts the kernel takes (multiples of 32 -> 64; at the reference's
     sizes all but the first, 48 -> 256) as a plain ops.conv3x3 - under 'auto' only where the launch is large enough to beat the torch
     path (:func:`conv3x3_auto_pays`); the others and the post-processing stay torch.
-    fused_vit (default False), a switch of its own: the transformer blocks of the ViT as HIP launches (:class:`TransformerBlock`)."""
+    fused_vit (default False), a switch of its own: the transformer blocks of the ViT as HIP launches (:class:`TransformerBlock`).
+    fused_backward (default False): where a call under `fused_conv` needs a gradient, the same convolutions as the differentiable HIP
+    pass (:class:`Conv3x3BiasFunction`; `conv_decode` under 'auto' keeps its workgroup rule)."""
 
     def __init__(self, img_size=(224, 224), patch_size=16, embed_dim=768, n_features=256, mlp_ratio=4, hooks=(3, 6, 9, 12),
-                 features=(48, 96, 192, 384), num_heads=12, fused_conv=False, fused_vit=False):
+                 features=(48, 96, 192, 384), num_heads=12, fused_conv=False, fused_vit=False, fused_backward=False):
         super().__init__()
         self.fused_conv = fused_conv
+        self.fused_backward = fused_backward
         self.vit = VisionTransformer(img_size, patch_size, embed_dim, mlp_ratio, hooks, num_heads, fused_vit)
         f = features
 
@@ -273,6 +306,14 @@ class VisionTransformerEncoder(nn.Module):
         self._fused_conv = _check_switch(value)
 
     @property
+    def fused_backward(self):
+        return self._fused_backward
+
+    @fused_backward.setter
+    def fused_backward(self, value):
+        self._fused_backward = _check_bool(value)
+
+    @property
     def fused_vit(self):
         return self.vit.fused_vit
 
@@ -293,26 +334,32 @@ class VisionTransformerEncoder(nn.Module):
             # (True is about gradients and devices, not channel counts; 'auto' also leaves launches too small to pay to torch)
             takes = conv3x3_fusable(dec, t.shape[1]) and (self.fused_conv is True or conv3x3_auto_pays(t.shape[0], *t.shape[2:], dec.out_channels))
             switch = self.fused_conv if takes else False
-            maps.append(_up(conv3x3_act(dec, t, None, None, switch)[0], s))
+            if switch is not False and _wants_fused_backward(switch, self.fused_backward, dec.weight, t):
+                maps.append(_up(conv3x3_bias(dec, t, None, switch, None, True)[0], s))
+            else:
+                maps.append(_up(conv3x3_act(dec, t, None, None, switch)[0], s))
         conv_a, conv_b = self.output_conv[1], self.output_conv[3]
-        x, amax = conv3x3_bias(conv_a, torch.cat(maps, 1), 'relu', self.fused_conv)
-        return conv3x3_bias(conv_b, x, 'relu', self.fused_conv, amax)[0]
+        x, amax = conv3x3_bias(conv_a, torch.cat(maps, 1), 'relu', self.fused_conv, None, self.fused_backward)
+        return conv3x3_bias(conv_b, x, 'relu', self.fused_conv, amax, self.fused_backward)[0]
 
 
 class VisualFeatures(nn.Module):
     """layers.py:232-259: images (N, H, W, 3) in [0, 1] -> (N, H/2, W/2, n_features) = [ViT latents resized | conv features].
     fused_conv: False (default) | True | 'auto' - handed to both encoders: their stride-1 3x3 convolutions and the batch-statistics
-    normalisation behind the blocks' as HIP passes when on the GPU and nothing needs a gradient (inference only, no backward).
-    fused_vit: False (default) | True | 'auto' - the ViT's transformer blocks as HIP passes, eval mode only (:class:`TransformerBlock`)."""
+    normalisation behind the blocks' as HIP passes when on the GPU and nothing needs a gradient (inference only; see `fused_backward`).
+    fused_vit: False (default) | True | 'auto' - the ViT's transformer blocks as HIP passes, eval mode only (:class:`TransformerBlock`).
+    fused_backward: False (default) | True - handed to both encoders: with it the stride-1 3x3 convolutions under `fused_conv` stay HIP
+    passes where a gradient is needed (training through train_nerf), forward and backward (:class:`Conv3x3BiasFunction`)."""
 
     def __init__(self, n_features=256, original_image_size=(480, 640), transformer_image_size=(224, 224), fused_conv=False, fused_vit=False,
-                 **vit_kw):
+                 fused_backward=False, **vit_kw):
         super().__init__()
         self.conv_features = ConvolutionalEncoder(n_features)
         self.vision_transformer = VisionTransformerEncoder(img_size=transformer_image_size, n_features=n_features, fused_vit=fused_vit, **vit_kw)
         self.transformer_image_size = tuple(transformer_image_size)
         self.half_size = (original_image_size[0] // 2, original_image_size[1] // 2)
         self.fused_conv = fused_conv
+        self.fused_backward = fused_backward
 
     @property
     def fused_conv(self):
@@ -323,6 +370,16 @@ class VisualFeatures(nn.Module):
         self._fused_conv = _check_switch(value)
         self.conv_features.fused_conv = value
         self.vision_transformer.fused_conv = value
+
+    @property
+    def fused_backward(self):
+        return self._fused_backward
+
+    @fused_backward.setter
+    def fused_backward(self, value):
+        self._fused_backward = _check_bool(value)
+        self.conv_features.fused_backward = value
+        self.vision_transformer.fused_backward = value
 
     @property
     def fused_vit(self):
@@ -359,6 +416,7 @@ def _mark_loaded(module):
     """A loader wrote `.data` (which does not bump the parameter version the packed caches key on): count it and drop the module's cache."""
     module.__dict__['_mvnerf_loads'] = module.__dict__.get('_mvnerf_loads', 0) + 1
     module.__dict__.pop('_mvnerf_packed', None)
+    module.__dict__.pop('_mvnerf_packed_t', None)
 
 
 def _cached(module, key, make):
@@ -631,9 +689,105 @@ def _nhwc(t):
     return None if t is None else t.detach().permute(0, 2, 3, 1).contiguous()      # free when the storage is channels-last already
 
 
-def conv3x3_bias(conv, x, act_in=None, fused_conv=False, amax=None):
+def _packed_conv3x3_t(conv):
+    """The packed stream of the data gradient's kernel (ops.conv3x3_pack_transposed: `conv.weight` flipped and transposed), cached next
+    to :func:`_packed_conv3x3` per parameter version and per load."""
+    from . import ops
+    weight = conv.weight
+    key = (weight._version, weight.data_ptr(), weight.device, conv.__dict__.get('_mvnerf_loads', 0))
+    cached = conv.__dict__.get('_mvnerf_packed_t')
+    if cached is None or cached[0] != key:
+        cached = (key, ops.conv3x3_pack_transposed(weight.detach().permute(2, 3, 1, 0).contiguous()))
+        conv.__dict__['_mvnerf_packed_t'] = cached
+    return cached[1]
+
+
+def conv3x3_dgrad_fusable(conv):
+    """Whether the data gradient of `conv` is one ops.conv3x3 launch on the transposed pack: its channel counts swap roles, so next to
+    the forward's rule the outputs must come in multiples of 32 and the inputs in multiples of 64."""
+    return conv.out_channels % 32 == 0 and conv.in_channels % 64 == 0
+
+
+class Conv3x3BiasFunction(torch.autograd.Function):
+    """`conv(act_in(x))` of NCHW x with a 3x3, stride-1 `conv` (bias or none) as HIP passes in both directions.
+    forward: the fused launch of :func:`conv3x3_bias`; saves x (NHWC) and its amax.  backward, for g = dL/dout:
+      dw, dbias   ops.conv3x3_wgrad of (x, g) with act_in applied as x is staged;
+      dx          ops.conv3x3 of g with the flipped, transposed pack (torch.nn.grad.conv2d_input where the channel counts do not fit:
+                  :func:`conv3x3_dgrad_fusable`), times act_in'(x) in torch; skipped when x needs no gradient.
+    Returns (out NCHW view of NHWC storage, max |out| as a device float)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, conv, act_in, amax):
+        from . import ops
+        xn = _nhwc(x)
+        if amax is None:
+            amax = ops.absmax(xn)
+        top = torch.empty(1, dtype=torch.float32, device=x.device)
+        out = ops.conv3x3(xn, None, _packed_conv3x3(conv), conv.out_channels, 0, amax_a=amax, amax_out=top,
+                          bias=None if bias is None else bias.detach(), act_in=_ACT_CODES[act_in])
+        ctx.save_for_backward(xn, amax, weight)
+        ctx.conv, ctx.act_in, ctx.has_bias = conv, act_in, bias is not None
+        out = out.permute(0, 3, 1, 2)
+        ctx.mark_non_differentiable(top)
+        return out, top
+
+    @staticmethod
+    def backward(ctx, g, _g_top):
+        from . import ops
+        xn, amax, weight = ctx.saved_tensors
+        conv, act_in = ctx.conv, ctx.act_in
+        gn = _nhwc(g)
+        amax_g = ops.absmax(gn)
+        dx = dw = dbias = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            got = ops.conv3x3_wgrad(xn, gn, _ACT_CODES[act_in], amax_x=amax, amax_g=amax_g, want_bias=ctx.has_bias)
+            dw, dbias = got if ctx.has_bias else (got, None)
+            dw = dw.permute(3, 2, 0, 1)                              # HWIO -> OIHW
+        if ctx.needs_input_grad[0]:
+            if conv3x3_dgrad_fusable(conv):
+                dx = ops.conv3x3(gn, None, _packed_conv3x3_t(conv), conv.in_channels, 0, amax_a=amax_g).permute(0, 3, 1, 2)
+            else:
+                dx = torch.nn.grad.conv2d_input((xn.shape[0], xn.shape[3], xn.shape[1], xn.shape[2]), weight.detach(), g, padding=1)
+            dx = conv3x3_act_grad(dx, xn.permute(0, 3, 1, 2), act_in)
+        return dx, dw, dbias, None, None, None
+
+
+def conv3x3_act_grad(dx, x, act_in):
+    """dx * act_in'(x): relu' = x > 0, elu' = x > 0 ? 1 : exp(x) - an elementwise torch pass on the saved x."""
+    if act_in is None:
+        return dx
+    if act_in == 'relu':
+        return dx * (x > 0)
+    return dx * torch.where(x > 0, torch.ones_like(x), torch.exp(x))
+
+
+def _wants_fused_backward(fused_conv, fused_backward, *tensors):
+    """The case `fused_backward` is about: a switch that is on (True | 'auto'), everything on the GPU, and a gradient needed - where
+    :func:`_wants_fused` says torch ('auto') or raises (True)."""
+    if fused_conv is False or not fused_backward:
+        return False
+    tensors = [t for t in tensors if t is not None]
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors) and all(t.is_cuda for t in tensors)
+
+
+def _conv3x3_train(conv, x, act_in, fused_conv, amax):
+    """The differentiable HIP convolution of a call that needs a gradient -> (out, amax), or None where the kernel does not take the
+    convolution under 'auto' (ValueError under True, as in :func:`_fused_or_torch`)."""
+    if not conv3x3_fusable(conv, x.shape[1], bias=True):
+        if fused_conv is True:
+            raise ValueError(f'fused_conv=True: a {tuple(conv.kernel_size)} convolution over {x.shape[1]} -> {conv.out_channels} channels is not '
+                             f"one the HIP pass takes (3x3, stride 1, multiples of 32 -> 64); use 'auto'")
+        return None
+    return Conv3x3BiasFunction.apply(x, conv.weight, conv.bias, conv, act_in, amax)
+
+
+def conv3x3_bias(conv, x, act_in=None, fused_conv=False, amax=None, fused_backward=False):
     """`conv(act_in(x))` of NCHW x with a biased 3x3 `conv` -> (out, amax | None): through torch unless `fused_conv` selects ops.conv3x3
-    with bias and act_in (zero padding after the activation, as torch pads the activated map).  amax bounds |x|; |act_in(x)| <= |x|."""
+    with bias and act_in (zero padding after the activation, as torch pads the activated map).  amax bounds |x|; |act_in(x)| <= |x|.
+    fused_backward: where the call needs a gradient, :class:`Conv3x3BiasFunction` instead of torch / the "no backward" error."""
+    if _wants_fused_backward(fused_conv, fused_backward, conv.weight, conv.bias, x):
+        got = _conv3x3_train(conv, x, act_in, fused_conv, amax)
+        return got if got is not None else (conv(_ACT_FNS[act_in](x)), None)
     if not _fused_or_torch(fused_conv, conv, x.shape[1], x):
         return conv(_ACT_FNS[act_in](x)), None
     from . import ops
@@ -643,10 +797,17 @@ def conv3x3_bias(conv, x, act_in=None, fused_conv=False, amax=None):
     return out.permute(0, 3, 1, 2), top
 
 
-def conv3x3_bn(conv, norm, x, skip=None, fused_conv=False, amax=None):
+def conv3x3_bn(conv, norm, x, skip=None, fused_conv=False, amax=None, fused_backward=False):
     """`relu(batch_norm(conv(x)) (+ skip))` of NCHW x with a biased 3x3 `conv` and the batch statistics of its own output (gamma, beta,
     eps of `norm`; layers.py:22-33) -> (out, amax | None).  Through torch unless `fused_conv` selects the three HIP passes: ops.conv3x3
-    with the bias and the per-tile statistics, ops.bn_finalize, ops.bn_apply in place with the skip, the relu and max |out|."""
+    with the bias and the per-tile statistics, ops.bn_finalize, ops.bn_apply in place with the skip, the relu and max |out|.
+    fused_backward: where the call needs a gradient, the convolution is :class:`Conv3x3BiasFunction` (no statistics) and the
+    normalisation, skip and relu are torch; no apply supplies max |out| then, so the next convolution measures its own input."""
+    if _wants_fused_backward(fused_conv, fused_backward, conv.weight, conv.bias, x, skip, norm.weight, norm.bias):
+        got = _conv3x3_train(conv, x, None, fused_conv, amax)
+        y = got[0] if got is not None else conv(x)
+        out = F.batch_norm(y, None, None, norm.weight, norm.bias, True, 0.0, norm.eps)
+        return F.relu(out if skip is None else out + skip), None
     if not _fused_or_torch(fused_conv, conv, x.shape[1], x, skip, norm.weight, norm.bias):
         out = F.batch_norm(conv(x), None, None, norm.weight, norm.bias, True, 0.0, norm.eps)
         return F.relu(out if skip is None else out + skip), None
@@ -1006,6 +1167,7 @@ def load_conv(conv, kernel_hwio, bias=None):
     """Keras Conv2D kernel (kh, kw, in, out) -> torch (out, in, kh, kw)."""
     conv.weight.data.copy_(_t(kernel_hwio).permute(3, 2, 0, 1))
     conv.__dict__.pop('_mvnerf_packed', None)            # (`.data` does not bump the parameter version the packed-stream cache keys on)
+    conv.__dict__.pop('_mvnerf_packed_t', None)
     if bias is not None:
         conv.bias.data.copy_(_t(bias))
 

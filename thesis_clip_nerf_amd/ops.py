@@ -1753,6 +1753,80 @@ def conv3x3_stats_bytes(n, h, w, cout):
     return nbytes
 
 
+# ---- backward of the biased 3x3 convolution (csrc/conv3x3_bwd.hip) ---------------------------------------------------------
+CONV3X3_WGRAD_SLAB_PIXELS = 4096       # mvnerf_conv3x3_wgrad_slab_pixels(): 16 tiles of 16 x 16 pixels per slab of the reduction
+
+
+def conv3x3_pack_transposed(w_hwio, out=None):
+    """The packed stream of the data gradient's kernel W'[dy,dx,co,ci] = W[2-dy,2-dx,ci,co] of w_hwio (3,3,cin,cout): flipped and
+    transposed on the device, then :func:`conv3x3_pack`.  `conv3x3(g, None, packed, cin, 0)` is then dL/d(act_in(x)) of
+    y = conv3x3_same(act_in(x), W).  Needs cout a multiple of 32 and cin a multiple of 64 (ValueError otherwise)."""
+    _chk(w_hwio, 'w_hwio', shape=(3, 3, None, None))
+    return conv3x3_pack(w_hwio.flip(0, 1).transpose(2, 3).contiguous(), out=out)
+
+
+def conv3x3_wgrad_workspace_bytes(n, h, w, cin, cout):
+    """Bytes of the workspace of :func:`conv3x3_wgrad` (mvnerf_conv3x3_wgrad_workspace_bytes; ValueError for a shape it does not take)."""
+    nbytes = _lib.lib().mvnerf_conv3x3_wgrad_workspace_bytes(int(n), int(h), int(w), int(cin), int(cout))
+    if nbytes == 0:
+        raise ValueError(f'conv3x3_wgrad: n={n} h={h} w={w} cin={cin} cout={cout} (positive sizes, cin a multiple of 32, cout a multiple of 64)')
+    return nbytes
+
+
+def conv3x3_wgrad(x, g, act_in=None, amax_x=None, amax_g=None, want_bias=False, workspace=None, out=None):
+    """mvnerf_conv3x3_wgrad_nhwc: dw (3,3,cin,cout) HWIO = sum over the pixels of act_in(x) shifted by the tap times g, for
+    y = conv3x3_same(act_in(x), W) + bias and g = dL/dy; with want_bias also dbias (cout,) = sum g, and the return value is (dw, dbias).
+    x (N,h,w,cin), g (N,h,w,cout): fp32 NHWC.  act_in: None | 0 | 'identity', 1 | 'relu', 2 | 'elu'.  amax_x / amax_g: device floats (1,)
+    bounding |x| / |g| (computed with :func:`absmax` when missing).  workspace: a uint8 tensor of at least
+    :func:`conv3x3_wgrad_workspace_bytes` bytes, 16-byte aligned (allocated when missing); out: dw, or (dw, dbias) with want_bias."""
+    _chk(x, 'x', shape=(None, None, None, None))
+    n, h, w, cin = x.shape
+    _chk(g, 'g', shape=(n, h, w, None))
+    cout = g.shape[3]
+    if act_in is not None and not isinstance(act_in, int):
+        if act_in not in FUSE_ACTIVATIONS:
+            raise ValueError(f'act_in: {act_in!r}, expected one of {list(FUSE_ACTIVATIONS)} or 0, 1, 2')
+        act_in = FUSE_ACTIVATIONS[act_in]
+    act_in = int(act_in or 0)
+    if not 0 <= act_in <= 2:
+        raise ValueError(f'act_in: {act_in}, expected 0, 1 or 2')
+    nbytes = conv3x3_wgrad_workspace_bytes(n, h, w, cin, cout)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    else:
+        _chk(workspace, 'workspace', dtype=torch.uint8, shape=(None,))
+        if workspace.numel() < nbytes:
+            raise ValueError(f'workspace: {workspace.numel()} bytes, expected at least {nbytes}')
+        if workspace.data_ptr() % 16:
+            raise ValueError('workspace: must be 16-byte aligned')
+    dw, dbias = (out if want_bias else (out, None)) if out is not None else (None, None)
+    if dw is None:
+        dw = torch.empty((3, 3, cin, cout), dtype=torch.float32, device=x.device)
+    else:
+        _chk(dw, 'out (dw)', shape=(3, 3, cin, cout))
+    if want_bias:
+        if dbias is None:
+            dbias = torch.empty(cout, dtype=torch.float32, device=x.device)
+        else:
+            _chk(dbias, 'out (dbias)', shape=(cout,))
+    for t, name in ((dw, 'out (dw)'), (dbias, 'out (dbias)'), (x, 'x'), (g, 'g')):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f'{name}: must be 16-byte aligned')
+    if amax_x is None:
+        amax_x = absmax(x)
+    else:
+        _chk(amax_x, 'amax_x', shape=(1,))
+    if amax_g is None:
+        amax_g = absmax(g)
+    else:
+        _chk(amax_g, 'amax_g', shape=(1,))
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().mvnerf_conv3x3_wgrad_nhwc(_p(x), _p(amax_x), act_in, _p(g), _p(amax_g), n, h, w, cin, cout, _p(dw), _p(dbias),
+                                                  _p(workspace), _stream(x))
+    _lib.check(rc, 'conv3x3_wgrad')
+    return (dw, dbias) if want_bias else dw
+
+
 def bn_finalize(stats, n, h, w, cout, eps=1e-3, out=None):
     """mvnerf_bn_finalize: the tile statistics of :func:`conv3x3` over an (n,h,w,cout) output -> (mean, rstd), each (cout,), rstd =
     1 / sqrt(biased variance + eps) over all n h w pixels.  out: a (2, cout) tensor to write them into.  No host read."""
