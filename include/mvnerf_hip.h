@@ -706,6 +706,35 @@ size_t mvnerf_language_grad_floats(int n5);
 size_t mvnerf_language_workspace_bytes(int B, int V, int H, int W, int np, int n5);
 int mvnerf_language_loss_and_grads(const mvnerf_language_call* call, mvnerf_stream_t stream);
 
+/* ---- the optimiser of that step (src/train_language.py:65-67: tf.keras.optimizers.Adam, behind optimize() = clip-by-value then Adam,
+ * nerf_utils.py:8-12) and the whole step behind one call.  The update is mvnerf_adam_clip's, operation for operation:
+ *     g = clip(g);  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;  p = p - lr_t m / (sqrt(v) + eps)
+ * with lr_t = (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)) formed ON THE DEVICE in double from t = *step + 1 (beta^t by square-and-
+ * multiply), so that a captured graph needs no host-side rate.  The variables are the 21 tensors the model owns, updated in place where
+ * they are; m, v have the flat layout of `grads` above.  Nothing is allocated, nothing synchronises with the host, no atomics. */
+typedef struct mvnerf_language_adam {
+    float* head_w[4];             /* activation_downscale 0..3 weights (64, 128): the variables themselves */
+    float* head_b[4];             /* their biases (64) */
+    float* head_wc;               /* combined_activation_downscale (64, 256) = mvnerf_language_call.head_wc */
+    float* head_bc;               /* (64) */
+    float* tail_w[11];            /* the pointers and the order of mvnerf_language_call.tail_w */
+    float* head_w4;               /* (4, 64, 128) the stacked image mvnerf_language_call.head_w4 reads: written from head_w[] */
+    float* head_b4;               /* (4, 64) likewise from head_b[] */
+    float* m;                     /* mvnerf_language_grad_floats(n5) first moments, the layout of `grads` */
+    float* v;                     /* second moments */
+    long long* step;              /* one device word, 8-byte aligned: the number of completed updates; read and advanced on the device */
+    float lr, beta1, beta2, eps;  /* Keras: lr, 0.9, 0.999, 1e-7; lr is NOT bias-corrected */
+    float clip;                   /* clip-by-value bound of optimize(), <= 0: none */
+} mvnerf_language_adam;
+/* One update from call->grads (only grads and n5 of `call` are read): a launch over the flat index space that clips, updates m, v and the
+ * variable an index belongs to and mirrors an updated head_w[] / head_b[] element into head_w4 / head_b4, then a one-thread launch that
+ * makes *step one larger - stream-ordered behind every read of it. */
+int mvnerf_language_apply_gradients(const mvnerf_language_call* call, const mvnerf_language_adam* adam, mvnerf_stream_t stream);
+/* LanguageNeRF.train_step on one device: head_w[] / head_b[] gathered into head_w4 / head_b4 (so a caller that rewrote the variables in
+ * place needs no invalidation call), mvnerf_language_loss_and_grads, mvnerf_language_apply_gradients.  The 15 weight pointers of `adam`
+ * must be those of `call`. */
+int mvnerf_language_train_step(const mvnerf_language_call* call, const mvnerf_language_adam* adam, mvnerf_stream_t stream);
+
 /* ---- the whole training step behind one call (MVVNeRFRenderer.train_step, model_v0.py:186-197: GradientTape over call(),
  * loss = MSE(y, rgb) + MSE(y, fine_rgb) :193, gradients :194, optimize() :195 = nerf_utils.py:8-12) ----
  * The matching `_bwd` of mvnerf_render_fwd: a host in any language takes a training step with these entry points and

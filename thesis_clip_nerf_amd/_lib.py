@@ -66,6 +66,13 @@ class LanguageCall(ctypes.Structure):
                 [('workspace_bytes', c_size_t)])
 
 
+class LanguageAdam(ctypes.Structure):
+    """mvnerf_language_adam (include/mvnerf_hip.h): the read-out's variables, moments, device step counter and Keras Adam constants."""
+    _fields_ = ([('head_w', c_void_p * 4), ('head_b', c_void_p * 4), ('head_wc', c_void_p), ('head_bc', c_void_p), ('tail_w', c_void_p * 11)] +
+                [(n, c_void_p) for n in ('head_w4', 'head_b4', 'm', 'v', 'step')] +
+                [(n, c_float) for n in ('lr', 'beta1', 'beta2', 'eps', 'clip')])
+
+
 class GemmTnBatch(ctypes.Structure):
     """mvnerf_gemm_tn_batch (include/mvnerf_hip.h)."""
     _fields_ = ([(n, c_void_p) for n in ('g', 'a', 'g2', 'a2')] +
@@ -166,6 +173,8 @@ SIGNATURES = {
     'mvnerf_language_grad_floats': (c_size_t, [c_int]),
     'mvnerf_language_workspace_bytes': (c_size_t, [c_int] * 6),
     'mvnerf_language_loss_and_grads': (c_int, [ctypes.POINTER(LanguageCall), c_void_p]),
+    'mvnerf_language_apply_gradients': (c_int, [ctypes.POINTER(LanguageCall), ctypes.POINTER(LanguageAdam), c_void_p]),
+    'mvnerf_language_train_step': (c_int, [ctypes.POINTER(LanguageCall), ctypes.POINTER(LanguageAdam), c_void_p]),
     'mvnerf_pose_adam_step': (c_int, [ctypes.POINTER(PoseAdamConfig), c_int, c_int] + [c_void_p] * 11),
     'mvnerf_grasp_workspace_bytes': (c_size_t, [c_int] * 4),
     'mvnerf_grasp_success': (c_int, [ctypes.POINTER(GraspCall), c_void_p]),

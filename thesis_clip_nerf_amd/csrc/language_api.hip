@@ -19,6 +19,7 @@
 // synchronisation, no global state, no atomics of its own (mvnerf_query_vjp's view sum for V > 1 is the one unordered sum of the step).
 #include <hip/hip_runtime.h>
 
+#include "mvnerf_adam.h"
 #include "mvnerf_api.h"
 
 namespace {
@@ -33,16 +34,12 @@ struct GradLayout {
     long w4, b4, wc, bc, w0, b0, w1, b1, ws, w0b, w1b, b0b, b1b, w_out, b_out, total;
 };
 
+// from the one table of the layout (mvnerf_adam.h, which the optimiser's segment map reads too): the fields above are its entries in order
 GradLayout grad_layout(int n5) {
-    const long K = 64L * n5;
-    GradLayout g;
-    long at = 0;
-    auto take = [&](long n) { const long o = at; at += n; return o; };
-    g.w4 = take(4 * 64 * 128); g.b4 = take(4 * 64); g.wc = take(64 * 256); g.bc = take(64);
-    g.w0 = take(128 * K); g.b0 = take(128); g.w1 = take(64 * 128); g.b1 = take(64); g.ws = take(64 * K);
-    g.w0b = take(64 * 64); g.w1b = take(64 * 64); g.b0b = take(64); g.b1b = take(64); g.w_out = take(64); g.b_out = take(1);
-    g.total = at;
-    return g;
+    static_assert(sizeof(GradLayout) == (mvnerf::adam::kFlatEntries + 1) * sizeof(long), "GradLayout lists the entries of adam::kFlat");
+    long at[mvnerf::adam::kFlatEntries + 1];
+    mvnerf::adam::flat_offsets(n5, at);
+    return {at[0], at[1], at[2], at[3], at[4], at[5], at[6], at[7], at[8], at[9], at[10], at[11], at[12], at[13], at[14], at[15]};
 }
 
 struct LangWs {
@@ -371,6 +368,12 @@ struct Step {
 };
 
 }  // namespace
+
+// for mvnerf_language_train_step (language_opt.hip): the checks of mvnerf_language_loss_and_grads before its own first launch
+int mvnerf::language_validate(const mvnerf_language_call* call) {
+    LangWs w;
+    return validate(call, &w);
+}
 
 extern "C" {
 

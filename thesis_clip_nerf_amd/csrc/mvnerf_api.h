@@ -75,4 +75,8 @@ inline int pose_rows_trunk(const float* points, const float* dirs, const float* 
     return mvnerf_stash_fused_acts(stash, B, V, (int)ld, acts, stream);
 }
 
+// ---- the LanguageNeRF step and its optimiser (language_api.hip, language_opt.hip) ----------------------------------------------------
+// every check of mvnerf_language_loss_and_grads on its struct, without a launch: 0 or its return code with the message set
+int language_validate(const mvnerf_language_call* call);
+
 }  // namespace mvnerf

@@ -34,14 +34,19 @@ COMPUTE_DTYPES = ('f32', 'bf16')
 class TrunkState:
     """Everything the trunk needs besides the query points: source views, cameras, packed weights."""
 
-    def __init__(self, images, features, intrinsics, extrinsics_inv, net_keras, compute_dtype='f32'):
+    def __init__(self, images, features, intrinsics, extrinsics_inv, net_keras, compute_dtype='f32', weight_images=None):
+        """weight_images: (packed, packed_split, bwd_streams) of `net_keras` kept by the caller (LanguageNeRF's trunk cache); None packs
+        them here."""
         if compute_dtype not in COMPUTE_DTYPES:
             raise ValueError(f"compute_dtype must be 'f32' or 'bf16', got {compute_dtype!r}")
         self.compute_dtype = compute_dtype
         self.geo = (images.contiguous(), features.contiguous(), intrinsics.contiguous(), extrinsics_inv.contiguous())
-        self.packed = ops.pack_net(net_keras)
-        self.packed_split = ops.pack_net_split(net_keras)          # value pass on the split-bf16 kernel (fp32-grade, DESIGN.md 4.0)
-        self.bwd_streams = ops.pack_bwd_streams(net_keras)
+        if weight_images is not None:
+            self.packed, self.packed_split, self.bwd_streams = weight_images
+        else:
+            self.packed = ops.pack_net(net_keras)
+            self.packed_split = ops.pack_net_split(net_keras)      # value pass on the split-bf16 kernel (fp32-grade, DESIGN.md 4.0)
+            self.bwd_streams = ops.pack_bwd_streams(net_keras)
         self.n_views = images.shape[1]
         if compute_dtype == 'bf16':                                # the hidden layers on the bf16 MFMA, forward and VJP (DESIGN.md 12.2)
             self.packed16 = ops.pack_net_bf16(net_keras)
@@ -568,10 +573,12 @@ class LanguageNeRF(nn.Module):
         self.optimizer = None
         self._graph_mode, self._graph, self._g_static, self._g_out, self._g_calls = False, None, None, None, 0
         self.fused_step, self.loss_weights, self._fs = False, (1.0, 1.0, 1.0), None
+        self.fused_optimizer, self._opt, self._learning_rate, self._trunk_images = False, None, 1e-4, None
         self.to(self.device_)
 
     # -- reference API --
-    def compile(self, optimizer=None, loss=None, learning_rate=1e-4, graph=False, fused_tail=None, fused_step=None, loss_weights=None):
+    def compile(self, optimizer=None, loss=None, learning_rate=1e-4, graph=False, fused_tail=None, fused_step=None, loss_weights=None,
+                fused_optimizer=None):
         """graph=True: `train_step` is captured ONCE as a HIP graph (torch.cuda.CUDAGraph) and replayed: the step is ~740 launches of
         3-500 us that the host cannot issue as fast as the GPU runs them - 6.6 ms per replay against 8-10.7 ms eager at the cfg3 shape
         (profiles/r02_language_step_graph.md).  The graph fixes shapes and addresses:
@@ -584,7 +591,23 @@ class LanguageNeRF(nn.Module):
         algebra, the losses and every weight gradient as HIP launches on the current stream, no autograd graph); the parameters' `.grad` are
         views into its flat gradient, the optimizer and `graph=True` work as before.  False is the autograd path; None keeps the setting.
         loss_weights: (landscape, grad_t, grad_r) factors of the three losses in the total that is differentiated (the reference: 1, 1, 1;
-        the returned losses stay unweighted); None keeps the setting."""
+        the returned losses stay unweighted); None keeps the setting.
+        fused_optimizer: True makes `train_step` one call of mvnerf_language_train_step (csrc/language_opt.hip): the head gather, the
+        fused step and clip + Keras Adam on the parameters where they live, with the bias-corrected rate formed on the device from a step
+        counter - in eager mode and under graph=True, whose captured graph then holds no torch optimizer.  It needs fused_step=True and
+        optimizer=None; `model.optimizer` is None in this mode, `optimizer_steps()` reads the counter, the moments and the counter start
+        at zero at every compile(), and the trunk's weight images are kept across steps (`invalidate_trunk`).  The update is Keras's,
+        p - lr_t m / (sqrt(v) + eps), not torch.optim.Adam's (eps elsewhere).  False is the torch optimizer; None keeps it."""
+        for name, flag in (('fused_step', fused_step), ('fused_optimizer', fused_optimizer)):
+            if flag is not None and not isinstance(flag, bool):
+                raise ValueError(f'{name} must be True or False (compile: or None to keep the setting), got {flag!r}')
+        if self.fused_optimizer if fused_optimizer is None else fused_optimizer:
+            if not (self.fused_step if fused_step is None else fused_step):
+                raise ValueError('fused_optimizer=True needs fused_step=True: the update reads the flat gradient of the C step')
+            if optimizer is not None:
+                raise ValueError('fused_optimizer=True is its own Adam inside the C call; pass learning_rate instead of an optimizer')
+        if fused_optimizer is not None and fused_optimizer != self.fused_optimizer:
+            self.fused_optimizer, self._trunk_images = fused_optimizer, None       # the optimizer itself is built below, once
         if fused_tail is not None:
             self.set_fused_tail(fused_tail)
         if fused_step is not None:
@@ -595,7 +618,12 @@ class LanguageNeRF(nn.Module):
             self.loss_weights = tuple(float(x) for x in loss_weights)
         if graph and optimizer is not None:
             raise ValueError('graph=True builds its own capturable Adam; pass learning_rate instead of an optimizer')
-        self.optimizer = optimizer or torch.optim.Adam(self.grasp_readout.parameters(), lr=learning_rate, eps=1e-7, capturable=bool(graph))
+        self._learning_rate = float(learning_rate)
+        if self.fused_optimizer:
+            self.optimizer, self._opt = None, self._adam_state(learning_rate)
+        else:
+            self._opt = None
+            self.optimizer = optimizer or torch.optim.Adam(self.grasp_readout.parameters(), lr=learning_rate, eps=1e-7, capturable=bool(graph))
         if loss is not None:
             self.loss = loss
         self._graph_mode, self._graph, self._g_static, self._g_out, self._g_calls = bool(graph), None, None, None, 0
@@ -614,9 +642,49 @@ class LanguageNeRF(nn.Module):
         step, like set_fused_tail."""
         if not isinstance(fused_step, bool):
             raise ValueError(f'fused_step must be True or False (compile: or None to keep the setting), got {fused_step!r}')
+        if not fused_step and self.fused_optimizer:
+            raise ValueError('fused_optimizer is on and needs fused_step=True; switch it off first (set_fused_optimizer(False))')
         if fused_step != self.fused_step:
             self.fused_step = fused_step
             self._graph, self._g_out, self._g_calls = None, None, 0
+
+    def set_fused_optimizer(self, fused_optimizer, learning_rate=None):
+        """The optimizer inside the C call (compile(fused_optimizer=...)).  Switching it on needs fused_step and starts new moments and a
+        new step counter at `learning_rate` (None: the last compile()'s); switching it off puts torch's Adam back at that rate.  A change
+        drops a captured step, like set_fused_step."""
+        if not isinstance(fused_optimizer, bool):
+            raise ValueError(f'fused_optimizer must be True or False (compile: or None to keep the setting), got {fused_optimizer!r}')
+        if fused_optimizer and not self.fused_step:
+            raise ValueError('fused_optimizer=True needs fused_step=True: the update reads the flat gradient of the C step')
+        if fused_optimizer == self.fused_optimizer:
+            return
+        lr = self._learning_rate if learning_rate is None else float(learning_rate)
+        self.fused_optimizer, self._trunk_images = fused_optimizer, None
+        if fused_optimizer:
+            self.optimizer, self._opt = None, self._adam_state(lr)
+        else:
+            self._opt = None
+            self.optimizer = torch.optim.Adam(self.grasp_readout.parameters(), lr=lr, eps=1e-7, capturable=self._graph_mode)
+        self._graph, self._g_out, self._g_calls = None, None, 0
+
+    def _adam_state(self, learning_rate):
+        """Zero moments in the layout of the flat gradient and a zero step counter, on the model's device."""
+        total = ops.language_grad_layout(self.n_transforms_to_check)[1]
+        dev = self.device_
+        return {'m': torch.zeros(total, dtype=torch.float32, device=dev), 'v': torch.zeros(total, dtype=torch.float32, device=dev),
+                'step': torch.zeros(1, dtype=torch.int64, device=dev), 'lr': float(learning_rate)}
+
+    def optimizer_steps(self):
+        """Completed updates of the fused optimizer: one host read of its device counter, on demand only."""
+        if not self.fused_optimizer:
+            raise RuntimeError('optimizer_steps() reads the counter of compile(fused_optimizer=True)')
+        return int(self._opt['step'].item())
+
+    def invalidate_trunk(self):
+        """For a caller that wrote `trunk_net` through a raw pointer (no version bump) under fused_optimizer: the next step packs the
+        trunk's weight images again, into the buffers it has (a captured graph stays valid)."""
+        if self._trunk_images is not None:
+            self._trunk_images['key'] = None
 
     # -- checkpoints (model_v4.py:132-174): torch.save'd tensors, one file per sub-model, load() -> False when a file is missing --
     # The reference also writes and reads `{path}_visual_features` / `{path}_combine_clip_visual`; here the feature map is an input
@@ -682,7 +750,23 @@ class LanguageNeRF(nn.Module):
         """inputs[4:7] = src_images (B,V,H,W,3), src_intrinsics (B,V,4,4), src_extrinsics_inv (B,V,4,4) (model_v4.py:209-213)."""
         dev = self.device_
         f32 = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev)
-        return TrunkState(f32(inputs[4]), f32(batched_features), f32(inputs[5]), f32(inputs[6]), self.trunk_net, compute_dtype)
+        images = self._trunk_weight_images() if self.fused_optimizer and compute_dtype == 'f32' else None
+        return TrunkState(f32(inputs[4]), f32(batched_features), f32(inputs[5]), f32(inputs[6]), self.trunk_net, compute_dtype, images)
+
+    def _trunk_weight_images(self):
+        """(packed, packed_split, bwd_streams) of the frozen trunk, kept while (trunk_net.data_ptr(), trunk_net._version) is unchanged
+        (load_backbone / load copy in place: a new version); packed again INTO the same buffers otherwise, so that a captured step,
+        which holds their addresses, reads the new trunk."""
+        net = self.trunk_net
+        key = (net.data_ptr(), net._version)
+        kept = self._trunk_images
+        if kept is None:
+            kept = self._trunk_images = {'key': key, 'images': (ops.pack_net(net), ops.pack_net_split(net), ops.pack_bwd_streams(net))}
+        elif kept['key'] != key:
+            for old, new in zip(kept['images'], (ops.pack_net(net), ops.pack_net_split(net), ops.pack_bwd_streams(net))):
+                old.copy_(new)
+            kept['key'] = key
+        return kept['images']
 
     def _query_points(self, transforms):
         """poses = transforms @ offsets (model_v4.py:222-226) reduced to what is used of them: points = the poses' translations, dirs =
@@ -811,7 +895,9 @@ class LanguageNeRF(nn.Module):
                     'workspace': torch.empty(ops.language_workspace_bytes(b, v, h, w, n_p, n5), dtype=torch.uint8, device=dev)}
         return self._fs
 
-    def _loss_and_grads_fused(self, data, combined_features):
+    def _fused_call(self, data, combined_features, stack_heads):
+        """The filled mvnerf_language_call of one step -> (call, its buffers, the tensor whose device and stream the call runs on).
+        stack_heads: gather the four per-activation layers into the stacked images here (mvnerf_language_train_step does it itself)."""
         if self.loss is kl_divergence and self.softmax_before_loss:
             kind = 'kl_divergence'
         elif self.loss is categorical_crossentropy_from_logits and not self.softmax_before_loss:
@@ -833,18 +919,37 @@ class LanguageNeRF(nn.Module):
         with torch.no_grad():
             fs['t_l'].copy_(torch.as_tensor(inputs[0], dtype=torch.float32), non_blocking=True)
             fs['r_l'].copy_(torch.as_tensor(inputs[1], dtype=torch.float32), non_blocking=True)
-            torch.stack([lin.weight.detach() for lin in heads], out=fs['w4'])
-            torch.stack([lin.bias.detach() for lin in heads], out=fs['b4'])
+            if stack_heads:
+                torch.stack([lin.weight.detach() for lin in heads], out=fs['w4'])
+                torch.stack([lin.bias.detach() for lin in heads], out=fs['b4'])
         self.set_pose(inputs[2], inputs[3])
         call = ops.language_call(*state.geo, state.packed, state.packed_split, state.bwd_streams,
                                  (fs['w4'], fs['b4'], comb.weight.detach(), comb.bias.detach()), [t.detach() for t in tail.values()],
                                  self.transforms_to_check, (fs['t_l'], fs['r_l'], self.translations.detach(), self.rotations.detach()), lab, kind,
                                  self.loss_weights, fs['grads'], fs['prediction'], fs['scalars'], fs['workspace'])
+        return call, fs, features
+
+    def _loss_and_grads_fused(self, data, combined_features):
+        call, fs, features = self._fused_call(data, combined_features, True)
         ops.language_loss_and_grads(call, features)
         for prm, g in fs['grad_views']:
             prm.grad = g
         s = fs['scalars'].clone()
         return {'landscape_loss': s[0], 'grad_loss_t': s[1], 'grad_loss_r': s[2], 'pred': s[3]}, fs['prediction'].clone()
+
+    def _train_step_fused(self, data, combined_features):
+        """compile(fused_optimizer=True): the whole step, update included, as one call of mvnerf_language_train_step."""
+        call, fs, features = self._fused_call(data, combined_features, False)
+        heads, comb, tail = self._readout_tensors()
+        opt = self._opt
+        adam = ops.language_adam_state([lin.weight.detach() for lin in heads], [lin.bias.detach() for lin in heads], comb.weight.detach(),
+                                       comb.bias.detach(), [t.detach() for t in tail.values()], fs['w4'], fs['b4'], opt['m'], opt['v'],
+                                       opt['step'], opt['lr'])
+        ops.language_train_step(call, adam, features)
+        for prm, g in fs['grad_views']:
+            prm.grad = g
+        s = fs['scalars'].clone()
+        return {'landscape_loss': s[0], 'grad_loss_t': s[1], 'grad_loss_r': s[2], 'pred': s[3]}
 
     def _clip_and_step(self):
         for prm in self.grasp_readout.parameters():                      # optimize(): clip-by-value 1.0, then Adam
@@ -853,10 +958,15 @@ class LanguageNeRF(nn.Module):
         self.optimizer.step()
 
     def train_step(self, data, combined_features):
-        if self.optimizer is None:
+        if self.optimizer is None and not self.fused_optimizer:
             self.compile()
         if self._graph_mode:
             return self._train_step_graphed(data, combined_features)
+        return self._step(data, combined_features)
+
+    def _step(self, data, combined_features):
+        if self.fused_optimizer:
+            return self._train_step_fused(data, combined_features)
         out, _ = self.loss_and_grads(data, combined_features)
         self._clip_and_step()
         return out
@@ -902,8 +1012,7 @@ class LanguageNeRF(nn.Module):
             side = torch.cuda.Stream(self.device_)
             side.wait_stream(torch.cuda.current_stream(self.device_))
             with torch.cuda.stream(side):
-                out, _ = self.loss_and_grads(data_s, feats)
-                self._clip_and_step()
+                out = self._step(data_s, feats)
             torch.cuda.current_stream(self.device_).wait_stream(side)
             return out
         if self._graph is None:
@@ -912,8 +1021,9 @@ class LanguageNeRF(nn.Module):
                 prm.grad = None
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out, _ = self.loss_and_grads(data_s, feats)
-                self._clip_and_step()
+                out = self._step(data_s, feats)
             self._graph, self._g_out = graph, out
+        elif self.fused_optimizer:
+            self._trunk_weight_images()                  # the captured step holds the kept images: packed again in place if the trunk changed
         self._graph.replay()
         return {k: v.clone() for k, v in self._g_out.items()}

@@ -1578,6 +1578,55 @@ def language_loss_and_grads(call, stream_of):
         _lib.check(_lib.lib().mvnerf_language_loss_and_grads(ctypes.byref(call), _stream(stream_of)), 'language_loss_and_grads')
 
 
+def language_adam_state(head_w, head_b, head_wc, head_bc, tail, w4, b4, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-7, clip=1.0):
+    """Fill a mvnerf_language_adam (include/mvnerf_hip.h) from device tensors; the caller keeps them alive.  head_w / head_b: the four
+    activation_downscale weights (64, 128) / biases (64,), the variables themselves; tail: the 11 tensors of language_call's `tail`; w4,
+    b4: the stacked images language_call's `head` holds; m, v: flat, the size and layout of the gradient; step: one int64 on the device
+    (completed updates).  lr is the plain rate: the bias correction is formed on the device from `step`."""
+    if len(head_w) != 4 or len(head_b) != 4:
+        raise ValueError('head_w, head_b: the four activation_downscale layers')
+    for k in range(4):
+        _chk(head_w[k], f'head_w[{k}]', shape=(64, 128))
+        _chk(head_b[k], f'head_b[{k}]', shape=(64,))
+    _chk(head_wc, 'head_wc', shape=(64, 256))
+    _chk(head_bc, 'head_bc', shape=(64,))
+    if len(tail) != 11:
+        raise ValueError('tail: the 11 tensors of grasp_tail_pack')
+    n5 = tail[0].shape[-1] // 64 if isinstance(tail[0], torch.Tensor) and tail[0].dim() == 2 else 0
+    k = 64 * n5
+    for t, name, shape in zip(tail, _TAIL_ORDER, ((128, k), (128,), (64, 128), (64,), (64, k), (64, 64), (64,), (64, 64), (64,), None, (1,))):
+        _chk(t, 'tail ' + name, shape=shape)
+    if n5 < 1 or tail[9].numel() != 64:
+        raise ValueError(f'tail: w0 {tuple(tail[0].shape)}, w_out {tuple(tail[9].shape)}, expected (128, 64 n5) and (1, 64)')
+    _chk(w4, 'w4', shape=(4, 64, 128))
+    _chk(b4, 'b4', shape=(4, 64))
+    total = int(_lib.lib().mvnerf_language_grad_floats(n5))
+    _chk(m, 'm', shape=(total,))
+    _chk(v, 'v', shape=(total,))
+    _chk(step, 'step', dtype=torch.int64, shape=(1,))
+    a = _lib.LanguageAdam()
+    for i in range(4):
+        a.head_w[i], a.head_b[i] = head_w[i].data_ptr(), head_b[i].data_ptr()
+    for i, t in enumerate(tail):
+        a.tail_w[i] = t.data_ptr()
+    for name, x in (('head_wc', head_wc), ('head_bc', head_bc), ('head_w4', w4), ('head_b4', b4), ('m', m), ('v', v), ('step', step)):
+        setattr(a, name, x.data_ptr())
+    a.lr, a.beta1, a.beta2, a.eps, a.clip = float(lr), float(beta1), float(beta2), float(eps), float(clip)
+    return a
+
+
+def language_apply_gradients(call, adam, stream_of):
+    """mvnerf_language_apply_gradients: clip + Keras Adam from call's grads on the variables of `adam`, in place; its step counter rises by one."""
+    with torch.cuda.device(stream_of.device):
+        _lib.check(_lib.lib().mvnerf_language_apply_gradients(ctypes.byref(call), ctypes.byref(adam), _stream(stream_of)), 'language_apply_gradients')
+
+
+def language_train_step(call, adam, stream_of):
+    """mvnerf_language_train_step: head gather, mvnerf_language_loss_and_grads, mvnerf_language_apply_gradients - LanguageNeRF.train_step."""
+    with torch.cuda.device(stream_of.device):
+        _lib.check(_lib.lib().mvnerf_language_train_step(ctypes.byref(call), ctypes.byref(adam), _stream(stream_of)), 'language_train_step')
+
+
 def pose_adam_config(lr0=(0.09, 0.09), decay=(1.0, 1.0), beta1=0.9, beta2=0.999, eps=1e-7, clip=1.0, clip_translation=False, bounds=None):
     """mvnerf_pose_adam_config: lr0 / decay per variable (translations, rotations); bounds (3, 2) = workspace_bounds."""
     bounds = np.zeros((3, 2)) if bounds is None else np.asarray(bounds, dtype=np.float64).reshape(3, 2)

@@ -526,16 +526,23 @@ def fit(grasp_model, data_generator, epochs, initial_epoch=0, log=print):
 
 
 def train_grasp_model(grasp_model, data_generator, n_epochs, eval_after_epochs, model_log_dir, model_checkpoint_name, grasp_optimizer,
-                      optimization_config, callback, valid_data, log=print, fused_tail=False, fused_step=False):
+                      optimization_config, callback, valid_data, log=print, fused_tail=False, fused_step=False, fused_optimizer=False):
     """training.py:23-78 (`callback` takes the place of wandb_config: called with log_results' dict).  One validation on valid_data[:1]
     first, as the reference does (also on a resumed run); then per `eval_after_epochs`: fit, validate all, results-{e}.pkl, log, store
     `{model_log_dir}/best` on a better t*1000 + r/pi*180, training_progress.json, the checkpoint.  -> the fit history.
     fused_tail: the read-out's per-pose layers as fused HIP passes for this run (LanguageNeRF.set_fused_tail; the default is today's
-    layer-by-layer path).  fused_step: the training step up to the optimiser as one C call for this run (LanguageNeRF.set_fused_step)."""
+    layer-by-layer path).  fused_step: the training step up to the optimiser as one C call for this run (LanguageNeRF.set_fused_step).
+    fused_optimizer: the optimiser inside that call too (LanguageNeRF.set_fused_optimizer: Keras Adam with a device-side step counter;
+    implies fused_step).  Its moments are in no checkpoint, as torch's are not: a resumed run starts them at zero either way."""
+    fused_step = bool(fused_step or fused_optimizer)
     if fused_tail or getattr(getattr(grasp_model, 'grasp_readout', None), 'fused_tail', False):
         grasp_model.set_fused_tail(bool(fused_tail))
+    if not fused_optimizer and getattr(grasp_model, 'fused_optimizer', False):
+        grasp_model.set_fused_optimizer(False)
     if fused_step or getattr(grasp_model, 'fused_step', False):
-        grasp_model.set_fused_step(bool(fused_step))
+        grasp_model.set_fused_step(fused_step)
+    if fused_optimizer:
+        grasp_model.set_fused_optimizer(True)
     best_mean_error, n_fits, start_epoch, start_n_fit, training_progress_file = load_training_progress(eval_after_epochs, model_log_dir,
                                                                                                        n_epochs)
     log(f'Starting training from epoch {start_epoch}; best mean error {best_mean_error}')
@@ -603,6 +610,9 @@ def main(argv=None):
                     help="compile(fused_tail=True): the read-out's per-pose layers as fused HIP passes (csrc/grasp_tail_train.hip)")
     ap.add_argument('--fused-step', action='store_true',
                     help='compile(fused_step=True): the training step up to the optimiser as one C call (csrc/language_api.hip)')
+    ap.add_argument('--fused-optimizer', action='store_true',
+                    help='compile(fused_optimizer=True): the whole training step, clip + Keras Adam included, as one C call '
+                         '(csrc/language_opt.hip); implies --fused-step')
     ap.add_argument('--size', default='32', help='image size: H or HxW (reference 480x640)')
     ap.add_argument('--n-scenes', type=int, default=16)
     ap.add_argument('--n-perspectives', type=int, default=5)
@@ -646,7 +656,9 @@ def main(argv=None):
     model = LanguageNeRF(np.zeros(NET_PARAMS, dtype=np.float32), n_points_train=args.pose_augmentation_factor * args.n_future_poses,
                          n_views=args.n_views, batch_size=args.batch_size, rotation_representation=args.rotation_representation,
                          softmax_before_loss=softmax_before_loss, device=dev)
-    model.compile(loss=loss, learning_rate=args.learning_rate, graph=args.graph, fused_tail=args.fused_tail, fused_step=args.fused_step)
+    fused_step = args.fused_step or args.fused_optimizer
+    model.compile(loss=loss, learning_rate=args.learning_rate, graph=args.graph, fused_tail=args.fused_tail, fused_step=fused_step,
+                  fused_optimizer=args.fused_optimizer)
     backbone = os.path.join(args.backbone_path, 'model_final')
     if args.init_backbone:
         os.makedirs(args.backbone_path, exist_ok=True)
@@ -666,7 +678,7 @@ def main(argv=None):
                                decay_t=args.decay_t, decay_r=args.decay_r)
     start = time.time()
     train_grasp_model(model, generator, args.epochs, args.eval_after, args.model_path, checkpoint, optimizer, optimization_config, None,
-                      valid_data, fused_tail=args.fused_tail, fused_step=args.fused_step)
+                      valid_data, fused_tail=args.fused_tail, fused_step=fused_step, fused_optimizer=args.fused_optimizer)
     print(f'done in {time.time() - start:.1f} s')
 
 
