@@ -846,6 +846,20 @@ int mvnerf_render_fwd_split_ex(const float* rays_o, const float* rays_d, const f
 int mvnerf_fuse_upsample2x(const float* a, const float* b, const float* weight, int N, int h, int w, int Ca, int Cb, int act,
                            void* out, int out_bf16, mvnerf_stream_t stream);
 
+/* The backward of mvnerf_fuse_upsample2x as one launch.  g = dL/dout (N,2h,2w,256) fp32 NHWC; a, b, weight as in the forward:
+ *   g_low[n,y,x,c] = sum_{Y,X'} cy(Y,y) cx(X',x) g[n,Y,X',c]       the adjoint of the x2 bilinear up-sampling (half-pixel centres, clamped
+ *                                                                 taps; the two taps that clamp onto one border sample add to 1)
+ *   dX[n,y,x,k]    = act'(X[n,y,x,k]) * sum_c g_low[n,y,x,c] weight[k,c],   X = [a | b];   da = dX[..., :Ca],  db = dX[..., Ca:]
+ * da (N,h,w,Ca), db (N,h,w,Cb), g_low (N,h,w,256): each may be NULL (not wanted; only the requested halves are computed); all three NULL
+ * is MVNERF_E_ARG.  g_low is the copy of the adjoint a weight gradient needs: dW = act(X)^T . g_low.  a (b) may be NULL where act == 0 or
+ * da (db) is NULL: the identity does not read them.  A low pixel gathers its <= 4 x 4 outputs in a fixed order (rows first, then columns,
+ * ascending; csrc/mvnerf_feature_tail.h), one rounding per written operation; the product is exact-fp32 MFMA, summed over the 256 channels
+ * in a fixed order.  No atomics, no workspace, no host read: bit-identical from run to run, and capturable.  A NaN in g reaches only the
+ * <= 2 x 2 low pixels it feeds.  Shape rules of the forward (Ca, Cb multiples of 16, each >= 16, Ca + Cb <= 512, act 0..2: else
+ * MVNERF_E_SHAPE); every non-NULL pointer 16-byte aligned. */
+int mvnerf_fuse_upsample2x_bwd(const float* g, const float* a, const float* b, const float* weight, int N, int h, int w, int Ca, int Cb,
+                               int act, float* da, float* db, float* g_low, mvnerf_stream_t stream);
+
 /* ---- 3x3 convolutions of the language fusion (layers.py:414-456 DoubleConv / Up, :593-660 CombineCLIPVisualV4) as one launch each:
  *   out[n,i,j,co] = mul[n,co] * act( sum_{dy,dx in 0..2} sum_c X[n, i+dy-1, j+dx-1, c] * W[dy,dx,c,co] ),   X = [a | b] along c
  * Conv2D(3, padding='same', use_bias=False), stride 1; taps outside the image are 0; images of a batch do not see each other.

@@ -196,6 +196,7 @@ SIGNATURES = {
     'mvnerf_render_fwd_split_ex': (c_int, [c_void_p] * 12 + [c_int] * 6 + [c_double, c_double, c_int] + [c_void_p] * 6 +
                                    [c_int, c_int, c_void_p, c_void_p]),
     'mvnerf_fuse_upsample2x': (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p, c_int, c_void_p]),
+    'mvnerf_fuse_upsample2x_bwd': (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p] * 4),
     'mvnerf_conv3x3_packed_bytes': (c_size_t, [c_int, c_int]),
     'mvnerf_conv3x3_pack': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'mvnerf_absmax_f32': (c_int, [c_void_p, c_long, c_void_p, c_void_p]),

@@ -537,9 +537,12 @@ def _wants_fused(fused_tail, *tensors, name='fused_tail'):
 
 def conv_fusion_tail(a, b, conv, activation=None, fused=False, out_dtype=None):
     """`up_sample(conv(act([a | b])))` of NCHW a, b with a bias-free 1x1 `conv` to 256 filters -> (N, 256, 2h, 2w), channels-last storage.
-    fused: one ops.fuse_upsample2x call, which writes NHWC in `out_dtype` (fp32 | bf16) directly; else torch (fp32; the caller casts)."""
+    fused: one ops.fuse_upsample2x call, which writes NHWC in `out_dtype` (fp32 | bf16) directly; else torch (fp32; the caller casts).
+    fused='backward': :class:`FuseUpsample2xFunction`, the same launch with a HIP backward (fp32 out)."""
     if not fused:
         return _up(conv(_ACT_FNS[activation](torch.cat([a, b], 1))), 2)
+    if fused == 'backward':
+        return FuseUpsample2xFunction.apply(a, b, conv.weight, activation)
     from . import ops
     nhwc = lambda t: t.detach().permute(0, 2, 3, 1).contiguous()      # free when the storage is channels-last already
     weight = conv.weight.detach().reshape(conv.out_channels, conv.in_channels).t().contiguous()      # (Cin, 256): the Keras kernel as stored
@@ -547,19 +550,86 @@ def conv_fusion_tail(a, b, conv, activation=None, fused=False, out_dtype=None):
     return out.permute(0, 3, 1, 2)
 
 
+class FuseUpsample2xFunction(torch.autograd.Function):
+    """:func:`conv_fusion_tail` as HIP passes in both directions: a, b NCHW, `weight` the (256, Ca + Cb, 1, 1) parameter of
+    the bias-free 1x1 convolution, `activation` None | 'relu' | 'elu' -> (N, 256, 2h, 2w) fp32, channels-last storage.
+    forward: the ops.fuse_upsample2x launch of the inference path; saves a, b (NHWC) and the weight, nothing else - neither the
+    concatenated input nor the low-resolution product.  backward, for g = dL/dout: one ops.fuse_upsample2x_bwd launch that computes only
+    the halves `needs_input_grad` asks for.  Where the weight needs a gradient the launch also writes the adjoint of the up-sampling,
+    g_low, and dW = act([a | b])^T . g_low runs through the fixed-order ops.gemm_tn (torch's matmul on the same two arrays where its shape
+    rule does not hold) - a route for correctness, not for speed: the reference never trains this weight (`combine_clip_visual` is not
+    in `FeatureProducer.trainable_parameters()`), and freezing it is the intended use."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, activation):
+        from . import ops
+        an, bn = _nhwc(a), _nhwc(b)
+        out = ops.fuse_upsample2x(an, bn, _tail_weight(weight), _ACT_CODES[activation], torch.float32)
+        ctx.save_for_backward(an, bn, weight)
+        ctx.activation = activation
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        an, bn, weight = ctx.saved_tensors
+        need_a, need_b, need_w = ctx.needs_input_grad[:3]
+        da, db, g_low = ops.fuse_upsample2x_bwd(_nhwc(g), an, bn, _tail_weight(weight), _ACT_CODES[ctx.activation], need_a=need_a, need_b=need_b,
+                                                need_g_low=need_w)
+        dw = None
+        if need_w:
+            x = _ACT_FNS[ctx.activation](torch.cat([an, bn], -1)).reshape(-1, an.shape[3] + bn.shape[3])
+            low = g_low.reshape(-1, g_low.shape[3])
+            if x.shape[0] % 8 == 0 and x.shape[1] % 32 == 0:                  # mvnerf_gemm_tn: M % 8, N % 32, K % 64 (K = 256 here)
+                dw = ops.gemm_tn(x, low)
+            else:
+                dw = x.t() @ low
+            dw = dw.t().reshape(weight.shape)                                 # (Cin, 256) -> (256, Cin, 1, 1)
+        nchw = lambda t: None if t is None else t.permute(0, 3, 1, 2)
+        return nchw(da), nchw(db), dw, None
+
+
+def _tail_weight(weight):
+    """(256, Cin, 1, 1) -> (Cin, 256), the Keras 1x1 kernel as stored (512 KiB at most: copied per call)."""
+    return weight.detach().reshape(weight.shape[0], weight.shape[1]).t().contiguous()
+
+
+def _tail_switch(fused_tail, fused_backward, *tensors):
+    """What :func:`conv_fusion_tail` runs: 'backward' where `fused_backward` is on and the call is its case (the switch True | 'auto',
+    everything on the GPU, a gradient needed; the Function's output is fp32, so a bf16 `out_dtype` keeps today's path) - else whatever
+    :func:`_wants_fused` says, its "no backward" error included."""
+    if fused_tail not in (True, False, 'auto'):
+        raise ValueError(f"fused_tail: {fused_tail!r}, expected True, False or 'auto'")
+    if _wants_fused_backward(fused_tail, fused_backward, *tensors):
+        return 'backward'
+    return _wants_fused(fused_tail, *tensors)
+
+
 class CombineCLIPVisualV0(nn.Module):
     """legacy_layers.py:154-191: [resize(clip stage-1 map, (H/2, W/2)) | visual features] -> 1x1 conv (no bias) -> x2 bilinear.
-    fused_tail (default False: torch): concat + conv + up-sampling as one HIP pass, see :func:`conv_fusion_tail`."""
+    fused_tail (default False: torch): concat + conv + up-sampling as one HIP pass, see :func:`conv_fusion_tail`.
+    fused_backward (default False): where a call under `fused_tail` (True | 'auto') needs a gradient and the output is fp32, the tail runs
+    as :class:`FuseUpsample2xFunction` - HIP in both directions - instead of torch ('auto') or the "no backward" error (True)."""
 
-    def __init__(self, half_size=(240, 320), clip_channels=256, visual_channels=256, filters=256, fused_tail=False):
+    def __init__(self, half_size=(240, 320), clip_channels=256, visual_channels=256, filters=256, fused_tail=False, fused_backward=False):
         super().__init__()
         self.conv = SameConv2d(clip_channels + visual_channels, filters, 1, bias=False)
         self.half_size = tuple(half_size)
         self.fused_tail = fused_tail
+        self.fused_backward = fused_backward
+
+    @property
+    def fused_backward(self):
+        return self._fused_backward
+
+    @fused_backward.setter
+    def fused_backward(self, value):
+        self._fused_backward = _check_bool(value)
 
     def forward(self, clip_256, visual_features, out_dtype=None):
         clip = _resize(clip_256, self.half_size)
-        fused = _wants_fused(self.fused_tail, clip, visual_features, self.conv.weight)
+        fused = _tail_switch(self.fused_tail, self.fused_backward and out_dtype in (None, torch.float32), clip, visual_features,
+                             self.conv.weight)
         return conv_fusion_tail(clip, visual_features, self.conv, None, fused, out_dtype)
 
 
@@ -920,12 +990,15 @@ class CombineCLIPVisualV4(nn.Module):
     tail of :class:`CombineCLIPVisualV0` (`conv_fusion_3` + `up_sample`).  up3_filters=128 is V4, 256 is V3 (:523-590), which differs
     in nothing else.  Inputs are NCHW (channels-last storage); the pooled CLIP vector is carried and not used, as in the reference.
     fused_tail: 'auto' | True | False - the tail as one HIP pass (:func:`conv_fusion_tail`) when on the GPU and nothing needs a gradient.
+    fused_backward: False (default) | True - where a call under `fused_tail` needs a gradient and the output is fp32, the tail runs as
+    :class:`FuseUpsample2xFunction`, HIP in both directions.
     fused_conv: False (default) | True | 'auto' - the seven 3x3 convolutions as ops.conv3x3 launches under the same rule
     (:func:`conv3x3_act`), `multiply_fusion_1..3` in the epilogue of the convolution in front of them, every amax_out the next amax.
     Parity unpinned, like the rest of this file."""
 
     def __init__(self, use_dense=False, activation='relu', half_size=(240, 320), clip_channels=(256, 512, 1024, 2048), text_dim=1024,
-                 widths=(1024, 512, 256), up3_filters=128, visual_channels=256, filters=256, fused_tail='auto', fused_conv=False):
+                 widths=(1024, 512, 256), up3_filters=128, visual_channels=256, filters=256, fused_tail='auto', fused_conv=False,
+                 fused_backward=False):
         super().__init__()
         hh, hw = half_size
         if hh % 8 or hw % 8:
@@ -948,6 +1021,15 @@ class CombineCLIPVisualV4(nn.Module):
         self.conv_fusion_3 = ConvFusion(up3_filters + visual_channels, filters, activation)
         self.fused_tail = fused_tail
         self.fused_conv = fused_conv
+        self.fused_backward = fused_backward
+
+    @property
+    def fused_backward(self):
+        return self._fused_backward
+
+    @fused_backward.setter
+    def fused_backward(self, value):
+        self._fused_backward = _check_bool(value)
 
     @property
     def fused_conv(self):
@@ -983,7 +1065,8 @@ class CombineCLIPVisualV4(nn.Module):
             x, _ = self.up_2.convs(x, clip_l2, tile(self.multiply_fusion_3))
             x = self.conv_fusion_2(x, vis_1)
             x, _ = self.up_3.convs(x, clip_l1)
-        fused = _wants_fused(self.fused_tail, x, visual_features, self.conv_fusion_3.conv.weight)
+        fused = _tail_switch(self.fused_tail, self.fused_backward and out_dtype in (None, torch.float32), x, visual_features,
+                             self.conv_fusion_3.conv.weight)
         return conv_fusion_tail(x, visual_features, self.conv_fusion_3.conv, self.activation, fused, out_dtype)
 
 

@@ -1688,6 +1688,45 @@ def fuse_upsample2x(a, b, weight, act, out_dtype=torch.float32, out=None):
     return out
 
 
+def fuse_upsample2x_bwd(g, a, b, weight, act, need_a=True, need_b=True, need_g_low=False, out=None):
+    """mvnerf_fuse_upsample2x_bwd: g = dL/dout (N,2h,2w,256) fp32 NHWC and the forward's a, b, weight, act -> (da | None, db | None,
+    g_low | None): the gradients of a (N,h,w,Ca) and b (N,h,w,Cb), and the adjoint of the up-sampling g_low (N,h,w,256) that a weight
+    gradient needs (dW = act([a | b])^T . g_low).  Only what the need flags ask for is computed.  out: None, or a (da, db, g_low) triple
+    of buffers to write (None where not needed).  One launch, no atomics, no workspace."""
+    _chk(a, 'a', shape=(None, None, None, None))
+    n, h, w, ca = a.shape
+    _chk(b, 'b', shape=(n, h, w, None))
+    cb = b.shape[3]
+    _chk(weight, 'weight', shape=(ca + cb, 256))
+    _chk(g, 'g', shape=(n, 2 * h, 2 * w, 256))
+    if not isinstance(act, int):
+        if act not in FUSE_ACTIVATIONS:
+            raise ValueError(f'act: {act!r}, expected one of {list(FUSE_ACTIVATIONS)} or 0, 1, 2')
+        act = FUSE_ACTIVATIONS[act]
+    needs = (bool(need_a), bool(need_b), bool(need_g_low))
+    if not any(needs):
+        raise ValueError('fuse_upsample2x_bwd: nothing asked for (need_a, need_b and need_g_low are all False)')
+    shapes = ((n, h, w, ca), (n, h, w, cb), (n, h, w, 256))
+    names = ('da', 'db', 'g_low')
+    if out is None:
+        out = (None, None, None)
+    elif len(out) != 3:
+        raise ValueError(f'out: expected a (da, db, g_low) triple, got {len(out)} entries')
+    bufs = []
+    for need, buf, shape, name in zip(needs, out, shapes, names):
+        if not need:
+            bufs.append(None)
+        elif buf is None:
+            bufs.append(torch.empty(shape, dtype=torch.float32, device=a.device))
+        else:
+            bufs.append(_chk(buf, f'out[{name}]', shape=shape))
+    with torch.cuda.device(a.device):
+        rc = _lib.lib().mvnerf_fuse_upsample2x_bwd(_p(g), _p(a), _p(b), _p(weight), n, h, w, ca, cb, int(act), _p(bufs[0]), _p(bufs[1]),
+                                                   _p(bufs[2]), _stream(a))
+    _lib.check(rc, 'fuse_upsample2x_bwd')
+    return tuple(bufs)
+
+
 def absmax(x, out=None):
     """mvnerf_absmax_f32: max |x| of a contiguous fp32 tensor as one device float (shape (1,)); a NaN in x gives a NaN.  No host read."""
     _chk(x, 'x')
