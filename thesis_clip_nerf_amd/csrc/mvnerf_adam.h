@@ -6,6 +6,8 @@
 //   adam_rate   lr_t = (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)) in double; beta^t of (double)beta by square-and-multiply from the
 //               low bit of t upwards, so that the host build, the device and a NumPy restatement agree on every bit (pow does not promise).
 //   kFlat       the 15 entries of `grads` in order (include/mvnerf_hip.h), each with the variable of mvnerf_language_adam it belongs to.
+//   warmup_rate nerf_utils.WarmupScheduler / encoders.warmup_lr_lambda at the counter BEFORE its increment, in double, rounded once.
+//   multi_plan  the chunk prefix of a list of tensors of uneven length, multi_find the tensor a chunk belongs to (no kernel yet: DESIGN.md 21).
 //
 // Arithmetic: compiled with -ffp-contract=off and correctly rounded divide / square root, as everything in this directory.
 #pragma once
@@ -14,8 +16,10 @@
 
 #if defined(__HIPCC__)
 #define MVA_HD __host__ __device__ __forceinline__
+#define MVA_MEMBER __host__ __device__ __forceinline__
 #else
 #define MVA_HD static inline
+#define MVA_MEMBER inline
 #endif
 
 namespace mvnerf {
@@ -48,6 +52,50 @@ MVA_HD void adam_one(float* p, float g, float* m, float* v, float lr_t, float be
     *v = vi;
     *p = *p - lr_t * mi / (sqrtf(vi) + eps);
 }
+
+// The un-corrected rate of the update that finds `step` completed ones (Keras evaluates a schedule at `iterations`, so the first update of
+// a warm-up has rate 0): target * step / warm while step <= warm (the product first), target while step <= after, a tenth of it behind.
+// warm <= 0: no warm-up; after < 0: the rate never drops.  The bias correction is adam_rate(this, b1, b2, step + 1).
+MVA_HD float warmup_rate(float target, double warm, double after, long long step) {
+    const double t = (double)target, s = (double)step;
+    if (warm > 0.0 && s <= warm) return (float)(t * s / warm);
+    if (after < 0.0 || s <= after) return target;
+    return (float)(t * 0.1);
+}
+
+// ---- many tensors of uneven length behind one launch: tensor t owns the chunks first_chunk[t] .. first_chunk[t + 1] of kMultiChunk
+// elements each (the last one partial), a tensor without elements owns none ----
+constexpr long long kMultiChunk = 4096;                     // 256 lanes x four 16-byte accesses
+
+// first_chunk (count + 1) <- the prefix of ceil(n / kMultiChunk); returns its last entry, the number of chunks
+MVA_HD long long multi_plan(const long long* n, int count, long long* first_chunk) {
+    long long at = 0;
+    for (int t = 0; t < count; ++t) {
+        first_chunk[t] = at;
+        if (n[t] > 0) at += (n[t] + kMultiChunk - 1) / kMultiChunk;
+    }
+    first_chunk[count] = at;
+    return at;
+}
+
+// the LAST t in 0 .. count - 1 with first(t) <= chunk: of a run of equal entries (tensors without elements, then their successor) the
+// one that owns the chunk.  chunk in 0 .. the total - 1; first(0) == 0.  multi_find_by reads the prefix through `first`, so that a
+// kernel can search the table it has (an array of structs) with the code the host build tests.
+template <class First>
+MVA_HD int multi_find_by(First first, int count, long long chunk) {
+    int lo = 0, hi = count - 1;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (first(mid) <= chunk) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+struct MultiPrefix {
+    const long long* first_chunk;
+    MVA_MEMBER long long operator()(int t) const { return first_chunk[t]; }
+};
+MVA_HD int multi_find(const long long* first_chunk, int count, long long chunk) { return multi_find_by(MultiPrefix{first_chunk}, count, chunk); }
 
 // ---- the flat layout of `grads`: head (w4, b4, wc, bc), block_0, block_1 (both weights, then both biases), output_layer ----
 // An entry holds fixed + per_k * K floats (K = 64 n5).  var: the index into mvnerf_language_call.tail_w[] / mvnerf_language_adam.tail_w[]
