@@ -932,6 +932,21 @@ size_t mvnerf_conv3x3_wgrad_workspace_bytes(int N, int h, int w, int Cin, int Co
 int mvnerf_conv3x3_wgrad_nhwc(const float* x, const float* amax_x, int act_in, const float* g, const float* amax_g, int N, int h, int w,
                               int Cin, int Cout, float* dw_hwio, float* dbias, void* workspace, mvnerf_stream_t stream);
 
+/* ---- backward through a FROZEN 3x3 convolution of the language fusion (csrc/act_gate.hip) ---------------------------------
+ * For out = mul * act(y), y = conv3x3_same([a | b], W), as mvnerf_conv3x3_nhwc wrote it, and g = dL/dout:
+ *   d[n,p,c] = g * mul[n,c] * act'(y), from `out` and `mul` alone (y is not kept, nothing is divided):
+ *     act(y) > 0, i.e. out and mul are both positive or both negative:  d = g * mul
+ *     else, relu: d = 0;  else, elu: d = g * (out + mul)   (elu' = elu + 1);  identity: d = g * mul
+ *   mul[n,c] == 0 gives an exact 0.  mul NULL means 1.  The data gradients are then mvnerf_conv3x3_nhwc of d with the transposed packs of
+ *   the rows of W that a and b meet.
+ * g, out, d (N, pixels_per_image, C) fp32 NHWC; d may be g (in place).  mul (N,C) or NULL.  act: 0 identity, 1 relu, 2 elu.
+ * amax_out (optional): one device word the CALLER ZEROES; on return max |d| (a NaN written anywhere makes it a NaN).
+ * One rounding per written operation.  No workspace, no atomics on d: two runs give the same bits.  Stream-ordered, no host read.
+ * 1 <= N <= 65535, N * pixels_per_image <= 2^31 - 1: else MVNERF_E_ARG; C a multiple of 4, act in 0..2: else MVNERF_E_SHAPE; before any
+ * launch.  g, out, mul, d 16-byte aligned. */
+int mvnerf_act_gate_nhwc(const float* g, const float* out, const float* mul, int act, int N, long pixels_per_image, int C, float* d,
+                         float* amax_out, mvnerf_stream_t stream);
+
 /* Batch statistics of a convolution output from its tile partials (layers.py:23, 27: tf.keras BatchNormalization, training=True):
  * mean[c] and rstd[c] = 1 / sqrt(var[c] + eps) with the BIASED variance over all N h w pixels, c < Cout.  The tiles are combined with
  * Chan's pairwise update in double, in a fixed order.  Stream-ordered, no host read (the chain can be captured in a graph). */

@@ -207,7 +207,8 @@ SIGNATURES = {
     'mvnerf_conv3x3_wgrad_slab_pixels': (c_int, []),
     'mvnerf_conv3x3_wgrad_workspace_bytes': (c_size_t, [c_int] * 5),
     'mvnerf_conv3x3_wgrad_nhwc': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 4),
-    'mvnerf_bn_finalize': (c_int, [c_void_p] + [c_int] * 4 + [c_double, c_void_p, c_void_p, c_void_p]),
+    'mvnerf_act_gate_nhwc': (c_int, [c_void_p] * 3 + [c_int, c_int, c_long, c_int] + [c_void_p] * 3),
+    'mvnerf_bn_finalize':(c_int, [c_void_p] + [c_int] * 4 + [c_double, c_void_p, c_void_p, c_void_p]),
     'mvnerf_bn_apply_nhwc': (c_int, [c_void_p] * 6 + [c_long, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'mvnerf_linear_packed_bytes': (c_size_t, [c_int, c_int]),
     'mvnerf_linear_pack': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),

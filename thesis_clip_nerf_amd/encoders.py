@@ -417,6 +417,7 @@ def _mark_loaded(module):
     module.__dict__['_mvnerf_loads'] = module.__dict__.get('_mvnerf_loads', 0) + 1
     module.__dict__.pop('_mvnerf_packed', None)
     module.__dict__.pop('_mvnerf_packed_t', None)
+    module.__dict__.pop('_mvnerf_packed_t_rows', None)
 
 
 def _cached(module, key, make):
@@ -705,11 +706,24 @@ def _packed_conv3x3(conv):
     return cached[1]
 
 
-def conv3x3_act(conv, a, b, activation, fused_conv=False, mul=None, amax_a=None, amax_b=None):
+def conv3x3_act(conv, a, b, activation, fused_conv=False, mul=None, amax_a=None, amax_b=None, fused_backward=False):
     """`act(conv([a | b])) * mul` of NCHW a, b (b may be None) with a bias-free 3x3 `conv`; mul (N, C, 1, 1) or None.  Returns (out, amax):
     through torch (amax None) unless `fused_conv` (True | False | 'auto', :func:`_wants_fused`) selects ops.conv3x3, which reads the two
     sources without a concat or a padded copy and returns max |out| as a device float - the next convolution's `amax_a`.  A convolution
-    the kernel does not take (:func:`conv3x3_fusable`) runs through torch under 'auto' and raises under True."""
+    the kernel does not take (:func:`conv3x3_fusable`) runs through torch under 'auto' and raises under True.
+    fused_backward: where the call needs a gradient with respect to a or b only - the weight and `mul` frozen - it runs as
+    :class:`Conv3x3ActFunction`, HIP in both directions; a weight or `mul` that requires a gradient is not its case: 'auto' uses torch
+    and True raises ValueError."""
+    if _wants_fused_backward(fused_conv, fused_backward, a, b, conv.weight, mul):
+        trains = conv.weight.requires_grad or (mul is not None and mul.requires_grad)
+        if trains and fused_conv is True:
+            raise ValueError('fused_conv=True with fused_backward: the HIP backward of the fusion covers the data gradient only; freeze '
+                             f"the weight and `mul` of this {conv.in_channels} -> {conv.out_channels} convolution or use 'auto'")
+        if not trains and conv3x3_fusable(conv, a.shape[1], 0 if b is None else b.shape[1]):
+            return Conv3x3ActFunction.apply(a, b, conv.weight, conv, activation, mul, amax_a, amax_b)
+        if not trains and fused_conv is True:
+            raise ValueError(f'fused_conv=True: a {tuple(conv.kernel_size)} convolution over {a.shape[1]} + {0 if b is None else b.shape[1]} -> '
+                             f"{conv.out_channels} channels is not one the HIP pass takes (3x3, no bias, multiples of 32 + 32 -> 64); use 'auto'")
     fused = _wants_fused(fused_conv, a, b, conv.weight, mul, name='fused_conv')
     if fused and not conv3x3_fusable(conv, a.shape[1], 0 if b is None else b.shape[1]):
         if fused_conv is True:
@@ -892,22 +906,96 @@ def conv3x3_bn(conv, norm, x, skip=None, fused_conv=False, amax=None, fused_back
     return out.permute(0, 3, 1, 2), top
 
 
+def _packed_conv3x3_t_rows(conv, lo, hi):
+    """:func:`_packed_conv3x3_t` of the input channels lo:hi of `conv.weight` alone - the data gradient's kernel towards one of the two
+    sources of a two-source convolution - cached next to it per parameter version, per load and per slice."""
+    from . import ops
+    weight = conv.weight
+    key = (weight._version, weight.data_ptr(), weight.device, conv.__dict__.get('_mvnerf_loads', 0))
+    rows = conv.__dict__.setdefault('_mvnerf_packed_t_rows', {})
+    cached = rows.get((lo, hi))
+    if cached is None or cached[0] != key:
+        cached = (key, ops.conv3x3_pack_transposed(weight.detach()[:, lo:hi].permute(2, 3, 1, 0).contiguous()))
+        rows[(lo, hi)] = cached
+    return cached[1]
+
+
+def conv3x3_rows_dgrad_fusable(conv, lo, hi):
+    """:func:`conv3x3_dgrad_fusable` on the slice lo:hi of the input channels."""
+    return conv.out_channels % 32 == 0 and hi > lo and (hi - lo) % 64 == 0
+
+
+class Conv3x3ActFunction(torch.autograd.Function):
+    """:func:`conv3x3_act` with a FROZEN weight and `mul` as HIP passes in both directions: the gradient of
+    out = act(conv([a | b])) * mul with respect to a and b - what the visual features need on their way back through the fusion.
+    forward: the ops.conv3x3 launch of the inference path, unchanged; saves `out` (NHWC) and `mul` (N, C) - not a, b or the sum.
+    backward, for g = dL/dout:
+      d           ops.act_gate(g, out, mul): g * mul * act'(y) from out and mul alone, with max |d| in its amax word (no ops.absmax);
+      da          ops.conv3x3 of d with the flipped, transposed pack of the `a` rows of the weight (:func:`_packed_conv3x3_t_rows`),
+                  torch.nn.grad.conv2d_input where the slice's channel counts do not fit (:func:`conv3x3_rows_dgrad_fusable`);
+      db          the same from the `b` rows, only if b needs a gradient (the CLIP maps never do).
+    Returns (out NCHW view of NHWC storage, max |out| as a device float)."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, conv, activation, mul, amax_a, amax_b):
+        from . import ops
+        an, bn = _nhwc(a), _nhwc(b)
+        n, c_out = a.shape[0], conv.out_channels
+        if mul is not None:
+            mul = mul.detach().reshape(mul.shape[0], c_out).expand(n, c_out).contiguous()
+        top = torch.empty(1, dtype=torch.float32, device=a.device)
+        out = ops.conv3x3(an, bn, _packed_conv3x3(conv), c_out, _ACT_CODES[activation], mul=mul, amax_a=amax_a, amax_b=amax_b, amax_out=top)
+        ctx.save_for_backward(out, mul, weight)
+        ctx.conv, ctx.activation, ctx.c_a = conv, activation, a.shape[1]
+        ctx.mark_non_differentiable(top)
+        return out.permute(0, 3, 1, 2), top
+
+    @staticmethod
+    def backward(ctx, g, _g_top):
+        from . import ops
+        out, mul, weight = ctx.saved_tensors
+        conv, c_a = ctx.conv, ctx.c_a
+        n, h, w, _ = out.shape
+        word = torch.empty(1, dtype=torch.float32, device=out.device)
+        d = ops.act_gate(_nhwc(g), out, mul, _ACT_CODES[ctx.activation], amax_out=word)
+
+        def source(lo, hi):
+            if conv3x3_rows_dgrad_fusable(conv, lo, hi):
+                return ops.conv3x3(d, None, _packed_conv3x3_t_rows(conv, lo, hi), hi - lo, 0, amax_a=word).permute(0, 3, 1, 2)
+            return torch.nn.grad.conv2d_input((n, hi - lo, h, w), weight.detach()[:, lo:hi], d.permute(0, 3, 1, 2), padding=1)
+
+        da = source(0, c_a) if ctx.needs_input_grad[0] else None
+        db = source(c_a, conv.in_channels) if ctx.needs_input_grad[1] else None
+        return da, db, None, None, None, None, None, None
+
+
 class DoubleConv(nn.Module):
     """layers.py:414-434: two bias-free 3x3 convolutions, the activation after each.
-    fused_conv (default False: torch): both as ops.conv3x3 launches, see :func:`conv3x3_act`."""
+    fused_conv (default False: torch): both as ops.conv3x3 launches, see :func:`conv3x3_act`.
+    fused_backward (default False): where a call under `fused_conv` needs a gradient and the weights are frozen, both run as
+    :class:`Conv3x3ActFunction`, HIP in both directions."""
 
-    def __init__(self, c_in, filters, activation='relu', fused_conv=False):
+    def __init__(self, c_in, filters, activation='relu', fused_conv=False, fused_backward=False):
         super().__init__()
         self.conv_1 = SameConv2d(c_in, filters, 3, bias=False)
         self.conv_2 = SameConv2d(filters, filters, 3, bias=False)
         self.activation = activation
         self.act = _activation(activation)
         self.fused_conv = fused_conv
+        self.fused_backward = fused_backward
+
+    @property
+    def fused_backward(self):
+        return self._fused_backward
+
+    @fused_backward.setter
+    def fused_backward(self, value):
+        self._fused_backward = _check_bool(value)
 
     def convs(self, a, b=None, mul=None, amax_a=None, amax_b=None):
         """act(conv_2(act(conv_1([a | b])))) * mul -> (out, amax | None); the first convolution's amax_out is the second one's amax."""
-        x, amax = conv3x3_act(self.conv_1, a, b, self.activation, self.fused_conv, None, amax_a, amax_b)
-        return conv3x3_act(self.conv_2, x, None, self.activation, self.fused_conv, mul, amax)
+        x, amax = conv3x3_act(self.conv_1, a, b, self.activation, self.fused_conv, None, amax_a, amax_b, self.fused_backward)
+        return conv3x3_act(self.conv_2, x, None, self.activation, self.fused_conv, mul, amax, fused_backward=self.fused_backward)
 
     def forward(self, x):
         if self.fused_conv is False:
@@ -917,12 +1005,21 @@ class DoubleConv(nn.Module):
 
 class Up(nn.Module):
     """layers.py:437-456: [x2 bilinear of x | CLIP stage map resized to `shape`] -> DoubleConv.
-    fused_conv (default False: torch): the DoubleConv reads the two maps from where they lie, no concat."""
+    fused_conv (default False: torch): the DoubleConv reads the two maps from where they lie, no concat.
+    fused_backward (default False): handed to the DoubleConv."""
 
-    def __init__(self, shape, c_in, c_clip, filters, activation='relu', fused_conv=False):
+    def __init__(self, shape, c_in, c_clip, filters, activation='relu', fused_conv=False, fused_backward=False):
         super().__init__()
         self.shape = tuple(shape)
-        self.double_conv = DoubleConv(c_in + c_clip, filters, activation, fused_conv)
+        self.double_conv = DoubleConv(c_in + c_clip, filters, activation, fused_conv, fused_backward)
+
+    @property
+    def fused_backward(self):
+        return self.double_conv.fused_backward
+
+    @fused_backward.setter
+    def fused_backward(self, value):
+        self.double_conv.fused_backward = value
 
     @property
     def fused_conv(self):
@@ -991,7 +1088,8 @@ class CombineCLIPVisualV4(nn.Module):
     in nothing else.  Inputs are NCHW (channels-last storage); the pooled CLIP vector is carried and not used, as in the reference.
     fused_tail: 'auto' | True | False - the tail as one HIP pass (:func:`conv_fusion_tail`) when on the GPU and nothing needs a gradient.
     fused_backward: False (default) | True - where a call under `fused_tail` needs a gradient and the output is fp32, the tail runs as
-    :class:`FuseUpsample2xFunction`, HIP in both directions.
+    :class:`FuseUpsample2xFunction`, HIP in both directions; it is also handed to `up_1..3`, whose convolutions under `fused_conv` then
+    run as :class:`Conv3x3ActFunction` where a gradient flows to the visual features and the fusion's weights are frozen.
     fused_conv: False (default) | True | 'auto' - the seven 3x3 convolutions as ops.conv3x3 launches under the same rule
     (:func:`conv3x3_act`), `multiply_fusion_1..3` in the epilogue of the convolution in front of them, every amax_out the next amax.
     Parity unpinned, like the rest of this file."""
@@ -1006,7 +1104,8 @@ class CombineCLIPVisualV4(nn.Module):
         c1, c2, c3, c4 = clip_channels
         w1, w2, w3 = widths
         self.half_size = (hh, hw)
-        self.size_1, self.size_2, self.size_3 = (hh // 2, hw // 2), (hh // 4, hw // 4), (hh // 8, hw // 8)
+        self.text_dim = text_dim
+        self.size_1,self.size_2, self.size_3 = (hh // 2, hw // 2), (hh // 4, hw // 4), (hh // 8, hw // 8)
         self.activation = activation
         self.act = _activation(activation)
         self.conv = SameConv2d(c4, w1, 3, bias=False)                                   # Conv2D(..., activation=activation)
@@ -1030,6 +1129,8 @@ class CombineCLIPVisualV4(nn.Module):
     @fused_backward.setter
     def fused_backward(self, value):
         self._fused_backward = _check_bool(value)
+        for up in (self.up_1, self.up_2, self.up_3):
+            up.fused_backward = value
 
     @property
     def fused_conv(self):
@@ -1059,7 +1160,8 @@ class CombineCLIPVisualV4(nn.Module):
             x = self.up_3(x, clip_l1)
         else:               # the same chain; each MultiplyFusion is the `mul` of the convolution in front of it
             tile = lambda fusion: fusion.tile(clip_textuals)
-            x, amax = conv3x3_act(self.conv, _resize(clip_l4, self.size_3), None, self.activation, self.fused_conv, tile(self.multiply_fusion_1))
+            x, amax = conv3x3_act(self.conv, _resize(clip_l4, self.size_3), None, self.activation, self.fused_conv, tile(self.multiply_fusion_1),
+                                  fused_backward=self.fused_backward)
             x, _ = self.up_1.convs(x, clip_l3, tile(self.multiply_fusion_2), amax)
             x = self.conv_fusion_1(x, vis_2)
             x, _ = self.up_2.convs(x, clip_l2, tile(self.multiply_fusion_3))
@@ -1174,6 +1276,53 @@ class LanguageFeatureProducer(nn.Module):
         return out if out.is_contiguous() else out.contiguous()
 
 
+class FeatureProducerV4(nn.Module):
+    """The V4 renderer's encoder prologue (mvnerf/model_v4.py:31, 82-84, 196-240) as one callable: images (N, H, W, 3) in [0, 1] ->
+    combined_features (N, H, W, 256), NHWC-contiguous in `out_dtype`, through VisualFeatures, the CLIP pyramid and
+    CombineCLIPVisualV4(use_dense=False, activation='relu') - the renderer's settings; `LanguageNeRF` builds the same fusion with
+    True / 'elu', so both are arguments - with a constant all-ones text embedding unless one is given.  Use it as
+    `MVVNeRFRenderer(feature_encoder=producer)`: the renderer trains `visual_features` THROUGH the language fusion and writes the
+    sub-model files `LanguageNeRF.load_backbone` reads.  `trainable_parameters()` is :class:`FeatureProducer`'s list (vision_transformer
+    + conv_features); the fusion and the pyramid are frozen (`requires_grad_(False)`), the pyramid runs under `no_grad`.
+    fused_tail / fused_conv / fused_backward are the fusion's switches, fused_visual the `fused_conv` of VisualFeatures (which gets
+    `fused_backward` too), everything else (`fused_vit`, the ViT's sizes) goes to VisualFeatures."""
+
+    def __init__(self, original_image_size=(480, 640), n_features=256, clip_pyramid=None, out_dtype=torch.float32, use_dense=False,
+                 activation='relu', fused_tail='auto', fused_conv=False, fused_backward=False, fused_visual=False, combine_kw=None,
+                 **visual_kw):
+        super().__init__()
+        h, w = original_image_size
+        if h % 16 or w % 16:
+            raise ValueError('image height and width must be multiples of 16 (the fusion starts at 1/16 resolution)')
+        self.visual_features = VisualFeatures(n_features, original_image_size, fused_conv=fused_visual, fused_backward=fused_backward,
+                                              **visual_kw)
+        self.clip_pyramid = clip_pyramid if clip_pyramid is not None else SyntheticCLIPPyramid()
+        kw = dict(use_dense=use_dense, activation=activation, half_size=(h // 2, w // 2), visual_channels=n_features, fused_tail=fused_tail,
+                  fused_conv=fused_conv, fused_backward=fused_backward)
+        kw.update(combine_kw or {})
+        self.combine_clip_visual = CombineCLIPVisualV4(**kw)
+        self.text_dim = self.combine_clip_visual.text_dim
+        self.out_dtype = out_dtype
+        self.combine_clip_visual.requires_grad_(False)
+        self.clip_pyramid.requires_grad_(False)
+
+    def trainable_parameters(self):
+        return list(self.visual_features.vision_transformer.parameters()) + list(self.visual_features.conv_features.parameters())
+
+    def forward(self, images_nhwc, text_embedding=None):
+        n = images_nhwc.shape[0]
+        if text_embedding is None:
+            text = torch.ones(n, self.text_dim, dtype=images_nhwc.dtype, device=images_nhwc.device)       # model_v4.py:31
+        else:
+            text = text_embedding.to(images_nhwc.dtype).expand(n, -1)
+        visual = self.visual_features(images_nhwc)
+        with torch.no_grad():
+            pyramid = self.clip_pyramid(images_nhwc.permute(0, 3, 1, 2))
+        fused = self.combine_clip_visual(pyramid, visual, text, out_dtype=self.out_dtype)      # (N, 256, H, W), channels-last storage
+        out = fused.permute(0, 2, 3, 1).to(self.out_dtype)
+        return out if out.is_contiguous() else out.contiguous()
+
+
 COMBINE_CLIP_VISUAL_V4_VARIABLES = ('conv', 'multiply_fusion_1.tile.dense', 'up_1.double_conv.conv_1', 'up_1.double_conv.conv_2',
                                     'multiply_fusion_2.tile.dense', 'conv_fusion_1.conv', 'up_2.double_conv.conv_1',
                                     'up_2.double_conv.conv_2', 'multiply_fusion_3.tile.dense', 'conv_fusion_2.conv',
@@ -1251,6 +1400,7 @@ def load_conv(conv, kernel_hwio, bias=None):
     conv.weight.data.copy_(_t(kernel_hwio).permute(3, 2, 0, 1))
     conv.__dict__.pop('_mvnerf_packed', None)            # (`.data` does not bump the parameter version the packed-stream cache keys on)
     conv.__dict__.pop('_mvnerf_packed_t', None)
+    conv.__dict__.pop('_mvnerf_packed_t_rows', None)
     if bias is not None:
         conv.bias.data.copy_(_t(bias))
 
@@ -1460,7 +1610,7 @@ def count_parameters(module):
     return sum(p.numel() for p in module.parameters())
 
 
-__all__ = ['FeatureProducer', 'LanguageFeatureProducer', 'CombineCLIPVisualV4', 'DoubleConv', 'Up', 'ConvFusion', 'Tile',
+__all__ = ['FeatureProducer', 'FeatureProducerV4', 'Conv3x3ActFunction', 'LanguageFeatureProducer', 'CombineCLIPVisualV4', 'DoubleConv', 'Up', 'ConvFusion', 'Tile',
            'MultiplyFusion', 'conv3x3_act', 'conv3x3_bias', 'conv3x3_bn', 'conv3x3_auto_pays', 'conv3x3_fusable', 'Block', 'SyntheticCLIPPyramid', 'SyntheticCLIPText', 'tokenize', 'conv_fusion_tail', 'load_combine_clip_visual_v4',
            'COMBINE_CLIP_VISUAL_V4_VARIABLES', 'VisualFeatures', 'CombineCLIPVisualV0', 'ConvolutionalEncoder', 'VisionTransformerEncoder',
            'VisionTransformer', 'TransformerBlock', 'transformer_block_fused', 'vit_block_unfusable', 'SyntheticCLIPStage1', 'flat_net_from_keras', 'keras_from_flat_net',

@@ -690,11 +690,17 @@ class LanguageNeRF(nn.Module):
     # The reference also writes and reads `{path}_visual_features` / `{path}_combine_clip_visual`; here the feature map is an input
     # (DESIGN.md 7), so those files are neither written nor read.  Loading copies IN PLACE into `trunk_net` and the read-out parameters:
     # the Adam state, a captured training graph and DNGFOptimizer's bound views all hold those tensors.
-    def load_backbone(self, path, verbose=True):
+    def load_backbone(self, path, verbose=True, producer=None):
         """The frozen trunk from `{path}_fine_embedding.pt` + `{path}_fine_readout.pt` (MVVNeRFRenderer.store's fine MLP) -> True, or
-        False (nothing changed) if either file is missing."""
+        False (nothing changed) if either file is missing.
+        producer: a LanguageFeatureProducer (anything with `visual_features` and `combine_clip_visual`) - then
+        `{path}_visual_features.pt` and `{path}_combine_clip_visual.pt`, as `MVVNeRFRenderer.store(path, encoders=True)` wrote them, are
+        loaded into it as well (model_v4.py:132-152); False (nothing changed) if either is missing, ValueError naming the first key
+        that does not match."""
+        from .model import ENCODER_SUBMODELS, check_state_dict
         files = [f'{path}_{name}.pt' for name in _BACKBONE_FILES]
-        for f in files:
+        encoder_files = [f'{path}_{name}.pt' for name in ENCODER_SUBMODELS] if producer is not None else []
+        for f in files + encoder_files:
             if not os.path.exists(f):
                 if verbose:
                     print(f'{f} does not exist')
@@ -702,6 +708,11 @@ class LanguageNeRF(nn.Module):
         flat = torch.cat([torch.load(f, weights_only=True).reshape(-1) for f in files])
         if flat.numel() != self.trunk_net.numel():
             raise ValueError(f'{path}: {flat.numel()} backbone parameters, expected {self.trunk_net.numel()}')
+        states = [torch.load(f, weights_only=True) for f in encoder_files]
+        for name, state, f in zip(ENCODER_SUBMODELS, states, encoder_files):
+            check_state_dict(getattr(producer, name), state, f)
+        for name, state in zip(ENCODER_SUBMODELS, states):
+            getattr(producer, name).load_state_dict(state)
         with torch.no_grad():
             self.trunk_net.copy_(flat)
         if self.trunk_net.is_cuda:

@@ -30,6 +30,19 @@ from ._lib import NET_PARAMS, Q7_ZERO
 from .synthetic import glorot_net
 
 _SUBMODELS = ('coarse_embedding', 'coarse_readout', 'fine_embedding', 'fine_readout')
+ENCODER_SUBMODELS = ('visual_features', 'combine_clip_visual')       # the renderer's other two files (mvnerf/model_v4.py:196-240)
+
+
+def check_state_dict(module, state, what):
+    """ValueError naming the first key of `state` that `module` lacks, misses or holds with another shape; nothing is written."""
+    own = module.state_dict()
+    for key in list(own) + [k for k in state if k not in own]:
+        if key not in state:
+            raise ValueError(f'{what}: key {key!r} is missing')
+        if key not in own:
+            raise ValueError(f'{what}: unexpected key {key!r}')
+        if tuple(state[key].shape) != tuple(own[key].shape):
+            raise ValueError(f'{what}: key {key!r} has shape {tuple(state[key].shape)}, expected {tuple(own[key].shape)}')
 _EMB_PARAMS = NET_PARAMS - (128 * 4 + 4)      # trunk part of the flat buffer; the rest is the read-out
 
 
@@ -439,17 +452,38 @@ class MVVNeRFRenderer:
     def _split(self, flat):
         return flat[:_EMB_PARAMS], flat[_EMB_PARAMS:]
 
-    def store(self, path):
+    def _encoder_modules(self):
+        """The sub-models of `feature_encoder` that have files of their own (model_v4.py:196-240), by file name."""
+        enc = self.feature_encoder
+        missing = [name for name in ENCODER_SUBMODELS if not isinstance(getattr(enc, name, None), torch.nn.Module)]
+        if missing:
+            raise ValueError(f'encoders=True: feature_encoder ({type(enc).__name__}) has no sub-module {missing[0]!r} '
+                             '(expected e.g. an encoders.FeatureProducerV4)')
+        return {name: getattr(enc, name) for name in ENCODER_SUBMODELS}
+
+    def store(self, path, encoders=False):
+        """The four MLP files; with encoders=True also `{path}_visual_features.pt` and `{path}_combine_clip_visual.pt`, the CPU state
+        dicts of the feature encoder's sub-models - the six files of the reference's renderer, which `LanguageNeRF.load_backbone` reads."""
+        modules = self._encoder_modules() if encoders else {}
         parts = dict(zip(_SUBMODELS, (*self._split(self.coarse_net), *self._split(self.fine_net))))
         for name, t in parts.items():
             torch.save(t.detach().cpu(), f'{path}_{name}.pt')
+        for name, module in modules.items():
+            torch.save({k: v.detach().cpu().clone() for k, v in module.state_dict().items()}, f'{path}_{name}.pt')
 
-    def load(self, path, old=False):
+    def load(self, path, old=False, encoders=False):
+        """-> True, or False (nothing changed) if any file is missing: the four MLP files, with encoders=True the two encoder files too."""
+        modules = self._encoder_modules() if encoders else {}
         files = [f'{path}_{name}.pt' for name in _SUBMODELS]
-        if not all(os.path.exists(f) for f in files):
+        if not all(os.path.exists(f) for f in files + [f'{path}_{name}.pt' for name in modules]):
             return False
         ce, cr, fe, fr = [torch.load(f, weights_only=True) for f in files]
+        states = {name: torch.load(f'{path}_{name}.pt', weights_only=True) for name in modules}
+        for name, module in modules.items():                  # every key and shape before anything is written
+            check_state_dict(module, states[name], f'{path}_{name}.pt')
         self.set_weights(torch.cat([ce, cr]), torch.cat([fe, fr]))
+        for name, module in modules.items():
+            module.load_state_dict(states[name])
         return True
 
     def _dev(self, t):

@@ -1915,6 +1915,61 @@ def conv3x3_wgrad(x, g, act_in=None, amax_x=None, amax_g=None, want_bias=False, 
     return (dw, dbias) if want_bias else dw
 
 
+# ---- backward through a frozen 3x3 convolution of the language fusion (csrc/act_gate.hip) -----------------------------------
+ACT_GATE_MAX_IMAGES = 65535
+
+
+def act_gate(g, out, mul, act, out_d=None, amax_out=None):
+    """mvnerf_act_gate_nhwc: d = g * mul * act'(y) for out = act(y) * mul as :func:`conv3x3` wrote it, from `out` and `mul` alone:
+    where act(y) > 0 (out and mul of one sign) d = g * mul; else 0 for relu and g * (out + mul) for elu; mul == 0 gives exact zeros.
+    g, out (N,h,w,C) fp32 NHWC with C a multiple of 4; mul (N,C) or None (= 1); act: 0 | 'identity', 1 | 'relu', 2 | 'elu'.
+    out_d: like g, may be g itself (in place); allocated when missing.  amax_out: a (1,) device float that receives max |d| (zeroed
+    here; a NaN in d gives a NaN) - the `amax_a` of the data-gradient convolution that reads d.  Every argument is checked by name
+    before anything reaches the GPU."""
+    if not isinstance(act, int):
+        if act not in FUSE_ACTIVATIONS:
+            raise ValueError(f'act: {act!r}, expected one of {list(FUSE_ACTIVATIONS)} or 0, 1, 2')
+        act = FUSE_ACTIVATIONS[act]
+    if isinstance(act, bool) or not 0 <= act <= 2:
+        raise ValueError(f'act: {act!r}, expected 0, 1 or 2')
+    for t, name in ((g, 'g'), (out, 'out')):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'{name}: expected a torch.Tensor, got {type(t).__name__}')
+    if g.dim() != 4 or g.numel() == 0:
+        raise ValueError(f'g: shape {tuple(g.shape)}, expected (N, h, w, C) with at least one element')
+    n, h, w, c = g.shape
+    if c % 4:
+        raise ValueError(f'g: {c} channels, expected a multiple of 4')
+    if n > ACT_GATE_MAX_IMAGES or n * h * w > 0x7fffffff:
+        raise ValueError(f'g: shape {tuple(g.shape)}, expected at most {ACT_GATE_MAX_IMAGES} images and 2^31 - 1 pixels')
+    if tuple(out.shape) != (n, h, w, c):
+        raise ValueError(f'out: shape {tuple(out.shape)}, expected {(n, h, w, c)}')
+    if mul is not None and (not isinstance(mul, torch.Tensor) or tuple(mul.shape) != (n, c)):
+        raise ValueError(f'mul: shape {tuple(mul.shape) if isinstance(mul, torch.Tensor) else type(mul).__name__}, expected {(n, c)} or None')
+    if out_d is not None and (not isinstance(out_d, torch.Tensor) or tuple(out_d.shape) != (n, h, w, c)):
+        raise ValueError(f'out_d: shape {tuple(out_d.shape) if isinstance(out_d, torch.Tensor) else type(out_d).__name__}, expected {(n, h, w, c)}')
+    _chk(g, 'g')
+    _chk(out, 'out')
+    if mul is not None:
+        _chk(mul, 'mul')
+    if out_d is None:
+        out_d = torch.empty_like(g)
+    else:
+        _chk(out_d, 'out_d')
+    for t, name in ((g, 'g'), (out, 'out'), (mul, 'mul'), (out_d, 'out_d')):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f'{name}: must be 16-byte aligned')
+        if t is not None and t.device != g.device:
+            raise ValueError(f'{name}: on {t.device}, expected {g.device}')
+    if amax_out is not None:
+        _chk(amax_out, 'amax_out', shape=(1,))
+        amax_out.zero_()
+    with torch.cuda.device(g.device):
+        rc = _lib.lib().mvnerf_act_gate_nhwc(_p(g), _p(out), _p(mul), act, n, h * w, c, _p(out_d), _p(amax_out), _stream(g))
+    _lib.check(rc, 'act_gate')
+    return out_d
+
+
 def bn_finalize(stats, n, h, w, cout, eps=1e-3, out=None):
     """mvnerf_bn_finalize: the tile statistics of :func:`conv3x3` over an (n,h,w,cout) output -> (mean, rstd), each (cout,), rstd =
     1 / sqrt(biased variance + eps) over all n h w pixels.  out: a (2, cout) tensor to write them into.  No host read."""

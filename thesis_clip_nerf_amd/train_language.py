@@ -644,7 +644,12 @@ def main(argv=None):
     with_tokens = args.encoder == 'v4'
     if with_tokens:
         from .encoders import LanguageFeatureProducer
-        producer = LanguageFeatureProducer((height, width), fused_conv='auto' if args.fused_conv else False,
+        # a fusion file written by the renderer (use_dense=False: `Slice` has no variable) decides the producer's own setting
+        fusion_file = os.path.join(args.backbone_path, 'model_final_combine_clip_visual.pt')
+        combine_kw = None
+        if os.path.exists(fusion_file) and not any('.tile.dense.' in key for key in torch.load(fusion_file, weights_only=True)):
+            combine_kw = dict(use_dense=False)
+        producer = LanguageFeatureProducer((height, width), combine_kw=combine_kw, fused_conv='auto' if args.fused_conv else False,
                                            fused_visual='auto' if args.fused_visual else False,
                                            fused_vit='auto' if args.fused_vit else False).to(dev)
         train, valid = (EncodedLanguageDataset(d, producer, None if args.host_batches else dev) for d in (train, valid))
@@ -663,8 +668,11 @@ def main(argv=None):
     if args.init_backbone:
         os.makedirs(args.backbone_path, exist_ok=True)
         store_trunk(backbone, glorot_net(np.random.default_rng(0)))
-    if model.load_backbone(backbone):
-        print(f'Backbone loaded from {backbone}.')
+    # a renderer trained with `train_nerf --encoder v4` also left its two encoder files (MVVNeRFRenderer.store(encoders=True)): they go
+    # into the producer before it computes its first feature map (model_v4.py:132-152); without them the producer keeps its initial weights
+    encoder_files = with_tokens and all(os.path.exists(f'{backbone}_{name}.pt') for name in ('visual_features', 'combine_clip_visual'))
+    if model.load_backbone(backbone, producer=producer if encoder_files else None):
+        print(f'Backbone loaded from {backbone}' + (' (with visual_features and combine_clip_visual).' if encoder_files else '.'))
     else:
         raise FileNotFoundError(f'Model not found at {backbone}.')
     os.makedirs(f'{args.model_path}/valid', exist_ok=True)

@@ -7,7 +7,9 @@ replaced by explicit stand-ins:
 * the dataset submodule (`src/lib/dataset`, absent from the reference tree) -> :class:`SyntheticSceneDataset`,
   random views with known cameras;
 * the image encoders -> a fixed per-pixel feature map supplied by the dataset (`features`), since
-  `combined_features` is an *input* of the hot path;
+  `combined_features` is an *input* of the hot path; with `--encoder v0 | v4` the renderer runs and trains
+  `encoders.FeatureProducer` / `encoders.FeatureProducerV4` inside `train_step` instead (train_nerf.py:24-32) and writes the
+  reference's six sub-model files, which `LanguageNeRF.load_backbone(producer=...)` reads;
 * hydra -> keyword arguments / argparse; cv2 PNG dumps -> binary PPM files.
 
     python -m thesis_clip_nerf_amd.train_nerf --model-path /tmp/nerf_run --epochs 4 --eval-after 2
@@ -175,9 +177,31 @@ class MVNeRFDataGenerator:
 
 
 def compile_model(nerf_renderer, grad_sync=None):
-    """train_nerf.py:20-34: MSE; Adam with WarmupScheduler(1e-4, 10000, 450000) on the two embeddings."""
+    """train_nerf.py:20-34: MSE; Adam with WarmupScheduler(1e-4, 10000, 450000) on the two embeddings; where the renderer has a
+    feature encoder with `trainable_parameters()`, also `optimizer_feature` (encoders.make_encoder_optimizer: Keras Adam at 1e-5 with
+    the same warm-up on vision_transformer + conv_features), whose scheduler :func:`fit` steps after every train_step."""
+    encoder = getattr(nerf_renderer, 'feature_encoder', None)
+    optimizer = scheduler = None
+    if hasattr(encoder, 'trainable_parameters'):
+        from .encoders import make_encoder_optimizer
+        optimizer, scheduler = make_encoder_optimizer(encoder)
     nerf_renderer.compile(learning_rate=WarmupScheduler(1e-4, 10000, 450000), gradients_clip=1.0, train_readout=False,
-                          grad_sync=grad_sync)
+                          grad_sync=grad_sync, encoder_optimizer=optimizer)
+    nerf_renderer._encoder_scheduler = scheduler
+
+
+def trains_encoder(nerf_renderer):
+    """Whether :func:`fit` lets the renderer's own feature encoder produce (and learn) the feature maps."""
+    return getattr(nerf_renderer, 'feature_encoder', None) is not None and getattr(nerf_renderer, '_encoder_optimizer', None) is not None
+
+
+def encode_views(nerf_renderer, images):
+    """images (B,V,H,W,3) in [0,1] -> combined_features (B,V,H,W,256) from the renderer's feature encoder, without gradients."""
+    images = nerf_renderer._dev(images)
+    b, v = images.shape[:2]
+    with torch.no_grad():
+        feats = nerf_renderer.encode(images.reshape(b * v, *images.shape[2:]))
+    return feats.reshape(b, v, *feats.shape[1:])
 
 
 def init_training_session(model_log_dir):
@@ -192,13 +216,21 @@ def init_training_session(model_log_dir):
 
 def fit(nerf_renderer, data_generator, epochs, initial_epoch=0, log=print, keep=None):
     """Keras `Model.fit(generator, epochs=, initial_epoch=)` over the custom train_step.
-    keep: a dict that receives the last batch as keep['batch'] = (inputs, features) (train_model's range check reads it)."""
+    keep: a dict that receives the last batch as keep['batch'] = (inputs, features) (train_model's range check reads it).
+    A renderer compiled with an encoder optimizer (:func:`trains_encoder`) gets combined_features=None: its feature encoder runs inside
+    train_step and is trained there; the generator's feature maps are not used (features is None in keep['batch'] then)."""
     history = []
+    own_features = trains_encoder(nerf_renderer)
+    scheduler = getattr(nerf_renderer, '_encoder_scheduler', None) if own_features else None
     for epoch in range(initial_epoch, epochs):
         losses = []
         for step in range(len(data_generator)):
             (inputs, features), targets = data_generator[step]
+            if own_features:
+                features = None
             losses.append(nerf_renderer.train_step((inputs, targets), combined_features=features)['loss'])
+            if scheduler is not None:
+                scheduler.step()
             if keep is not None:
                 keep['batch'] = (inputs, features)
         data_generator.on_epoch_end()
@@ -214,7 +246,8 @@ def check_training_range(nerf_renderer, batch):
     forward on `batch` = (inputs, features) and raises FloatingPointError naming the limit; one host synchronisation."""
     if batch is None or getattr(nerf_renderer, 'f32_gemm', None) == 'mfma_f32' or getattr(nerf_renderer, 'range_policy', 'off') == 'off':
         return None
-    rep = nerf_renderer.check_range(batch[0], batch[1], training=True)
+    features = batch[1] if batch[1] is not None else encode_views(nerf_renderer, batch[0][2])
+    rep = nerf_renderer.check_range(batch[0], features, training=True)
     if not rep['in_range']:
         raise FloatingPointError(f"training has left the range of the fp16 backward (limit {rep['limit']:g}): {rep['message']}")
     return rep
@@ -227,8 +260,10 @@ def write_ppm(path, image):
 
 
 def validate(nerf_renderer, tgt_color, valid_data):
-    """train_nerf.py:68-81: [sources | target | rendered rgb | rendered depth] side by side."""
-    rgb, depth = render_view(nerf_renderer, **valid_data)
+    """train_nerf.py:68-81: [sources | target | rendered rgb | rendered depth] side by side.  Without `combined_features` in
+    valid_data the renderer's feature encoder produces them from the source views (no gradients)."""
+    with torch.no_grad():
+        rgb, depth = render_view(nerf_renderer, **valid_data)
     src = np.concatenate([c[..., :3] for c in valid_data['src_colors']], axis=1)
     return np.concatenate([src, tgt_color[..., :3], rgb, np.repeat(depth, 3, axis=2)], axis=1)
 
@@ -252,8 +287,39 @@ def train_model(nerf_renderer, data_generator, n_epochs, eval_after_epochs, mode
         write_ppm(f'{model_log_dir}/valid/valid-{e_epoch}.ppm', validate(nerf_renderer, tgt_color, valid_data))
         with open(training_progress_file, 'w') as f:
             json.dump({'epoch': e_epoch}, f)
-        nerf_renderer.store(model_checkpoint_name)
+        nerf_renderer.store(model_checkpoint_name, encoders=trains_encoder(nerf_renderer))
     return history
+
+
+# the test-size encoders of --tiny-encoder: a one-block-per-hook ViT on 32 x 32 crops and a fusion at the narrowest widths the HIP
+# convolutions take (multiples of 32 + 32 -> 64), for smoke runs and tests - nothing about them is the reference's
+TINY_VISUAL = dict(transformer_image_size=(32, 32), patch_size=16, embed_dim=32, num_heads=4, hooks=(1, 2, 3, 4), features=(4, 8, 16, 32))
+TINY_FUSION = dict(clip_channels=(32, 32, 32, 32), text_dim=64, widths=(64, 64, 64), up3_filters=64)
+TINY_N_FEATURES = 32
+
+
+def make_feature_encoder(kind, size, tiny=False, fused_conv=False, fused_backward=False, device='cuda:0'):
+    """--encoder: 'none' -> None (the dataset's feature maps), 'v0' -> encoders.FeatureProducer (CombineCLIPVisualV0),
+    'v4' -> encoders.FeatureProducerV4 (the language fusion with the all-ones text embedding).  size: (height, width)."""
+    from . import encoders as E
+    if kind == 'none':
+        return None
+    switch = 'auto' if fused_conv else False
+    if kind == 'v0':
+        visual = dict(TINY_VISUAL, n_features=TINY_N_FEATURES) if tiny else {}
+        producer = E.FeatureProducer(size, fused_conv=switch, fused_backward=fused_backward, **visual)
+        producer.combine_clip_visual.requires_grad_(False)
+        if fused_backward:
+            producer.combine_clip_visual.fused_tail, producer.combine_clip_visual.fused_backward = 'auto', True
+        return producer.to(device)
+    if kind != 'v4':
+        raise ValueError(f"encoder: {kind!r}, expected 'none', 'v0' or 'v4'")
+    kw = dict(fused_conv=switch, fused_visual=switch, fused_backward=fused_backward)
+    if tiny:
+        sizes = tuple((max(1, size[0] // s), max(1, size[1] // s)) for s in (4, 8, 16, 32))
+        kw.update(n_features=TINY_N_FEATURES, combine_kw=TINY_FUSION, **TINY_VISUAL,
+                  clip_pyramid=E.SyntheticCLIPPyramid(TINY_FUSION['clip_channels'], sizes, TINY_FUSION['text_dim']))
+    return E.FeatureProducerV4(size, **kw).to(device)
 
 
 def main(argv=None):
@@ -266,7 +332,21 @@ def main(argv=None):
     ap.add_argument('--n-rays', type=int, default=512)
     ap.add_argument('--size', type=int, default=32)
     ap.add_argument('--host-batches', action='store_true', help='assemble batches in NumPy on the host (default: on the GPU)')
+    ap.add_argument('--encoder', default='none', choices=['none', 'v0', 'v4'],
+                    help="where combined_features come from: 'none' the dataset's fixed maps; 'v0' encoders.FeatureProducer, 'v4' "
+                         'encoders.FeatureProducerV4 - the renderer then runs and trains its visual encoder inside train_step '
+                         '(train_nerf.py:24-32) and writes visual_features / combine_clip_visual files next to the four MLP files')
+    ap.add_argument('--fused-conv', action='store_true',
+                    help="with --encoder v0 | v4: the encoders' 3x3 convolutions as HIP launches (fused_conv='auto'; csrc/conv3x3.hip)")
+    ap.add_argument('--fused-backward', action='store_true',
+                    help='with --fused-conv: the same convolutions and the fused tail stay HIP under gradients '
+                         '(csrc/conv3x3_bwd.hip, csrc/act_gate.hip, csrc/feature_tail_bwd.hip)')
+    ap.add_argument('--tiny-encoder', action='store_true', help='with --encoder v0 | v4: test-size widths (TINY_VISUAL, TINY_FUSION)')
     args = ap.parse_args(argv)
+    if args.encoder == 'none' and (args.fused_conv or args.fused_backward or args.tiny_encoder):
+        ap.error('--fused-conv, --fused-backward and --tiny-encoder need --encoder v0 or v4')
+    if args.fused_backward and not args.fused_conv:
+        ap.error('--fused-backward needs --fused-conv')
     train = SyntheticSceneDataset(n_scenes=8, height=args.size, width=args.size, seed=0)
     valid = SyntheticSceneDataset(n_scenes=1, height=args.size, width=args.size, seed=1)
     src = list(range(args.n_views))
@@ -277,11 +357,14 @@ def main(argv=None):
                   'combined_features': torch.from_numpy(np.array([[valid.features[0][i] for i in src]], dtype=np.float32))}
     gen = MVNeRFDataGenerator(train, n_rays_train=args.n_rays, batch_size=args.batch_size, n_views=args.n_views,
                               device=None if args.host_batches else 'cuda:0')
-    model = MVVNeRFRenderer(args.n_rays, 512, n_views=args.n_views, batch_size=args.batch_size, near=0.3, far=1.3)
+    encoder = make_feature_encoder(args.encoder, (args.size, args.size), args.tiny_encoder, args.fused_conv, args.fused_backward)
+    if encoder is not None:
+        del valid_data['combined_features']                  # validate(): the encoder's own maps of the source views
+    model = MVVNeRFRenderer(args.n_rays, 512, n_views=args.n_views, batch_size=args.batch_size, near=0.3, far=1.3, feature_encoder=encoder)
     compile_model(model)
     ckpt = f'{args.model_path}/model_final'
     os.makedirs(args.model_path, exist_ok=True)
-    print('Model loaded from checkpoint.' if model.load(ckpt) else 'New model initialized')
+    print('Model loaded from checkpoint.' if model.load(ckpt, encoders=encoder is not None) else 'New model initialized')
     train_model(model, gen, args.epochs, args.eval_after, args.model_path, ckpt, valid_data)
 
 
